@@ -179,27 +179,76 @@ def extras(g, args, k, L, genome_len, reads_per_rank):
     return out
 
 
+def c64(v):
+    """A 64-bit constant as the int64 with the same bits."""
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def srl33(x):
+    """Logical shift right by 33 of an int64 tensor."""
+    return (x >> 33) & ((1 << 31) - 1)
+
+
+def mix(x):
+    """The 64-bit finaliser of oracle/orc_c.digest on int64 tensors (the arithmetic wraps like uint64)."""
+    x = x ^ srl33(x)
+    x = x * c64(0xff51afd7ed558ccd)
+    x = x ^ srl33(x)
+    x = x * c64(0xc4ceb9fe1a85ec53)
+    return x ^ srl33(x)
+
+
 def node_digest_gpu(g):
     """The node digest of oracle/orc_c.digest, computed on the device with torch (int64 arithmetic wraps like uint64)."""
     import torch
     nodes = g.node_tensors()
     keys, stamps, counts = nodes["keys"], nodes["stamps"], nodes["counts"].view(-1, 4).to(torch.int64) & 0xFFFFFFFF
-
-    def c64(v):  # a 64-bit constant as the int64 with the same bits
-        return v - (1 << 64) if v >= (1 << 63) else v
-
-    def srl33(x):  # logical shift right by 33 on int64
-        return (x >> 33) & ((1 << 31) - 1)
-
-    def mix(x):
-        x = x ^ srl33(x)
-        x = x * c64(0xff51afd7ed558ccd)
-        x = x ^ srl33(x)
-        x = x * c64(0xc4ceb9fe1a85ec53)
-        return x ^ srl33(x)
-
     w = counts[:, 0] + 3 * counts[:, 1] + 5 * counts[:, 2] + 7 * counts[:, 3] + 1
     return int(mix(keys ^ mix(stamps) ^ mix(w)).sum().item()) & ((1 << 64) - 1)
+
+
+DUMP_NODES = 1 << 18   # nodes in the sample --dump-outputs writes (13 float64 columns at most: 27 MB)
+DUMP_SEED = 0x9e3779b97f4a7c15
+DUMP_SIZES = ("n_reads", "n_bytes", "n_kmer_instances", "n_edge_instances", "n_nodes", "n_edges", "max_degree")
+
+
+def split32(x):
+    """An int64 tensor as two float64 columns (high and low 32 bits, each exact), for keys beyond float64's 53 bits."""
+    import torch
+    return torch.stack([((x >> 32) & 0xFFFFFFFF).double(), (x & 0xFFFFFFFF).double()], dim=1)
+
+
+def dump_outputs(g, out_dir):
+    """What a caller of the timed path receives from the graph it just built, as float64 .npy files under `out_dir`:
+    the graph's totals (sizes.npy, in the order of DUMP_SIZES) and a fixed sample of its nodes.  The sample is every
+    node whose seeded hash of its k-mer falls below a threshold (about 2 x DUMP_NODES of them), in ascending stamp
+    order (the first occurrence in the reads: dict order), cut to DUMP_NODES -- it depends on the graph only, never
+    on the order in which the table holds its nodes.  Per sampled node: the k-mer as 32-bit halves (low word, then
+    the high word of two-word k-mers), the stamp, the 4 successor counts by base code and, for every base, the stamp
+    of the successor node (-1: none) in place of its table position."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    sz = g.sizes()
+    np.save(os.path.join(out_dir, "sizes.npy"), np.array([float(sz[key]) for key in DUMP_SIZES], dtype=np.float64))
+    nodes = g.node_tensors()
+    keys, stamps = nodes["keys"], nodes["stamps"]
+    n = int(keys.numel())
+    h = mix(keys ^ c64(DUMP_SEED)) if "keys_hi" not in nodes else mix(keys ^ mix(nodes["keys_hi"] ^ c64(DUMP_SEED)))
+    bound = min(1 << 24, -(-(2 * DUMP_NODES << 24) // max(n, 1)))  # on the top 24 bits of the hash
+    sel = torch.nonzero(((h >> 40) & 0xFFFFFF) < bound).flatten()
+    sel = sel[torch.argsort(stamps[sel])][:DUMP_NODES]
+    key_cols = [split32(keys[sel])] + ([split32(nodes["keys_hi"][sel])] if "keys_hi" in nodes else [])
+    counts = nodes["counts"].view(-1, 4)[sel].to(torch.int64) & 0xFFFFFFFF
+    succ = nodes["succ"].view(-1, 4)[sel].to(torch.int64) & 0xFFFFFFFF
+    present = succ != 0xFFFFFFFF
+    succ_stamp = torch.where(present, stamps[torch.where(present, succ, 0)], -1)
+    out = {"node_keys": torch.cat(key_cols, dim=1), "node_stamps": stamps[sel].double(), "node_counts": counts.double(),
+           "node_succ_stamps": succ_stamp.double()}
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    del nodes, keys, stamps, h, sel, out
+    torch.cuda.empty_cache()
 
 
 def cpu_baseline(g, read_len, k, n_reads, gpu_sizes, gpu_digest):
@@ -290,7 +339,11 @@ def main():
                     "exchange of one under the extraction of the next (multi_gpu._exchange_records_in_parts); 1 = one exchange")
     ap.add_argument("--table-hint", type=int, default=0)
     ap.add_argument("--no-extras", action="store_true", help="skip the untimed extras (rest of the path, error-free variant)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one built as DIR/<name>.npy (float64; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -306,6 +359,8 @@ def main():
     dist = None
     force_sharded = os.environ.get("BENCH_FORCE_SHARDED", "") == "1"  # 1-rank rehearsal of the RCCL path
     sharded = world > 1 or force_sharded or args.scaling == "strong"
+    if sharded and args.dump_outputs:
+        sys.exit("--dump-outputs: the single-table path only (--gpus 1, --scaling weak)")
     if sharded:
         import torch.distributed as dist
         # BENCH_BACKEND=gloo BENCH_SAME_GPU=1: rehearsal of the N>1 path on a one-GPU box (not a measurement)
@@ -373,6 +428,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if dist.get_backend() == "gloo" else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs:  # untimed: the graph of the last timed step, before anything below rebuilds or changes it
+        dump_outputs(built, args.dump_outputs)
 
     # the first build on a read set also scans it for its alphabet (cached per read set): what the multi-k driver pays
     # after every `sequences.extend(...)`; the timed steps above are the steady state
