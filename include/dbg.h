@@ -47,7 +47,7 @@ typedef struct dbg dbg_t;
 #define DBG_E_CAPACITY (-4) /* hash table or an output limit was exceeded */
 #define DBG_E_NOMEM (-5)    /* host or device allocation failed */
 
-#define DBG_ABI_VERSION 5
+#define DBG_ABI_VERSION 6
 
 /* node flag bits (dbg_export_nodes: flags[]) */
 #define DBG_F_INDEG 0x01u    /* Node.indegree (0 or 1), debruijn.py:134,141-142 */
@@ -101,6 +101,21 @@ typedef struct dbg_stats {
     uint64_t n_queries;      /* engine 0: successors resolved across buckets */
 } dbg_stats_t;
 
+/* what the last FASTA ingest (dbg_set_reads_fasta_file, or dbg_set_reads_fasta: one chunk) did */
+typedef struct dbg_ingest_stats {
+    uint64_t bytes_read;        /* file bytes read (the owned lines, the byte before `begin`, the read-ahead of the last chunk) */
+    uint64_t chunks;            /* staging chunks copied to the device */
+    uint64_t chunk_bytes;       /* size of a staging buffer */
+    uint64_t peak_device_bytes; /* most device memory the ingest held at once: text, parse scratch, bases, offsets (the
+                                 * read-start bitmap every read set gets is not counted) */
+    uint64_t n_reads;
+    uint64_t n_bases;
+    double ms_total;            /* wall time of the call */
+    double ms_io_wait;          /* host time spent in file reads */
+    double ms_h2d;              /* device time of the staging copies */
+    double ms_parse;            /* device time of the parse kernels */
+} dbg_ingest_stats_t;
+
 /* ---- lifetime ---------------------------------------------------------- */
 int dbg_create(int device, dbg_t **out);
 void dbg_destroy(dbg_t *h);
@@ -132,6 +147,17 @@ int dbg_set_reads(dbg_t *h, const char *bases, const uint64_t *offsets, uint64_t
  * does not start with '>' becomes one read, rstrip'ed (universal newlines, multi-line records are separate
  * reads, blank lines are empty reads).  Sizes afterwards: dbg_get_sizes; the reads: dbg_copy_reads. */
 int dbg_set_reads_fasta(dbg_t *h, const char *text, uint64_t n_text);
+/* Reads of the lines whose FIRST byte lies in [begin, end) of the file at `path` (end = UINT64_MAX: to EOF), with
+ * dbg_set_reads_fasta semantics.  A line that starts inside the range is read to its terminator, even past `end`.
+ * Byte p starts a line iff p == 0, t[p-1] == '\n', or t[p-1] == '\r' and t[p] != '\n' (universal newlines), so the
+ * reads of [0, b) followed by those of [b, n) are the reads of the whole file for every b.
+ * The file streams through two pinned staging buffers of chunk_bytes (0 = library default, 16 MiB); the host reads
+ * chunk i+1 while chunk i is copied and parsed on the device.  Neither the host nor the device ever holds the whole
+ * image: the device holds the packed bases (sized from the range), the offsets (grown as reads arrive) and ~1.5 chunks
+ * of parse state.  DBG_E_ARG (text in dbg_last_error) for a missing or unreadable file or begin > end; a begin at or
+ * past the end of the file gives an empty read set. */
+int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t begin, uint64_t end, uint64_t chunk_bytes);
+int dbg_fasta_ingest_stats(dbg_t *h, dbg_ingest_stats_t *out);
 /* Zero-copy: device pointers the caller keeps alive (16-byte aligned bases, u64 offsets[n_reads+1]). */
 int dbg_set_reads_device(dbg_t *h, const void *d_bases, uint64_t n_bytes, const void *d_offsets, uint64_t n_reads);
 /* Generate reads [first_read, first_read+n_reads) of the synthetic set on the device

@@ -17,12 +17,12 @@ LIB_PATH = os.environ.get("DBG_LIB") or os.path.join(_HERE, "libdbg_hip.so")  # 
 DBG_OK, DBG_E_ARG, DBG_E_HIP, DBG_E_ALPHABET, DBG_E_CAPACITY, DBG_E_NOMEM = 0, -1, -2, -3, -4, -5
 F_INDEG, F_KEEP_MASK, F_KEEP_SHIFT, F_BRANCH, F_PULLED = 0x01, 0x1E, 1, 0x20, 0x40
 NO_NODE = 0xFFFFFFFF
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # symbols declared in include/dbg.h; tests check that the library exports every one of them
 SYMBOLS = (
     "dbg_create", "dbg_destroy", "dbg_last_error", "dbg_abi_version", "dbg_set_option", "dbg_set_reads", "dbg_set_reads_fasta",
-    "dbg_set_reads_device",
+    "dbg_set_reads_fasta_file", "dbg_fasta_ingest_stats", "dbg_set_reads_device",
     "dbg_synth_reads", "dbg_reads_checksum", "dbg_copy_reads", "dbg_reads_device", "dbg_build", "dbg_refine_edge_order", "dbg_export_orders",
     "dbg_get_alphabet", "dbg_export_keepmask", "dbg_export_dict_order",
     "dbg_prune", "dbg_remove_tips",
@@ -55,6 +55,15 @@ class Stats(C.Structure):
         "ms_startbits", "ms_table_init", "ms_count", "ms_compact", "ms_succ", "ms_csr", "ms_build_total", "ms_prune",
         "ms_tips", "ms_pull_reads", "ms_walk", "ms_h2d", "ms_extract", "ms_partition")] + [
         (n, C.c_uint64) for n in ("count_launches", "n_records", "n_buckets", "n_queries")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class IngestStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "bytes_read", "chunks", "chunk_bytes", "peak_device_bytes", "n_reads", "n_bases")] + [
+        (n, C.c_double) for n in ("ms_total", "ms_io_wait", "ms_h2d", "ms_parse")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -100,6 +109,8 @@ def load_library():
         "dbg_set_option": (C.c_int, [H, C.c_char_p, C.c_int64]),
         "dbg_set_reads": (C.c_int, [H, vp, vp, C.c_uint64]),
         "dbg_set_reads_fasta": (C.c_int, [H, vp, C.c_uint64]),
+        "dbg_set_reads_fasta_file": (C.c_int, [H, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64]),
+        "dbg_fasta_ingest_stats": (C.c_int, [H, C.POINTER(IngestStats)]),
         "dbg_set_reads_device": (C.c_int, [H, vp, C.c_uint64, vp, C.c_uint64]),
         "dbg_synth_reads": (C.c_int, [H, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]),
         "dbg_reads_checksum": (C.c_int, [H, u64p]),
@@ -243,6 +254,20 @@ class Graph:
             raw = np.fromfile(path_or_bytes, dtype=np.uint8)
         self.generation += 1
         self._chk(self._lib.dbg_set_reads_fasta(self._h, _ptr(raw) if raw.size else None, raw.size))
+
+    def set_reads_fasta_file(self, path, begin=0, end=None, chunk_bytes=0):
+        """Streams the lines of ``path`` that start in bytes [begin, end) (end None: to the end of the file) through
+        pinned staging chunks of ``chunk_bytes`` (0: library default) and parses them on the GPU (``set_reads_fasta``
+        semantics).  Neither the host nor the device holds the whole file."""
+        end = (1 << 64) - 1 if end is None else int(end)
+        self.generation += 1
+        self._chk(self._lib.dbg_set_reads_fasta_file(self._h, os.fsencode(path), int(begin), end, int(chunk_bytes)))
+
+    def ingest_stats(self):
+        """What the last FASTA ingest did: bytes read, chunks, peak device bytes, ms in file reads / H2D / parse."""
+        out = IngestStats()
+        self._chk(self._lib.dbg_fasta_ingest_stats(self._h, C.byref(out)))
+        return out.as_dict()
 
     def set_reads_device(self, bases_ptr, n_bytes, offsets_ptr, n_reads, keepalive=()):
         self._keep = list(keepalive)

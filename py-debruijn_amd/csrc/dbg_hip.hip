@@ -19,6 +19,11 @@
 #include <string>
 #include <vector>
 
+#include <cerrno>
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 #include <rocprim/device/device_radix_sort.hpp>  // library sorts off the timed path: dbg_export_dict_order, dbg_export_marked, dbg_support_read_scores, dbg_export_sorted_fasta
 
 #include "../../include/dbg.h"
@@ -32,6 +37,7 @@
 #include "dbg_wide.h"
 #include "dbg_support.h"
 #include "dbg_wsk.h"
+#include "dbg_fasta.h"
 
 using namespace dbgk;
 
@@ -163,6 +169,7 @@ struct dbg {
     uint64_t btab_cap = 0;
 
     dbg_stats_t stats{};
+    dbg_ingest_stats_t ingest{};  // the last FASTA ingest
 };
 
 // What a sharded build leaves behind for the exchange of successors owned by other ranks.
@@ -1714,10 +1721,285 @@ extern "C" int dbg_set_reads_fasta(dbg_t *h, const char *text, uint64_t n_text) 
             hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "FASTA ingest failed on the device"; rc = DBG_E_HIP; break; }
         h->n_bytes = n_bases;
         h->n_reads = n_reads;
+        const uint64_t n_words_ = (n_text + 31) / 32;
+        h->ingest = dbg_ingest_stats_t{};
+        h->ingest.bytes_read = n_text;
+        h->ingest.chunks = 1;
+        h->ingest.chunk_bytes = n_text;
+        h->ingest.peak_device_bytes = (n_text + 64) + 8 * std::max<uint64_t>(n_words_, 1) + 29 * std::max<uint64_t>(n_lines, 1) +
+                                      (n_bases + 64) + 8 * (n_reads + 1);  // everything above is alive here at once
+        h->ingest.n_reads = n_reads;
+        h->ingest.n_bases = n_bases;
+        h->ingest.ms_h2d = h->stats.ms_h2d;
     } while (0);
     cleanup();
     if (rc != DBG_OK) { free_reads(h); return rc; }
     return make_startbits(h);
+}
+
+// ------------------------------------------------------------------------------------------
+// chunked FASTA ingest from a file (kernels: dbg_fasta.h).  Two pinned staging buffers: the host reads chunk i+1 while
+// chunk i is copied and parsed on the handle's stream; the stream state (byte cursor, read count, the line open at the
+// chunk border) stays on the device, double-buffered so that a chunk can run again after the offsets have grown.
+// ------------------------------------------------------------------------------------------
+constexpr uint64_t FS_DEFAULT_CHUNK = 16ull << 20;
+constexpr uint64_t FS_MAX_CHUNK = 1ull << 30;  // the per-chunk counts of FsPopcPair are 32-bit
+
+static int64_t pread_full(int fd, char *buf, uint64_t len, uint64_t off) {  // short only at the end of the file
+    uint64_t got = 0;
+    while (got < len) {
+        const ssize_t r = pread(fd, buf + got, std::min<uint64_t>(len - got, 1ull << 30), (off_t)(off + got));
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            return -1;
+        }
+        if (r == 0) break;
+        got += (uint64_t)r;
+    }
+    return (int64_t)got;
+}
+
+namespace {
+struct FastaStream {
+    struct HostView {
+        FsState st;
+        uint64_t flags;
+    };
+    dbg *h;
+    int fd = -1;
+    char *pin[2] = {nullptr, nullptr};
+    HostView *hv = nullptr;  // pinned: the state after the last chunk
+    hipEvent_t ev_copy[2] = {nullptr, nullptr}, ev_t0 = nullptr, ev_done = nullptr;
+    char *d_text = nullptr;
+    uint32_t *d_wr = nullptr, *d_rs = nullptr;
+    uint64_t *d_rank = nullptr, *d_flags = nullptr;
+    uint8_t *d_blk = nullptr;
+    FsState *d_state = nullptr;
+    FsChunk *d_chunk = nullptr;
+    char *bases = nullptr;
+    uint64_t *offsets = nullptr;
+    uint64_t bases_cap = 0, off_cap = 0;  // usable bytes (the allocation has 64 more) / entries
+    uint64_t stage = 0, words_cap = 0, nblk_cap = 0;
+    uint64_t cur = 0, peak = 0;           // device bytes held by the ingest
+
+    explicit FastaStream(dbg *hh) : h(hh) {}
+    template <class T>
+    int alloc(T **p, uint64_t count) {
+        CHK(dev_alloc(h, p, count));
+        cur += std::max<uint64_t>(count, 1) * sizeof(T);
+        peak = std::max(peak, cur);
+        return DBG_OK;
+    }
+    template <class T>
+    void release(T *&p, uint64_t count) {
+        if (p) cur -= std::max<uint64_t>(count, 1) * sizeof(T);
+        dev_free(p);
+    }
+    template <class T>
+    int grow(T *&p, uint64_t &cap, uint64_t new_cap, uint64_t keep, uint64_t pad) {  // keep: elements to carry over
+        T *q = nullptr;
+        CHK(alloc(&q, new_cap + pad));
+        if (keep) HIPCHK(h, hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+        release(p, cap + pad);
+        p = q;
+        cap = new_cap;
+        return DBG_OK;
+    }
+    ~FastaStream() {
+        (void)hipStreamSynchronize(h->stream);
+        if (fd >= 0) close(fd);
+        for (auto &p : pin) if (p) (void)hipHostFree(p);
+        if (hv) (void)hipHostFree(hv);
+        for (auto e : {ev_copy[0], ev_copy[1], ev_t0, ev_done}) if (e) (void)hipEventDestroy(e);
+        dev_free(d_text); dev_free(d_wr); dev_free(d_rs); dev_free(d_rank); dev_free(d_flags); dev_free(d_blk);
+        dev_free(d_state); dev_free(d_chunk); dev_free(bases); dev_free(offsets);
+        (void)hipGetLastError();
+    }
+};
+}  // namespace
+
+static int fasta_parse_chunk(FastaStream &fs, uint64_t n, int si) {
+    dbg *h = fs.h;
+    const uint64_t words = (n + 31) / 32, nblk = (words + FS_WPB - 1) / FS_WPB;
+    const FsState *in = fs.d_state + si;
+    uint8_t *blk_f = fs.d_blk, *blk_b = fs.d_blk + fs.nblk_cap;
+    hipLaunchKernelGGL(k_fs_blocks, dim3((unsigned)nblk), dim3(256), 0, h->stream, fs.d_text, n, in, blk_f, blk_b);
+    hipLaunchKernelGGL(k_fs_carry, dim3(1), dim3(256), 0, h->stream, blk_f, blk_b, nblk, in, fs.d_chunk);
+    hipLaunchKernelGGL(k_fs_count, dim3((unsigned)nblk), dim3(256), 0, h->stream, fs.d_text, n, in, (const uint8_t *)blk_f,
+                       (const uint8_t *)blk_b, fs.d_wr, fs.d_rs, fs.d_chunk);
+    CHK(exclusive_scan(h, words, FsPopcPair{fs.d_wr, fs.d_rs}, fs.d_rank, (uint64_t *)nullptr));
+    const uint64_t *total = (const uint64_t *)h->ar_scan.p + std::max<uint64_t>((words + SCAN_TILE - 1) / SCAN_TILE, 1);
+    hipLaunchKernelGGL(k_fs_write, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, fs.d_text, n, in,
+                       (const FsChunk *)fs.d_chunk, (const uint32_t *)fs.d_wr, (const uint32_t *)fs.d_rs,
+                       (const uint64_t *)fs.d_rank, fs.bases, fs.bases_cap, fs.offsets, fs.off_cap, fs.d_flags);
+    hipLaunchKernelGGL(k_fs_finish, dim3(1), dim3(64), 0, h->stream, fs.d_text, n, in, (const FsChunk *)fs.d_chunk, total,
+                       fs.d_state + (si ^ 1));
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(&fs.hv->st, fs.d_state + (si ^ 1), sizeof(FsState), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&fs.hv->flags, fs.d_flags, 8, hipMemcpyDeviceToHost, h->stream));
+    return DBG_OK;
+}
+
+extern "C" int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t begin, uint64_t end, uint64_t chunk_bytes) {
+    if (!h) return DBG_E_ARG;
+    using clk = std::chrono::steady_clock;
+    const auto t_call = clk::now();
+    if (!path) { h->err = "set_reads_fasta_file: no path"; return DBG_E_ARG; }
+    if (begin > end) {
+        h->err = "set_reads_fasta_file: begin " + std::to_string(begin) + " > end " + std::to_string(end);
+        return DBG_E_ARG;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    FastaStream fs(h);
+    fs.fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fs.fd < 0) { h->err = std::string(path) + ": " + strerror(errno); return DBG_E_ARG; }
+    struct stat sb;
+    if (fstat(fs.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { h->err = std::string(path) + ": not a readable regular file"; return DBG_E_ARG; }
+    const uint64_t size = (uint64_t)sb.st_size;
+    const uint64_t lim = std::min(end, size);      // line starts at or past lim are not owned: they end the last owned line
+    const uint64_t start = std::min(begin, size);
+    uint32_t prev = '\n';                          // before the file: byte 0 starts a line
+    if (start > 0 && start < size) {
+        char c;
+        if (pread_full(fs.fd, &c, 1, start - 1) != 1) { h->err = std::string(path) + ": read failed: " + strerror(errno); return DBG_E_ARG; }
+        prev = (uint8_t)c;
+    }
+    uint64_t chunk = chunk_bytes ? std::min(chunk_bytes, FS_MAX_CHUNK) : FS_DEFAULT_CHUNK;
+    free_build(h);
+    free_reads(h);
+    h->ingest = dbg_ingest_stats_t{};
+    h->ingest.chunk_bytes = chunk;
+    h->ingest.bytes_read = (start > 0 && start < size) ? 1 : 0;
+
+    // staging and parse state for chunks of up to `stage` bytes
+    fs.stage = std::max<uint64_t>(std::min(chunk, size - start), 1);
+    fs.words_cap = (fs.stage + 31) / 32;
+    fs.nblk_cap = (fs.words_cap + FS_WPB - 1) / FS_WPB;
+    for (auto &p : fs.pin) HIPCHK(h, hipHostMalloc((void **)&p, fs.stage, hipHostMallocDefault));
+    HIPCHK(h, hipHostMalloc((void **)&fs.hv, sizeof(FastaStream::HostView), hipHostMallocDefault));
+    for (auto *e : {&fs.ev_copy[0], &fs.ev_copy[1], &fs.ev_t0, &fs.ev_done}) HIPCHK(h, hipEventCreate(e));
+    CHK(fs.alloc(&fs.d_text, fs.stage + 64));
+    CHK(fs.alloc(&fs.d_wr, fs.words_cap));
+    CHK(fs.alloc(&fs.d_rs, fs.words_cap));
+    CHK(fs.alloc(&fs.d_rank, fs.words_cap));
+    CHK(fs.alloc(&fs.d_blk, 2 * fs.nblk_cap));
+    CHK(fs.alloc(&fs.d_state, 2));
+    CHK(fs.alloc(&fs.d_chunk, 1));
+    CHK(fs.alloc(&fs.d_flags, 1));
+    fs.cur += (std::max<uint64_t>((fs.words_cap + SCAN_TILE - 1) / SCAN_TILE, 1) + 1) * 8;  // scan partials (handle arena)
+    fs.peak = std::max(fs.peak, fs.cur);
+    // the packed bases of a range are at most its length; the offsets start small and grow as reads arrive
+    fs.bases_cap = lim > start ? lim - start : 0;
+    CHK(fs.alloc(&fs.bases, fs.bases_cap + 64));
+    fs.off_cap = std::min<uint64_t>(1 << 16, fs.bases_cap + 2);
+    CHK(fs.alloc(&fs.offsets, fs.off_cap));
+    HIPCHK(h, hipMemsetAsync(fs.d_flags, 0, 8, h->stream));
+    for (auto e : fs.ev_copy) HIPCHK(h, hipEventRecord(e, h->stream));  // "buffer free" holds from the start
+    fs.hv->st = FsState{0, 0, 0, prev, 0};
+    HIPCHK(h, hipMemcpyAsync(fs.d_state, &fs.hv->st, sizeof(FsState), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+
+    uint64_t stop = lim >= size ? size : UINT64_MAX;  // first line start at or past lim (UINT64_MAX: not seen yet)
+    uint32_t host_prev = prev;                         // the byte before the next chunk
+    double ms_io = 0;
+    auto read_chunk = [&](int b, uint64_t pos, uint64_t &len) -> int {
+        const uint64_t limit = stop == UINT64_MAX ? size : stop;
+        len = pos < limit ? std::min(fs.stage, limit - pos) : 0;
+        if (!len) return DBG_OK;
+        const auto t0 = clk::now();
+        const int64_t got = pread_full(fs.fd, fs.pin[b], len, pos);
+        ms_io += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+        if (got < 0) { h->err = std::string(path) + ": read failed: " + strerror(errno); return DBG_E_ARG; }
+        len = (uint64_t)got;  // short: the file ended early
+        h->ingest.bytes_read += len;
+        if (stop == UINT64_MAX && pos + len > lim) {  // the last owned line ends at the first line start at or past lim
+            for (uint64_t p = std::max(lim, pos); p < pos + len; ++p) {
+                const uint32_t pv = p == pos ? host_prev : (uint8_t)fs.pin[b][p - pos - 1], c = (uint8_t)fs.pin[b][p - pos];
+                if (pv == '\n' || (pv == '\r' && c != '\n')) { stop = p; break; }
+            }
+            if (stop != UINT64_MAX) len = stop - pos;
+        }
+        if (len) host_prev = (uint8_t)fs.pin[b][len - 1];
+        return DBG_OK;
+    };
+    const double range_len = (double)(lim > start ? lim - start : 0);
+    auto offsets_for = [&](uint64_t n_reads, uint64_t done, uint64_t at_least) {  // amortised: 1.5x, or the projection
+        const double proj = done ? (double)n_reads * std::max(range_len, (double)done) / (double)done * 1.05 + 1024 : 0;
+        return std::max<uint64_t>({at_least, fs.off_cap + fs.off_cap / 2, (uint64_t)proj});
+    };
+
+    uint64_t len[2] = {0, 0}, pos = start;
+    CHK(read_chunk(0, pos, len[0]));
+    FsState hs = fs.hv->st;
+    int b = 0, si = 0;
+    double ms_h2d = 0, ms_parse = 0;
+    while (len[b] > 0) {
+        const uint64_t n = len[b], done = pos - start;
+        if (hs.cursor + hs.pend + n > fs.bases_cap)  // only a last line that runs far past `end`
+            CHK(fs.grow(fs.bases, fs.bases_cap, std::max(hs.cursor + hs.pend + n, fs.bases_cap + fs.bases_cap / 2),
+                        hs.cursor + hs.pend, 64));
+        if (done) {  // the offsets this chunk will likely need, at the read density seen so far
+            const uint64_t est = hs.n_reads + (uint64_t)((double)hs.n_reads * n / done * 1.25) + 64;
+            if (est + 1 > fs.off_cap) CHK(fs.grow(fs.offsets, fs.off_cap, offsets_for(hs.n_reads, done, est + 1), hs.n_reads, 0));
+        }
+        HIPCHK(h, hipEventRecord(fs.ev_t0, h->stream));
+        HIPCHK(h, hipMemcpyAsync(fs.d_text, fs.pin[b], n, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipEventRecord(fs.ev_copy[b], h->stream));
+        CHK(fasta_parse_chunk(fs, n, si));
+        HIPCHK(h, hipEventRecord(fs.ev_done, h->stream));
+        // the other buffer is free once its copy (chunk i-1) has completed: read chunk i+1 into it meanwhile
+        const uint64_t npos = pos + n;
+        HIPCHK(h, hipEventSynchronize(fs.ev_copy[b ^ 1]));
+        CHK(read_chunk(b ^ 1, npos, len[b ^ 1]));
+        HIPCHK(h, hipEventSynchronize(fs.ev_done));
+        float a = 0, c = 0;
+        (void)hipEventElapsedTime(&a, fs.ev_t0, fs.ev_copy[b]);
+        (void)hipEventElapsedTime(&c, fs.ev_copy[b], fs.ev_done);
+        ms_h2d += a;
+        ms_parse += c;
+        if (fs.hv->st.n_reads + 1 > fs.off_cap) {  // more reads than the estimate: grow and parse the chunk again
+            CHK(fs.grow(fs.offsets, fs.off_cap, offsets_for(hs.n_reads, done + n, fs.hv->st.n_reads + 1), hs.n_reads, 0));
+            HIPCHK(h, hipEventRecord(fs.ev_t0, h->stream));
+            CHK(fasta_parse_chunk(fs, n, si));
+            HIPCHK(h, hipEventRecord(fs.ev_done, h->stream));
+            HIPCHK(h, hipEventSynchronize(fs.ev_done));
+            (void)hipEventElapsedTime(&c, fs.ev_t0, fs.ev_done);
+            ms_parse += c;
+        }
+        if (fs.hv->flags) { h->err = "set_reads_fasta_file: packed bases overran their buffer (internal error)"; return DBG_E_HIP; }
+        hs = fs.hv->st;
+        si ^= 1;
+        b ^= 1;
+        pos = npos;
+        ++h->ingest.chunks;
+    }
+    const uint64_t n_reads = hs.n_reads, n_bases = hs.cursor;  // the pending white space of the last line is dropped
+    HIPCHK(h, hipMemcpyAsync(fs.offsets + n_reads, &n_bases, 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->d_bases = fs.bases;
+    h->own_bases = true;
+    h->d_offsets = fs.offsets;
+    h->own_offsets = true;
+    fs.bases = nullptr;
+    fs.offsets = nullptr;
+    h->n_bytes = n_bases;
+    h->n_reads = n_reads;
+    h->ingest.peak_device_bytes = fs.peak;
+    h->ingest.n_reads = n_reads;
+    h->ingest.n_bases = n_bases;
+    h->ingest.ms_io_wait = ms_io;
+    h->ingest.ms_h2d = ms_h2d;
+    h->ingest.ms_parse = ms_parse;
+    h->stats.ms_h2d = ms_h2d;
+    const int rc = make_startbits(h);
+    h->ingest.ms_total = std::chrono::duration<double, std::milli>(clk::now() - t_call).count();
+    return rc;
+}
+
+extern "C" int dbg_fasta_ingest_stats(dbg_t *h, dbg_ingest_stats_t *out) {
+    if (!h || !out) return DBG_E_ARG;
+    *out = h->ingest;
+    return DBG_OK;
 }
 
 extern "C" int dbg_set_reads_device(dbg_t *h, const void *d_bases, uint64_t n_bytes, const void *d_offsets,

@@ -52,6 +52,11 @@ def read_reads(fname):
         return [line.rstrip() for line in fh.readlines() if line[0] != ">"]
 
 
+# Files of at least this many bytes stream to the device in chunks (dbg_set_reads_fasta_file) instead of going over in one
+# image (dbg_set_reads_fasta, which holds ~2.5x the file on the device at its peak).  The reads are the same either way.
+STREAM_MIN_BYTES = int(os.environ.get("DBG_STREAM_MIN_BYTES", str(1 << 30)))
+
+
 class DeviceReads:
     """``read_reads`` on the GPU: a read-only sequence of the reads of a FASTA file.
 
@@ -61,11 +66,21 @@ class DeviceReads:
     materialised lazily (one device-to-host copy of the packed buffer on first access).
     The object owns one device handle: a later ``construct_graph`` on the same object replaces the
     graph of an earlier one (``output_contigs`` on the earlier result then raises instead of walking the new graph).
+
+    byte_range=(begin, end): only the lines whose first byte lies in [begin, end) (end None: to the end of the file);
+    a line that starts in the range is read to its end.  The reads of [0, b) followed by those of [b, size) are the
+    reads of the whole file for every b.  chunk_bytes: size of the staging chunks of the streamed ingest (0: library
+    default).  Either argument, or a file of ``STREAM_MIN_BYTES`` or more, takes the streamed ingest
+    (``dbg_set_reads_fasta_file``); smaller files go over in one image.
     """
 
-    def __init__(self, fname):
+    def __init__(self, fname, byte_range=None, chunk_bytes=None):
         self._graph = _dbg.Graph()
-        self._graph.set_reads_fasta(fname)
+        if byte_range is None and chunk_bytes is None and os.path.getsize(fname) < STREAM_MIN_BYTES:
+            self._graph.set_reads_fasta(fname)
+        else:
+            begin, end = (0, None) if byte_range is None else byte_range
+            self._graph.set_reads_fasta_file(fname, begin, end, chunk_bytes or 0)
         self._n = self._graph.sizes()["n_reads"]
         self._host = None
 
@@ -107,9 +122,9 @@ class DeviceReads:
         return [text[int(a):int(b)] for a, b in zip(off[:-1], off[1:])]
 
 
-def read_reads_device(fname):
-    """``read_reads`` (debruijn.py:22-32) without leaving the GPU; see DeviceReads."""
-    return DeviceReads(fname)
+def read_reads_device(fname, byte_range=None, chunk_bytes=None):
+    """``read_reads`` (debruijn.py:22-32) without leaving the GPU; see DeviceReads (byte ranges, streamed ingest)."""
+    return DeviceReads(fname, byte_range, chunk_bytes)
 
 
 class _Vertices(dict):

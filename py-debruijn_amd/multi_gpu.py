@@ -25,6 +25,8 @@ through the host) or nccl.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 
 
@@ -116,6 +118,21 @@ def stamp_bases(dist, n_bytes, device):
         bases.append(acc)
         acc += int(t.item())
     return bases
+
+
+def set_reads_fasta_shard(g, path, dist, chunk_bytes=0):
+    """Sets this rank's share of the FASTA file at ``path`` as the reads of handle ``g`` (the input of sharded_build).
+
+    Rank r of w takes the lines that start in bytes [r*S//w, (r+1)*S//w) of the S-byte file (a line that starts in
+    the slice is read to its end), streamed from the file through pinned chunks of ``chunk_bytes`` (0: library
+    default): no rank reads or holds more than its slice and one line.  Every line belongs to exactly one rank, so the
+    ranks' reads concatenated in rank order are the file's reads in file order, and the stamp bases of sharded_build
+    (the byte offset of every rank's reads in that concatenation, as in ``stamp_bases``) give every node the global
+    stamp a single handle ingesting the whole file would give it.  Returns ``g``."""
+    w, r = dist.get_world_size(), dist.get_rank()
+    size = os.path.getsize(path)
+    g.set_reads_fasta_file(path, r * size // w, (r + 1) * size // w, chunk_bytes)
+    return g
 
 
 def message_digests(t, counts):
