@@ -356,13 +356,15 @@ int dbg_device_views(dbg_t *h, const void **d_keys, const void **d_counts, const
  *      (owner shard << 29) | node id on that shard; stamps are global ((byte offset in the
  *      rank-major concatenation of all reads) << 1 | pos != 0). */
 /* step 1: this rank's reads -> super-k-mer records grouped by owner (device arrays: w0, w1 uint64,
- * st = rank-local stamps: uint32 while this rank's reads stay below 2 GiB, else uint64 (k <= 31 only; option
- * "shard_stamp64" 1 forces the wide ones) -- dbg_shard_record_layout says which); send_counts[n_shards] records go to
- * each owner, contiguous and in owner order */
+ * st = rank-local stamps: k <= 31: uint32 while this rank's reads stay below 2 GiB, else uint64 -- dbg_shard_record_layout
+ * says which; k > 31 on the LDS engine: always uint32 on the wire, and from 2 GiB of reads on bits 61..32 of the stamp ride
+ * in bits 63..34 of the record's meta word (zero below 2 GiB, so the messages are those of a narrow rank); the option
+ * "shard_stamp64" 1 forces the wide path at any size.  k > 31 on the global-table engine ("wide_engine" 0): reads below
+ * 2 GiB only); send_counts[n_shards] records go to each owner, contiguous and in owner order */
 int dbg_shard_extract(dbg_t *h, int k, int n_shards, uint64_t *send_counts, const void **d_w0, const void **d_w1,
                       const void **d_st);
 /* dbg_shard_extract for part `part` of n_parts (1..4) slices of this rank's reads (k <= 31: super-k-mer records; k > 31: the
- * records by value of the LDS engine, reads below 2 GiB): slices of the position space cut at
+ * records by value of the LDS engine, stamps as for dbg_shard_extract): slices of the position space cut at
  * tile borders -- a k-mer belongs to the slice its first base lies in, so the parts' records together are exactly those of
  * dbg_shard_extract; the stamps are positions in ALL of the rank's reads either way.  The arrays of part p stay valid until
  * part p is extracted again (own buffers per part): multi_gpu.sharded_build_multipass(chunks=...) has part p on the wire
@@ -372,7 +374,8 @@ int dbg_shard_extract_part(dbg_t *h, int k, int n_shards, int part, int n_parts,
 /* What the last dbg_shard_extract handed out: *w0_words = 64-bit words per record in d_w0 (1: super-k-mer records of
  * k <= 31, or the low key word of the k-mer instances of k > 31 with "wide_engine" 0; 4: the aligned bases of a
  * super-k-mer record of k > 31), *stamp_bytes = bytes per entry of d_st (4; 8 for the instance tuples and for
- * k <= 31 records of a rank that holds 2 GiB of reads or more).  The exchange moves counts[d] x words elements of d_w0;
+ * k <= 31 records of a rank that holds 2 GiB of reads or more; the records of k > 31 stay at 4 at any size, their wider
+ * stamps continue in the meta word).  The exchange moves counts[d] x words elements of d_w0;
  * all senders of one dbg_shard_build must use ONE stamp width (a rank with 4-byte stamps zero-extends them when another
  * rank has 8: multi_gpu.sharded_build). */
 int dbg_shard_record_layout(dbg_t *h, int *w0_words, int *stamp_bytes);
@@ -387,7 +390,8 @@ int dbg_shard_bucket_counts(dbg_t *h, uint64_t *counts512);
  * the buckets THIS shard owns.  With it the receiver skips the first multisplit level (the senders did it before the
  * exchange) and rebases the stamps inside the second one.
  * stamp_bytes: width of the entries of d_st32 -- 0 = the layout's default (4; 8 for k-mer instance tuples), 4, or 8
- * (k <= 31 with sender_bucket_counts: senders that hold 2 GiB of reads or more). */
+ * (k <= 31 with sender_bucket_counts: senders that hold 2 GiB of reads or more).  The records of k > 31 (LDS engine) come
+ * with 4-byte stamps from every sender: the second multisplit level joins the high bits their meta words carry. */
 int dbg_shard_build(dbg_t *h, int k, int n_shards, int my_shard, const void *d_w0, const void *d_w1, const void *d_st32,
                     const uint64_t *recv_counts, const uint64_t *stamp_base, uint64_t *q_starts, uint64_t *q_counts,
                     const void **d_q_keys, const uint64_t *sender_bucket_counts, int stamp_bytes);

@@ -3522,7 +3522,7 @@ struct CeilDiv {
 
 // One multisplit level: segments (p_start/p_cnt, device) -> children (c_start/c_cnt, device,
 // n_groups * nb entries), records moved from in_* to out_*.
-template <class ST, bool HAS_ST, class STI = ST>
+template <class ST, bool HAS_ST, class STI = ST, int STHI = 0>
 static int multisplit_level(dbg *h, const uint64_t *p_start, const uint64_t *p_cnt, uint32_t n_seg, uint32_t spg,
                             uint64_t total, const uint64_t *in_w0, const uint64_t *in_w1, const STI *in_st,
                             uint64_t *out_w0, uint64_t *out_w1, ST *out_st, int shift, int nb, uint64_t *c_start,
@@ -3566,7 +3566,7 @@ static int multisplit_level(dbg *h, const uint64_t *p_start, const uint64_t *p_c
     hipLaunchKernelGGL(k_ms_children, dim3(grid_for(n_child, 256)), dim3(256), 0, h->stream, P, offs, nb, total, c_start,
                        c_cnt);
     if (nsc) {
-        auto kern = k_ms_scatter<ST, HAS_ST, STI>;
+        auto kern = k_ms_scatter<ST, HAS_ST, STI, STHI>;
         const size_t lds = sizeof(MsLds<ST>);
         HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3((unsigned)nsc), dim3(MS_NT), lds, h->stream, P, in_w0, in_w1, in_st, seg_add, shift, nb,
@@ -4280,10 +4280,13 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
             HIPCHK(h, hipMemsetAsync(b_start, 0, n_buckets * 16, h->stream));
             if (nb3 > 1) HIPCHK(h, hipMemsetAsync(l2_start, 0, n_l2 * 16, h->stream));
             HIPCHK(h, hipMemsetAsync(h->d_scalars + 56, 0, 16, h->stream));
-            CHK((multisplit_level<ST, true, STI>(h, ps_start, ps_cnt, ps_n, (uint32_t)pre->n_senders, n_rec, in_w0, in_w1,
-                                                 (const STI *)pre->in_st, w0[0], w1[0], st[0], sh2, nb2, l2_start + b_lo * nb2,
-                                                 l2_cnt + b_lo * nb2, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], fb2, ps_add,
-                                                 (unsigned long long *)nullptr)));
+            // records received by value with 4-byte stamps (a sharded build): the stamps' bits 61..32 come in the meta
+            // words (WREC_ST_HI) and join the stamps here, where the sender's stamp base is added
+            constexpr int sthi = (sizeof(STI) == 4 && sizeof(ST) == 8) ? WREC_ST_HI : 0;
+            CHK((multisplit_level<ST, true, STI, sthi>(h, ps_start, ps_cnt, ps_n, (uint32_t)pre->n_senders, n_rec, in_w0, in_w1,
+                                                       (const STI *)pre->in_st, w0[0], w1[0], st[0], sh2, nb2, l2_start + b_lo * nb2,
+                                                       l2_cnt + b_lo * nb2, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], fb2, ps_add,
+                                                       (unsigned long long *)nullptr)));
         } else {
             CHK((multisplit_level<ST, true>(h, c1_start, c1_cnt, (uint32_t)nb1, 1, n_rec, w0[1], w1[1], st[1], w0[0], w1[0], st[0], sh2,
                                             nb2, l2_start, l2_cnt, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], fb2)));
@@ -4722,6 +4725,7 @@ static int shard_build_wide(dbg *h, int k, int n_shards, int my_shard, const uin
 //      (k_wsk_gather: four aligned words), meta word and rank-local stamp, 44 bytes for ~26 k-mer instances at k = 63
 //      (the instance tuples of shard_extract_wide are 24 bytes each).  The receiver takes the received bases as its
 //      packed reads: record i sits at base position 128 i.
+template <class ST>  // ST: width of the rank-local stamps until the gather; the wire carries 4 of their bytes either way
 static int shard_extract_wsk(dbg *h, int k, int n_shards, uint64_t *send_counts, const void **d_rb, const void **d_w1,
                              const void **d_st, int part = 0, int n_parts = 1) {
     free_build(h);
@@ -4729,29 +4733,38 @@ static int shard_extract_wsk(dbg *h, int k, int n_shards, uint64_t *send_counts,
     CHK(compute_alphabet(h));
     if (!h->is_dna) { h->err = "sharded builds take ACGT reads"; return DBG_E_ALPHABET; }
     uint64_t *pk = nullptr, *w0[2], *w1[2], *seg_start = nullptr, *seg_cnt = nullptr, n_rec = 0;
-    uint32_t *st[2];
+    ST *st[2];
     uint32_t n_seg = 0;
-    CHK(wsk_extract<uint32_t>(h, k, &pk, w0, w1, st, &seg_start, &seg_cnt, &n_seg, &n_rec, part, n_parts));
+    CHK(wsk_extract<ST>(h, k, &pk, w0, w1, st, &seg_start, &seg_cnt, &n_seg, &n_rec, part, n_parts));
+    // the 4-byte stamps that travel: the level-1 output itself (32-bit stamps), or the low halves k_wsk_gather_split
+    // writes next to it -- into the unsplit stamps' array, which level 1 has read by then
+    uint32_t *st_out = sizeof(ST) == 4 ? (uint32_t *)st[1] : (uint32_t *)st[0];
     if (n_parts > 1) {  // what travels (meta words, stamps; the gathered bases below) keeps buffers of its own per part
         CHK(buf_ensure(h, h->ar_part[part][1], (n_rec + 16) * 8));
         CHK(buf_ensure(h, h->ar_part[part][2], (n_rec + 16) * 4));
         w1[1] = (uint64_t *)h->ar_part[part][1].p;
-        st[1] = (uint32_t *)h->ar_part[part][2].p;
+        st_out = (uint32_t *)h->ar_part[part][2].p;
+        if (sizeof(ST) == 4) st[1] = (ST *)st_out;  // (64-bit stamps stay in the record arena until the gather splits them)
     }
     const int nb1 = 512;
     CHK(buf_ensure(h, h->ar_misc[1], (uint64_t)nb1 * 16));
     uint64_t *c1_start = (uint64_t *)h->ar_misc[1].p, *c1_cnt = c1_start + nb1;
     Timer t(h->stream);
-    CHK((multisplit_level<uint32_t, true>(h, seg_start, seg_cnt, n_seg, n_seg, n_rec, w0[0], w1[0], st[0], w0[1], w1[1], st[1],
-                                          6 + SK_BUCKET_BITS - 9, nb1, c1_start, c1_cnt, h->ar_misc[2], h->ar_misc[3],
-                                          h->ar_misc[4], 0, nullptr, nullptr, h->host_seg_cnt.data())));
+    CHK((multisplit_level<ST, true>(h, seg_start, seg_cnt, n_seg, n_seg, n_rec, w0[0], w1[0], st[0], w0[1], w1[1], st[1],
+                                    6 + SK_BUCKET_BITS - 9, nb1, c1_start, c1_cnt, h->ar_misc[2], h->ar_misc[3],
+                                    h->ar_misc[4], 0, nullptr, nullptr, h->host_seg_cnt.data())));
     std::vector<uint64_t> cnt(nb1);
     HIPCHK(h, hipMemcpyAsync(cnt.data(), c1_cnt, nb1 * 8, hipMemcpyDeviceToHost, h->stream));
     dbg::Buf &b_rb = n_parts > 1 ? h->ar_part[part][0] : h->ar_wide[2];
     CHK(buf_ensure(h, b_rb, (n_rec + 1) * 32));
     uint4 *rec_b = (uint4 *)b_rb.p;
-    if (n_rec)
-        hipLaunchKernelGGL(k_wsk_gather, dim3(grid_for(n_rec, 256)), dim3(256), 0, h->stream, w0[1], w1[1], n_rec, pk, k, rec_b);
+    if constexpr (sizeof(ST) == 4) {
+        if (n_rec)
+            hipLaunchKernelGGL(k_wsk_gather, dim3(grid_for(n_rec, 256)), dim3(256), 0, h->stream, w0[1], w1[1], n_rec, pk, k, rec_b);
+    } else if (n_rec) {
+        hipLaunchKernelGGL(k_wsk_gather_split, dim3(grid_for(n_rec, 256)), dim3(256), 0, h->stream, w0[1], w1[1], st[1], st_out,
+                           n_rec, pk, k, rec_b);
+    }
     HIPCHK(h, hipGetLastError());
     h->stats.ms_partition = t.stop();
     for (int d = 0; d < n_shards; ++d) {
@@ -4760,7 +4773,7 @@ static int shard_extract_wsk(dbg *h, int k, int n_shards, uint64_t *send_counts,
     }
     *d_rb = rec_b;
     *d_w1 = w1[1];
-    *d_st = st[1];
+    *d_st = st_out;
     ShardState &sh = shard_of(h);
     sh.n_shards = n_shards;
     sh.k = k;
@@ -4889,10 +4902,10 @@ extern "C" int dbg_shard_extract_part(dbg_t *h, int k, int n_shards, int part, i
     if (n_parts < 1 || n_parts > 4 || part < 0 || part >= n_parts) { h->err = "dbg_shard_extract_part: 1 <= n_parts <= 4, 0 <= part < n_parts"; return DBG_E_ARG; }
     const bool st64 = h->n_bytes >= (1ull << 31) || h->shard_stamp64;
     HIPCHK(h, hipSetDevice(h->device));
-    if (k > 31) {  // two-word k-mers: records by value (the LDS engine), 32-bit rank-local stamps
+    if (k > 31) {  // two-word k-mers: records by value (the LDS engine), 4-byte stamps on the wire (wider: dbg_wsk.h WREC_ST_HI)
         if (h->wide_engine != 1) { h->err = "dbg_shard_extract_part: two-word k-mers on the LDS engine (\"wide_engine\" 1)"; return DBG_E_ARG; }
-        if (h->n_bytes >= (1ull << 31)) { h->err = "a shard's reads must stay below 2 GiB for k > 31 (32-bit local stamps)"; return DBG_E_ARG; }
-        return shard_extract_wsk(h, k, n_shards, send_counts, d_w0, d_w1, d_st, part, n_parts);
+        return st64 ? shard_extract_wsk<uint64_t>(h, k, n_shards, send_counts, d_w0, d_w1, d_st, part, n_parts)
+                    : shard_extract_wsk<uint32_t>(h, k, n_shards, send_counts, d_w0, d_w1, d_st, part, n_parts);
     }
     return st64 ? shard_extract_sk<uint64_t>(h, k, n_shards, send_counts, d_w0, d_w1, d_st, part, n_parts)
                 : shard_extract_sk<uint32_t>(h, k, n_shards, send_counts, d_w0, d_w1, d_st, part, n_parts);
@@ -4906,8 +4919,13 @@ extern "C" int dbg_shard_extract(dbg_t *h, int k, int n_shards, uint64_t *send_c
     const bool st64 = h->n_bytes >= (1ull << 31) || h->shard_stamp64;
     HIPCHK(h, hipSetDevice(h->device));
     if (k > 31) {
-        if (h->n_bytes >= (1ull << 31)) { h->err = "a shard's reads must stay below 2 GiB for k > 31 (32-bit local stamps)"; return DBG_E_ARG; }
-        if (h->wide_engine == 1) return shard_extract_wsk(h, k, n_shards, send_counts, d_w0, d_w1, d_st);
+        if (h->wide_engine == 1)  // the stamps' bits 61..32 travel in the meta word (dbg_wsk.h WREC_ST_HI)
+            return st64 ? shard_extract_wsk<uint64_t>(h, k, n_shards, send_counts, d_w0, d_w1, d_st)
+                        : shard_extract_wsk<uint32_t>(h, k, n_shards, send_counts, d_w0, d_w1, d_st);
+        if (h->n_bytes >= (1ull << 31)) {
+            h->err = "a shard's reads must stay below 2 GiB for k > 31 on the global-table engine (\"wide_engine\" 0: 32-bit local stamps)";
+            return DBG_E_ARG;
+        }
         int rcw = shard_extract_wide(h, k, n_shards, send_counts, d_w0, d_w1, d_st);
         if (rcw == DBG_OK) { shard_of(h).rec_words = 1; shard_of(h).rec_stamp_bytes = 8; }
         return rcw;

@@ -509,8 +509,10 @@ __device__ unsigned long long g_ms_prof[8];
 #endif
 
 // STI: stamp type of the input (a sharded build receives rank-local 32-bit stamps and rebases them to global 64-bit
-// ones here: seg_add[segment] = 2 x the byte offset of the sender's reads in the rank-major concatenation)
-template <class ST, bool HAS_ST, class STI = ST>
+// ones here: seg_add[segment] = 2 x the byte offset of the sender's reads in the rank-major concatenation).
+// STHI > 0: the input meta word carries bits 32.. of the rank-local stamp from bit STHI up (two-word records of a rank
+// holding 2 GiB of reads or more, dbg_wsk.h WREC_ST_HI); they join the 32-bit stamp and leave the meta word here.
+template <class ST, bool HAS_ST, class STI = ST, int STHI = 0>
 __global__ __launch_bounds__(MS_NT) void k_ms_scatter(MsParents P, const uint64_t *__restrict__ in_w0,
                                                     const uint64_t *__restrict__ in_w1, const STI *__restrict__ in_st,
                                                     const uint64_t *__restrict__ seg_add,
@@ -550,7 +552,13 @@ __global__ __launch_bounds__(MS_NT) void k_ms_scatter(MsParents P, const uint64_
             if (q < n) {
                 r0[i] = in_w0[c0 + q];
                 r1[i] = in_w1[c0 + q];
-                if (HAS_ST) rs[i] = (ST)in_st[c0 + q] + st_add;
+                if constexpr (STHI > 0) {
+                    static_assert(sizeof(ST) == 8 && sizeof(STI) == 4, "stamp high bits: 32-bit stamps in, 64-bit out");
+                    rs[i] = (((ST)(r1[i] >> STHI) << 32) | (ST)in_st[c0 + q]) + st_add;
+                    r1[i] &= (1ull << STHI) - 1;
+                } else if (HAS_ST) {
+                    rs[i] = (ST)in_st[c0 + q] + st_add;
+                }
                 rk[i] = atomicAdd(&s.hist[ms_child(r1[i], shift, nb, fbits)], 1u);
             }
         }

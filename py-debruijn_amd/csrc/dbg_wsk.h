@@ -34,7 +34,10 @@ constexpr int WSK_HALO = 128;
 using TileLdsW = TileLdsT<WSK_HALO>;
 
 // record meta word: bits 27..6 bucket hash (where the one-word records keep it: ms_child is shared), bits 33..28
-// length - 1 (a super-k-mer holds at most k - 12 <= 51 k-mers), bit 0: the last k-mer has a successor
+// length - 1 (a super-k-mer holds at most k - 12 <= 51 k-mers), bit 0: the last k-mer has a successor.
+// On the wire of a sharded build (records by value, 4-byte stamps) bits 63..34 carry bits 61..32 of the rank-local stamp:
+// zero below 2 GiB of reads; the receiver's level-2 multisplit moves them back into the stamp (k_ms_scatter STHI)
+constexpr int WREC_ST_HI = 34;
 __host__ __device__ inline int wrec_len(uint64_t w1) { return (int)((w1 >> SK_META_BITS) & 63) + 1; }
 __host__ __device__ inline uint32_t wrec_has_succ(uint64_t w1) { return (uint32_t)(w1 & 1); }
 
@@ -426,11 +429,7 @@ __global__ __launch_bounds__(256, 2) void k_wsk_extract_w(const char *__restrict
 // (= bucket) order: one pass of independent 40-byte reads of the packed reads at full occupancy.  Read inside the count
 // kernel, where a bucket's ~140 records are all a workgroup has in flight, the same reads were a dependent round trip
 // through HBM at the start of every bucket: 8 ms of 40 at k = 63.
-__global__ __launch_bounds__(256) void k_wsk_gather(const uint64_t *__restrict__ rec_w0, const uint64_t *__restrict__ rec_w1,
-                                                    uint64_t n_rec, const uint64_t *__restrict__ pk, int k, uint4 *out /* [n_rec][2] */) {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_rec) return;
-    const uint64_t p = rec_w0[r], w1 = rec_w1[r];
+__device__ inline void wsk_gather_one(uint64_t r, uint64_t p, uint64_t w1, const uint64_t *__restrict__ pk, int k, uint4 *out) {
     const int nb = k + wrec_len(w1) - 1 + (int)wrec_has_succ(w1);  // bases the record covers (<= 115)
     const uint64_t wi = p >> 5;
     const int sh = (int)(p & 31) * 2;
@@ -446,6 +445,27 @@ __global__ __launch_bounds__(256) void k_wsk_gather(const uint64_t *__restrict__
     }
     out[2 * r] = make_uint4((uint32_t)v[0], (uint32_t)(v[0] >> 32), (uint32_t)v[1], (uint32_t)(v[1] >> 32));
     out[2 * r + 1] = make_uint4((uint32_t)v[2], (uint32_t)(v[2] >> 32), (uint32_t)v[3], (uint32_t)(v[3] >> 32));
+}
+
+__global__ __launch_bounds__(256) void k_wsk_gather(const uint64_t *__restrict__ rec_w0, const uint64_t *__restrict__ rec_w1,
+                                                    uint64_t n_rec, const uint64_t *__restrict__ pk, int k, uint4 *out /* [n_rec][2] */) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rec) return;
+    wsk_gather_one(r, rec_w0[r], rec_w1[r], pk, k, out);
+}
+
+// k_wsk_gather for the sender of a sharded build with 64-bit rank-local stamps (reads of 2 GiB and more): the wire keeps
+// 4-byte stamps -- st32[r] = the low half, bits 61..32 go to bits 63..34 of the meta word (WREC_ST_HI), in place
+__global__ __launch_bounds__(256) void k_wsk_gather_split(const uint64_t *__restrict__ rec_w0, uint64_t *rec_w1,
+                                                          const uint64_t *__restrict__ st64, uint32_t *__restrict__ st32,
+                                                          uint64_t n_rec, const uint64_t *__restrict__ pk, int k,
+                                                          uint4 *out /* [n_rec][2] */) {
+    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rec) return;
+    const uint64_t w1 = rec_w1[r], st = st64[r];
+    wsk_gather_one(r, rec_w0[r], w1, pk, k, out);
+    st32[r] = (uint32_t)st;
+    rec_w1[r] = w1 | ((st >> 32) << WREC_ST_HI);
 }
 
 // ------------------------------------------------------------------------------------------------

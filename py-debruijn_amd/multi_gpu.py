@@ -254,8 +254,9 @@ def sharded_build(g, k, dist, check=True):
     metas = _all_gather_ints(dist, meta, device)
     if any(m_r[1] != words for m_r in metas):
         raise RuntimeError("sharded build: the ranks disagree about the record layout (different engines or input sizes)")
-    # rank-local stamps are 32-bit while a rank's reads stay below 2 GiB: a receiver takes ONE width, the widest any
-    # sender uses (a rank with narrow stamps zero-extends them: they are unsigned positions)
+    # rank-local stamps are 32-bit while a rank's reads stay below 2 GiB (k <= 31; two-word records keep 4-byte stamps at
+    # any size, their bits 61..32 travel in the meta word): a receiver takes ONE width, the widest any sender uses (a
+    # rank with narrow stamps zero-extends them: they are unsigned positions)
     if max(m_r[2] for m_r in metas) > st_bytes:
         st = widen_stamps(st)
     bases, acc = [], 0
