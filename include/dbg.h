@@ -417,6 +417,21 @@ int dbg_import_graph(dbg_t *h, int k, int n_shards, const uint64_t *shard_nodes,
 /* device pointer of the upper key words (NULL for k <= 31) */
 int dbg_device_keys_hi(dbg_t *h, const void **d_keys_hi);
 
+/* ---- the driver's next k (II_assembleFromReads.py:56-75: build at k, walk, sort the contigs, append the pull-out reads,
+ *      build at k+1 from those): the k1 = k + 1 graph of (the contigs of src's last walk, in `order`) followed by the
+ *      n_extra reads extra_bases / extra_offsets[n_extra + 1], built into the fresh handle dst from the chain structure of
+ *      src's graph -- no contig is ever spelled.  order[n_order]: contig indices (dbg_export_contig_index) in driver order,
+ *      a permutation of 0..n_contigs-1.  src is read-only and stays valid; dst must live on the same device.
+ *      Afterwards dst is what dbg_build(k1) would have produced on the spelled-out reads: same nodes, keys, counts, stamps
+ *      (offsets in that concatenation, T = the contigs' characters, then the extra reads) and flags, node order aside; the
+ *      successor ranks are already exact (dbg_refine_edge_order leaves them); dbg_prune, dbg_remove_tips,
+ *      dbg_mark_pull_reads, dbg_walk and every export apply.  dbg_export_pull_reads reports n_order + n_extra reads
+ *      (contigs first), dbg_get_sizes n_reads = n_order + n_extra and n_bytes = T + the extra bytes.
+ *      DBG_E_ARG (text in dbg_last_error) for: no walk of src's current graph, a final-mode walk, a generic alphabet, a graph
+ *      in parts, k1 > 63 or k1 != k + 1, an order that is not a permutation of the contig index. */
+int dbg_build_from_walk(dbg_t *dst, dbg_t *src, int k1, const uint64_t *order, uint64_t n_order, const char *extra_bases,
+                        const uint64_t *extra_offsets, uint64_t n_extra);
+
 /* ---- f4: read-support scores of contigs (findSupportReadScore, IV_sortOutputs.py:10-15): out_scores[c] = sum of
  *      read_scores[r] over the reads r (distinct strings: the reference's dict keys) that occur in contig c as a
  *      substring, added in ascending r from 0.0 -- the reference's order, so double sums equal the reference's bit for

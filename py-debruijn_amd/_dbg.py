@@ -36,6 +36,7 @@ SYMBOLS = (
     "dbg_export_marked", "dbg_part_keys_hi", "dbg_take_reads",
     "dbg_part_prune", "dbg_part_select", "dbg_part_gather", "dbg_part_mark", "dbg_part_clear", "dbg_part_cross_targets",
     "dbg_part_segments", "dbg_part_pflags", "dbg_scan_reads_for_keys", "dbg_set_orders", "dbg_part_segment_text",
+    "dbg_build_from_walk",
 )
 
 
@@ -170,6 +171,7 @@ def load_library():
         "dbg_part_segment_text": (C.c_int, [H, C.c_int, vp, C.c_uint64, vp, vp, C.c_uint64]),
         "dbg_scan_reads_for_keys": (C.c_int, [H, C.c_int, vp, vp, C.c_uint64, vp, vp]),
         "dbg_set_orders": (C.c_int, [H, vp]),
+        "dbg_build_from_walk": (C.c_int, [H, H, C.c_int, vp, C.c_uint64, vp, vp, C.c_uint64]),
         "dbg_shard_apply": (C.c_int, [H, vp]),
         "dbg_import_graph": (C.c_int, [H, C.c_int, C.c_int, u64p, vp, vp, vp, vp, vp]),
         "dbg_device_keys_hi": (C.c_int, [H, C.POINTER(vp)]),
@@ -307,6 +309,17 @@ class Graph:
     def build(self, k, table_capacity_hint=0):
         self.generation += 1
         self._chk(self._lib.dbg_build(self._h, int(k), int(table_capacity_hint)))
+
+    def build_from_walk(self, src, k1, order, bases, offsets):
+        """The k1 = k + 1 graph of (the contigs of ``src``'s last non-final walk, in ``order``) + the extra reads
+        ``bases`` / ``offsets`` (as for set_reads), built on the device from src's chains (dbg_build_from_walk)."""
+        o = np.ascontiguousarray(order, dtype=np.uint64)
+        b = np.ascontiguousarray(np.frombuffer(bases, dtype=np.uint8) if not isinstance(bases, np.ndarray) else bases, dtype=np.uint8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert off.ndim == 1 and off.size >= 1 and int(off[-1]) == b.size
+        self.generation += 1
+        self._chk(self._lib.dbg_build_from_walk(self._h, src._h, int(k1), _ptr(o) if o.size else None, o.size,
+                                                _ptr(b) if b.size else None, _ptr(off), off.size - 1))
 
     def refine_edge_order(self):
         self._chk(self._lib.dbg_refine_edge_order(self._h))

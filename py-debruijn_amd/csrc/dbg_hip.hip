@@ -114,6 +114,7 @@ struct dbg {
     uint32_t *d_lift = nullptr;       // binary-lifting tables of the last walk, built on the first text request
     int lift_levels = 0;
     bool walked = false;          // contig text materialised
+    bool walk_final = false;      // the last walk was a final-mode one (all simple paths, not chains)
     bool walk_indexed = false;    // contig index (offsets, scores, start stamps) valid
     uint64_t walk_jump_min = 1ull << 14;  // non-final walk: list ranking from this many nodes on (below: one thread per start)
 
@@ -167,6 +168,12 @@ struct dbg {
     // branch k-mer lookup (pull-out reads)
     uint64_t *d_btab = nullptr;
     uint64_t btab_cap = 0;
+    // graph of dbg_build_from_walk (dbg_nextk.h): nk_reads contigs of nk_bytes characters are virtual reads in front of
+    // the real ones; their pull-out test needs the chain successors of the k-graph, y(x) and the start of every contig
+    bool nk_graph = false;
+    uint64_t nk_reads = 0, nk_bytes = 0, nk_src_nodes = 0;
+    uint32_t *d_nk_next = nullptr, *d_nk_y = nullptr, *d_nk_start = nullptr;
+    uint8_t *d_nk_read_flags = nullptr;
 
     dbg_stats_t stats{};
     dbg_ingest_stats_t ingest{};  // the last FASTA ingest
@@ -1530,6 +1537,7 @@ __global__ __launch_bounds__(256) void k_text_fill(uint64_t n_chars, G g, const 
 // a shard's successor ids (owner << 29 | id) index other handles' node tables: traversal kernels must not follow them
 static const char *const kPartialGraph =
     "this handle holds one shard of a multi-GPU build: gather the shards first (multi_gpu.gather_graph / dbg_import_graph)";
+static int nk_mark_contigs(dbg *h);
 static void free_build(dbg *h) {
     multipass_free(h);
     dev_free(h->d_tab); dev_free(h->d_occ);
@@ -1564,6 +1572,9 @@ static void free_build(dbg *h) {
     h->n_starts = h->n_contigs = h->contig_chars = 0;
     h->starts_known = false;
     h->n_kmer_inst = h->n_edge_inst = 0;
+    dev_free(h->d_nk_next); dev_free(h->d_nk_y); dev_free(h->d_nk_start); dev_free(h->d_nk_read_flags);
+    h->nk_graph = false;
+    h->nk_reads = h->nk_bytes = h->nk_src_nodes = 0;
 }
 
 static void free_reads(dbg *h) {
@@ -2690,6 +2701,7 @@ extern "C" int dbg_refine_edge_order(dbg_t *h) {
     HIPCHK(h, hipSetDevice(h->device));
     CHK(ensure_dense(h));
     if (h->D == GEN_D) return DBG_OK;  // the generic engine ranks by per-edge first-seen positions at build time
+    if (h->nk_graph) return DBG_OK;    // dbg_build_from_walk wrote the exact ranks (the contigs are not in the reads)
     dev_free(h->d_fsorder);
     CHK(dev_alloc(h, &h->d_fsorder, h->n_nodes));
     if (!h->n_nodes) { h->order_exact = true; return DBG_OK; }
@@ -2817,7 +2829,7 @@ extern "C" int dbg_export_dict_order(dbg_t *h, uint32_t *order) {
         if ((rc = dev_alloc(h, &ids_out, n)) != DBG_OK) break;
         hipLaunchKernelGGL(k_iota32, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, n, ids);
         int end_bit = 2;  // stamp = position << 1 | flag, position < n_bytes
-        while (end_bit < 64 && (h->n_bytes >> (end_bit - 1))) ++end_bit;
+        while (end_bit < 64 && ((h->n_bytes + h->nk_bytes) >> (end_bit - 1))) ++end_bit;
         size_t tmp_bytes = 0;
         hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, h->d_stamps, keys_out, ids, ids_out, (size_t)n, 0u,
                                                  (unsigned)end_bit, h->stream);
@@ -3099,6 +3111,7 @@ extern "C" int dbg_mark_pull_reads(dbg_t *h) {
         CHK(reduce_sum(h, h->n_reads, ByteAt{h->d_read_flags}, &total));
         h->n_pull_reads = total;
     }
+    if (h->nk_graph) CHK(nk_mark_contigs(h));  // the virtual contig reads of a graph built from a walk
     h->stats.ms_pull_reads = t.stop();
     h->pull_reads_done = true;
     return DBG_OK;
@@ -3110,6 +3123,7 @@ static int walk_impl(dbg *h, const G &g, int final_mode, uint64_t max_chars) {
     // without a branch node every node has at most one surviving successor: "all simple paths" of the final mode ARE the
     // chain walks, and those have the parallel path (the per-start DFS took 2 s on BASELINE configs[0] without errors)
     if (final_mode && h->n_branch == 0) final_mode = 0;
+    h->walk_final = final_mode != 0;
     Timer t(h->stream);
     dev_free(h->d_ctg_off); dev_free(h->d_ctg_chars); dev_free(h->d_ctg_score); dev_free(h->d_ctg_stamp);
     dev_free(h->d_ctg_seq); dev_free(h->d_ctg_start); dev_free(h->d_lift);
@@ -3287,8 +3301,8 @@ extern "C" int dbg_get_sizes(dbg_t *h, dbg_sizes_t *o) {
     memset(o, 0, sizeof(*o));
     o->k = h->k;
     o->abi_version = DBG_ABI_VERSION;
-    o->n_reads = h->n_reads;
-    o->n_bytes = h->n_bytes;
+    o->n_reads = h->n_reads + h->nk_reads;
+    o->n_bytes = h->n_bytes + h->nk_bytes;
     o->n_kmer_instances = h->n_kmer_inst;
     o->n_edge_instances = h->n_edge_inst;
     o->table_capacity = h->cap;
@@ -3370,6 +3384,10 @@ extern "C" int dbg_export_pull_ranks(dbg_t *h, uint64_t *ranks) {
 extern "C" int dbg_export_pull_reads(dbg_t *h, uint8_t *read_flags) {
     if (!h || !h->pull_reads_done) { if (h) h->err = "dbg_mark_pull_reads must run first"; return DBG_E_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
+    if (h->nk_graph) {  // the contigs first, then the real reads
+        D2H(h, read_flags, h->d_nk_read_flags, h->nk_reads);
+        if (read_flags) read_flags += h->nk_reads;
+    }
     D2H(h, read_flags, h->d_read_flags, h->n_reads);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DBG_OK;
@@ -6579,3 +6597,5 @@ extern "C" int dbg_export_sorted_fasta(dbg_t *h, uint32_t *order_out, char *buf,
     dev_free(ka); dev_free(kb); dev_free(ia); dev_free(ib); dev_free(pos); dev_free(d_out);
     return rc;
 }
+
+#include "dbg_nextk.h"  // dbg_build_from_walk: the next k's graph from the last walk

@@ -388,6 +388,10 @@ class LazyContigs(Sequence):
     arbitrary ``key`` would mean fetching every text (10^12 characters at the BASELINE size).  A ``key`` that is not
     that score is detected on a sample of the shortest contigs and refused."""
 
+    _final = None       # set by output_contigs: the walk's mode and the handle state it read (construct_graph at k + 1
+    _generation = None  # builds from the chains of a current non-final walk, dbg_build_from_walk)
+    _walk = None
+
     def __init__(self, graph, order, off, score):
         self._graph = graph
         self._order = np.asarray(order)
@@ -434,6 +438,39 @@ class LazyContigs(Sequence):
         self._tail.extend(more)
 
 
+class _PulledReads(Sequence):
+    """pull_out_read of a graph built from a walk: the pulled contigs fetch their text from the k-graph when indexed
+    (like LazyContigs.__getitem__), the pulled original reads are strings."""
+
+    def __init__(self, reads, idx):
+        self._reads = reads
+        self._idx = [int(i) for i in idx]
+
+    def __len__(self):
+        return len(self._idx)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        return self._reads[self._idx[i]]
+
+    def __eq__(self, other):
+        return isinstance(other, (list, Sequence)) and list(self) == list(other)
+
+
+def _walk_source(reads, k):
+    """The k-graph whose chains build the (k = its k + 1)-graph of ``reads`` (dbg_build_from_walk), or None: a
+    LazyContigs of a current non-final walk over ACGT whose appended tail holds plain strings."""
+    if type(reads) is not LazyContigs or reads._final is not False:
+        return None
+    g = reads._graph
+    if g.generation != reads._generation or g.walks != reads._walk or g.alphabet()[1] != 2 or g.sizes()["k"] + 1 != k:
+        return None
+    if not all(type(r) is str for r in reads._tail):
+        return None
+    return g
+
+
 def _pack_reads(reads):
     try:
         blob = "".join(reads).encode("latin-1")  # one byte per character
@@ -454,13 +491,23 @@ def construct_graph(reads, k, threshold=3, final=False):
     if not isinstance(k, (int, np.integer)) or not (1 <= int(k) <= 63):
         raise ValueError("the device path supports 1 <= k <= 63")
     k = int(k)
-    if isinstance(reads, DeviceReads):
-        g = reads._graph  # reads are resident (alphabet is checked by the kernels: AlphabetError is a ValueError)
-    else:
-        bases, offsets = _pack_reads(reads)
+    src = _walk_source(reads, k)
+    if src is not None:
+        bases, offsets = _pack_reads(reads._tail)
+        if not np.isin(bases, np.frombuffer(b"ACGT", dtype=np.uint8)).all():
+            src = None
+    if src is not None:
+        # the contigs of the k-graph's walk + the appended reads, built from the chains: no contig text is spelled
         g = _dbg.Graph()
-        g.set_reads(bases, offsets)
-    g.build(k)
+        g.build_from_walk(src, k, reads._order, bases, offsets)
+    else:
+        if isinstance(reads, DeviceReads):
+            g = reads._graph  # reads are resident (alphabet is checked by the kernels: AlphabetError is a ValueError)
+        else:
+            bases, offsets = _pack_reads(reads)
+            g = _dbg.Graph()
+            g.set_reads(bases, offsets)
+        g.build(k)
     g.refine_edge_order()  # Counter order of the successors (first-seen ties), debruijn.py:159-165, :215-216
     sz = g.sizes()
     print('number of {}mer: '.format(k), sz["n_nodes"])  # debruijn.py:224
@@ -568,7 +615,10 @@ def construct_graph(reads, k, threshold=3, final=False):
     else:
         rf = g.export_pull_reads()
         pulled_idx = np.nonzero(rf)[0]
-        pull_out_read = reads.take(pulled_idx) if isinstance(reads, DeviceReads) else [reads[i] for i in pulled_idx]
+        if src is not None:
+            pull_out_read = _PulledReads(reads, pulled_idx)
+        else:
+            pull_out_read = reads.take(pulled_idx) if isinstance(reads, DeviceReads) else [reads[i] for i in pulled_idx]
         branch_kmer = _Tracked(marked_labels(_dbg.F_BRANCH))
 
     token = object()
@@ -605,7 +655,10 @@ def output_contigs(g, branch_kmer, already_pull_out):
     graph.walk(final_mode, MAX_CONTIG_CHARS)
     if not graph.sizes()["contigs_materialised"]:  # index only: the texts stay on the device until asked for
         off, score, stamp, seq = graph.export_contig_index()
-        return LazyContigs(graph, np.lexsort((seq, stamp)), off, score)
+        lazy = LazyContigs(graph, np.lexsort((seq, stamp)), off, score)
+        lazy._final = bool(final_mode) and sz["n_branch"] > 0  # without a branch node the final walk is the chain walk
+        lazy._generation, lazy._walk = graph.generation, graph.walks
+        return lazy
     off, chars, score, stamp, seq = graph.export_contigs()
     order = np.lexsort((seq, stamp))  # starts in dict order, emission order inside a start
     text = chars.tobytes().decode("latin-1")
