@@ -483,8 +483,41 @@ def main_support():
           sum(1 for c in cases for w in c["want"] if w not in (0, "0x0.0p+0")), "non-zero scores")
 
 
+# the awkward FASTA files of tests/test_hip_driver.py::FASTA_CASES (same names, same texts)
+FASTA_CASES = {
+    "plain": ">r0\nACGTACGTTG\n>r1\nTTGACCA\n",
+    "no_final_newline": ">r0\nACGTACGTTG\n>r1\nTTGACCA",
+    "crlf": ">r0\r\nACGTACGTTG\r\n>r1\r\nTTGACCA\r\n",
+    "lone_cr": ">r0\rACGTACGTTG\r>r1\rTTGACCA\r",
+    "blank_and_multiline": ">r0\nACGT\nACGTTG\n\n>r1\n\nTTGACCA\n\n",
+    "trailing_space": ">r0 some text\nACGTACGTTG  \t\n>r1\nTTGACCA \n",
+    "gt_inside": "ACG>TT\n>hdr\n >notheader\nAC\n",
+    "empty": "",
+    "only_headers": ">a\n>b\n",
+    "double_cr": "ACGT\r\r\nTTGA\n",
+}
+
+
+def main_read_reads():
+    """read_reads (debruijn.py:22-32) of the reference on the FASTA_CASES files: file text in, list of reads out.
+    (The aux_ prefix keeps the file out of tests/conftest.py::golden_case_names.)"""
+    import tempfile
+    cases = {}
+    with tempfile.TemporaryDirectory() as d:
+        for name, text in FASTA_CASES.items():
+            path = os.path.join(d, name + ".fasta")
+            with open(path, "wb") as fh:
+                fh.write(text.encode())
+            cases[name] = {"text": text, "reads": ref.read_reads(path)}
+    with open(os.path.join(GOLDEN, "aux_read_reads.json"), "w") as fh:
+        json.dump(cases, fh, indent=1, sort_keys=True)
+    print("aux_read_reads:", len(cases), "files")
+
+
 if __name__ == "__main__":
-    if sys.argv[1:] == ["support"]:
+    if sys.argv[1:] == ["read_reads"]:
+        main_read_reads()
+    elif sys.argv[1:] == ["support"]:
         main_support()
     elif sys.argv[1:] == ["wide"]:
         main_wide()
@@ -498,3 +531,4 @@ if __name__ == "__main__":
         main_pepwide()
         main_aux()
         main_support()
+        main_read_reads()

@@ -91,6 +91,8 @@ def test_device_fasta_ingest_matches_read_reads(name, tmp_path):
     p = tmp_path / (name + ".fasta")
     p.write_bytes(FASTA_CASES[name].encode())
     want = orc.read_reads(str(p))            # Python text mode: the reference's semantics
+    fixture = load_golden("aux_read_reads")[name]   # what the reference's read_reads returned on this file
+    assert fixture["text"] == FASTA_CASES[name] and want == fixture["reads"]
     assert prod.read_reads(str(p)) == want
     dev = prod.read_reads_device(str(p))
     assert len(dev) == len(want)

@@ -167,3 +167,87 @@ def test_1m_reads_equal_text_path(monkeypatch, tmp_path):
     print("NEXTK_1M " + json.dumps({"n_nodes_k32": gg.sizes()["n_nodes"], "contig_chars_k31": len(texts) and
                                     int(sum(lazy.lengths)), "text_path_seconds": round(t_text, 3),
                                     "text_fetch_seconds": round(t_fetch, 3), "new_path_seconds": round(t_new, 3)}))
+
+
+def _fasta_device_reads(tmp_path, bases, read_len):
+    """Fixed-length reads (bases) as a FASTA file, read back on the device."""
+    n = bases.size // read_len
+    rec = np.empty((n, 3 + read_len + 1), dtype=np.uint8)
+    rec[:, :3] = np.frombuffer(b">r\n", dtype=np.uint8)
+    rec[:, 3:3 + read_len] = bases.reshape(n, read_len)
+    rec[:, -1] = ord("\n")
+    path = tmp_path / "reads.fasta"
+    path.write_bytes(rec.tobytes())
+    return debruijn.read_reads_device(str(path))
+
+
+NEXTK_TEXT_BOUND = 4 << 30   # characters of contig text the oracle spells for the k + 1 build
+
+
+@pytest.mark.parametrize("src,n,k", [("configs1", 1_000_000, 31), ("g10m", 300_000, 62)])
+def test_next_k_equals_c_oracle(monkeypatch, tmp_path, src, n, k):
+    """construct_graph(lazy, k + 1) (dbg_build_from_walk, no text) against the C oracle's own k -> k + 1 step: its
+    contigs sorted stably by score, descending (II_assembleFromReads.py:64), its pull-out reads appended (:74), that
+    text spelled and built at k + 1, then traversed.  Node table, ranks, branch and pulled lists, pull-out reads and the
+    contig index must be equal."""
+    import synth
+    import test_traversal_vs_c_oracle as tv
+    from oracle import orc_c
+    thr = 2
+    monkeypatch.setattr(debruijn, "MAX_CONTIG_CHARS", 1)   # the k walk keeps no text: the driver gets LazyContigs
+    if src == "configs1":     # the first n reads of configs[1]
+        g0 = _dbg.Graph()
+        g0.synth_reads(1, GENOME, n, READ_LEN, 0.01)
+        bases, off = g0.copy_reads()
+        g0.close()
+    else:                     # 4.5x of a 10 Mbp genome: branches and tips at k = 62 and 63
+        bases = synth.reads_ascii(4, 10_000_000, n, READ_LEN, 0.01).reshape(-1)
+        off = np.arange(0, bases.size + 1, READ_LEN, dtype=np.uint64)
+
+    # the oracle's step: k-graph, sorted contigs + pull-out reads, (k+1)-graph
+    t0 = time.perf_counter()
+    o = orc_c.Oracle(bases, off, k)
+    t = o.traverse(thr)
+    assert t["branch"].size > 0 and t["n_pull_reads"] > 0
+    order = np.argsort(-t["score"].astype(np.int64), kind="stable")
+    assert t["contig_chars"] < NEXTK_TEXT_BOUND, t["contig_chars"]
+    text, toff = o.spell(order)
+    want_scores, want_lengths = t["score"][order], t["chars"][order]
+    o.close()
+    pr = np.nonzero(t["read_flags"])[0]
+    starts, lens = off[pr], np.diff(off)[pr]
+    pull_bytes = np.concatenate([bases[int(a):int(a + b)] for a, b in zip(starts, lens)])
+    nbases = np.concatenate([text, pull_bytes])
+    noff = np.concatenate([toff, toff[-1] + np.cumsum(lens, dtype=np.uint64)]).astype(np.uint64)
+    del text, pull_bytes
+    o1 = orc_c.Oracle(nbases, noff, k + 1)
+    t1 = o1.traverse(thr)
+    oracle_s = time.perf_counter() - t0
+
+    # the device's step, through the driver's surface
+    reads = _fasta_device_reads(tmp_path, bases, READ_LEN)
+    del bases
+    t0 = time.perf_counter()
+    lazy = _step_k(reads, k, thr, 1)
+    assert lazy.scores == want_scores.tolist() and lazy.lengths == want_lengths.tolist()   # the stable score sort
+    assert len(lazy._tail) == pr.size
+    calls = _counting_calls(monkeypatch)
+    monkeypatch.setattr(_dbg.Graph, "export_contig_text", lambda *a: (_ for _ in ()).throw(AssertionError("contig text fetched")))
+    got = _quiet(debruijn.construct_graph, lazy, k + 1, threshold=thr)
+    assert calls == [1]                                            # the dbg_build_from_walk path was taken
+    gg = got[0][0]._graph
+    assert gg.sizes()["n_reads"] == noff.size - 1 and gg.sizes()["n_bytes"] == int(noff[-1])
+    gg.walk(False, 0)
+    # node arrays are exported when compare() reaches them (host memory: one device array at a time next to the oracle)
+    dev = {"keys": lambda: gg.export_nodes(True, False, False, False)[0], "hi": gg.export_keys_hi,
+           "stamps": lambda: gg.export_nodes(False, True, False, False)[1],
+           "counts": lambda: gg.export_nodes(False, False, True, False)[2],
+           "flags": lambda: gg.export_nodes(False, False, False, True)[3], "keep": gg.export_keepmask,
+           "order": lambda: gg.export_orders()[0], "ranks": gg.export_pull_ranks, "read_flags": gg.export_pull_reads()}
+    dev["contig_off"], dev["score"], dev["stamp"], dev["seq"] = gg.export_contig_index()
+    device_s = time.perf_counter() - t0
+    tv.compare(o1, t1, dev, k + 1)
+    assert t1["branch"].size > 0 and t1["pulled"].size > 0 and t1["score"].size > 0
+    tv.report(f"next_k {src} {n} reads k={k}->{k + 1}", o1, t1, oracle_s, device_s,
+              f"k_contigs {order.size} k_contig_chars {int(toff[-1])} appended_reads {pr.size}")
+    o1.close()

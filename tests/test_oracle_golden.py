@@ -74,3 +74,15 @@ def test_oracle_unused_helpers_against_reference_vectors():
         V, E = orc.get_graph_from_kmers(list(kmers), c["k"])
         assert [[v, V[v].indegree, V[v].outdegree] for v in V] == c["vertices"]
         assert [[v, list(E[v])] for v in E] == c["edges"]
+
+
+def test_oracle_read_reads_against_reference_fixture(tmp_path):
+    """read_reads (debruijn.py:22-32) on the awkward FASTA files of test_hip_driver.py, against what the reference
+    returned on them (oracle/make_golden.py read_reads)."""
+    from conftest import load_golden
+    cases = load_golden("aux_read_reads")
+    assert len(cases) == 10
+    for name, c in sorted(cases.items()):
+        p = tmp_path / (name + ".fasta")
+        p.write_bytes(c["text"].encode())
+        assert orc.read_reads(str(p)) == c["reads"], name
