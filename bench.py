@@ -17,8 +17,12 @@ Workloads:
                      runs the same code.
 The driver launches N > 1 as  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel AND whole step) and
-`cpu_baseline` (the oracle's multi-threaded C restatement on the host cores this process may use, full input).
+Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel AND whole step, both from the
+timed steps' own clocks).  A plain run does no more than that line needs: set up, warm up, time the steps, write
+--dump-outputs, print.  --full adds everything that takes runs of its own, after the timed steps and never inside them:
+`first_build_ms`, `extras` (rest of the path, FASTA ingest, traversal in parts, error-free variant) and `cpu_baseline`
+(the oracle's multi-threaded C restatement on the host cores this process may use, full input, compared with the GPU
+graph through a digest); --no-extras and --no-cpu-baseline leave one of them out of a --full run.
 """
 import argparse
 import hashlib
@@ -333,12 +337,14 @@ def main():
     ap.add_argument("--err", type=float, default=0.01, help="per-base substitution rate")
     ap.add_argument("--coverage", type=float, default=30.0)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check what the headline "
+                    "figure does not need: first_build_ms, the untimed extras, the CPU baseline and its digest comparison")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-exchange-check", action="store_true", help="sharded builds: skip the per-message digests")
     ap.add_argument("--chunks", type=int, default=1, help="sharded builds: cut and send the records in this many parts, the "
                     "exchange of one under the extraction of the next (multi_gpu._exchange_records_in_parts); 1 = one exchange")
     ap.add_argument("--table-hint", type=int, default=0)
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extras (rest of the path, error-free variant)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the untimed extras (rest of the path, error-free variant)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one built as DIR/<name>.npy (float64; see dump_outputs)")
     args = ap.parse_args()
@@ -434,7 +440,7 @@ def main():
     # the first build on a read set also scans it for its alphabet (cached per read set): what the multi-k driver pays
     # after every `sequences.extend(...)`; the timed steps above are the steady state
     first_build_ms = None
-    if not sharded:
+    if args.full and not sharded:
         g.synth_reads(args.seed, genome_len, reads_per_rank, L, args.err, first_read=rank * reads_per_rank)
         sync()
         t1 = time.perf_counter()
@@ -485,17 +491,17 @@ def main():
         }
         gpu_digest = None
         # the untimed additions must never cost the headline line
-        if not sharded and not args.no_extras:
+        if args.full and not sharded and not args.no_extras:
             try:
                 out["extras"] = extras(g, args, k, L, genome_len, reads_per_rank)
             except Exception as e:  # noqa: BLE001
                 out["extras_error"] = f"{type(e).__name__}: {e}"
-        if not sharded and not args.no_cpu_baseline and k <= 31:
+        if args.full and not sharded and not args.no_cpu_baseline and k <= 31:
             try:
                 gpu_digest = node_digest_gpu(g)
             except Exception as e:  # noqa: BLE001
                 out["gpu_digest_error"] = f"{type(e).__name__}: {e}"
-        if not args.no_cpu_baseline and world == 1 and k <= 31:  # contract: rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and k <= 31:  # contract: rank 0 at N=1 only
             try:
                 out["cpu_baseline"] = cpu_baseline(g, L, k, reads_per_rank,
                                                    sz if not sharded else {"n_nodes": sz["n_nodes"], "n_edges": sz["n_edges"],

@@ -317,14 +317,14 @@ def test_bench_digest_on_the_device_equals_the_oracle_digest():
 
 
 def test_bench_line_contract_at_a_small_size(tmp_path):
-    """bench.py end to end in a child process (200 k reads): ONE JSON line with the driver's contract fields, the
+    """bench.py --full end to end in a child process (200 k reads): ONE JSON line with the driver's contract fields, the
     roofline and cpu_baseline blocks, the CPU/GPU digest comparison and the FASTA-ingest extra."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--reads", "200000", "--steps", "2", "--warmup", "1"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--reads", "200000", "--steps", "2", "--warmup", "1"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -345,6 +345,37 @@ def test_bench_line_contract_at_a_small_size(tmp_path):
     assert d["extras"]["traversal_in_parts_sizes"]["same_as_single_graph"] is True
     assert d["first_build_ms"] > 0 and c["one_thread"]["value"] > 0 and c["every_thread_scans_all_reads"]["value"] > 0
     assert "orc_build_mt_partitioned" in c["sample"]
+
+
+def test_bench_plain_run_is_lean_at_a_small_size(tmp_path):
+    """bench.py without --full (200 k reads): the same contract fields and roofline block as the --full line, the dumped
+    arrays, and nothing that takes runs of its own -- no cpu_baseline, no extras, no first build on a fresh read set."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--reads", "200000", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=600, cwd=root)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "roofline", "phases_ms", "graph"):
+        assert key in d, key
+    assert d["metric"] == "k-mers/s hashed+graph-built at k=31" and d["unit"] == "k-mers/s" and d["dtype"] == "u64"
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True
+    assert abs(d["value"] - 200000 * 120 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    r = d["roofline"]
+    assert r["bound"] == "hbm" and r["unit"] == "GB/s" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
+    for key in ("cpu_baseline", "cpu_baseline_error", "extras", "extras_error", "gpu_digest_error"):
+        assert key not in d, key
+    assert d["first_build_ms"] is None
+    sizes = np.load(tmp_path / "dump" / "sizes.npy")
+    assert sizes[0] == 200000 and sizes[2] == 200000 * 120 and sizes[4] == d["graph"]["n_nodes"]
+    for name in ("node_keys", "node_stamps", "node_counts", "node_succ_stamps"):
+        assert np.load(tmp_path / "dump" / (name + ".npy")).shape[0] > 0
 
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])

@@ -17,5 +17,5 @@ for pass in FETCH_SIZE WRITE_SIZE "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INS
 done
 cp $(find "$OUT/stats" -name "*kernel_stats.csv" | head -1) "$OUT/kernel_stats.csv"
 python3 tools/hbm_traffic.py "$OUT/pmc_FETCH_SIZE.json" "$OUT/pmc_WRITE_SIZE.json" > "$OUT/hbm_traffic_pmc.json"
-timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 > "$OUT/bench_line.log" 2>&1
+timeout -k 10 500 python3 bench.py --full --steps 20 --warmup 5 > "$OUT/bench_line.log" 2>&1
 echo "bench rc=$?"
