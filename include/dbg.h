@@ -135,7 +135,9 @@ int dbg_abi_version(void);
  * 1 = k_wsk_count; "stamp64" 1: dbg_build / dbg_build_multipass keep 64-bit stamps below 2 GiB of reads too (what larger
  * inputs get by themselves); "resolve_sorted" 1 (2: at any size): cross-bucket successor queries grouped by their target
  * before the resolver (measured slower: off); "wide_engine" 0: k > 31 on the global-table engine of round 1;
- * "extract_generic" 1: the window-minimum-through-LDS extraction kernels; "shard_stamp64" 1: dbg_shard_extract hands out
+ * "extract_generic" 1: the window-minimum-through-LDS extraction kernels; "extract_presplit" f0 in 0..6: dbg_build's
+ * extraction (13 <= k <= 31 over ACGT) writes its records pre-split by the top f0 bits of the bucket hash so that level 1 of
+ * the multisplit has 2^f0 times fewer children per group (0: one segment per workgroup); "shard_stamp64" 1: dbg_shard_extract hands out
  * 64-bit rank-local stamps; "target_distinct": mean distinct k-mers per bucket the geometry aims at (0 = default). */
 int dbg_set_option(dbg_t *h, const char *name, int64_t value);
 
@@ -306,6 +308,12 @@ int dbg_walk(dbg_t *h, int final_mode, uint64_t max_chars);
 
 int dbg_get_sizes(dbg_t *h, dbg_sizes_t *out);
 int dbg_get_stats(dbg_t *h, dbg_stats_t *out);
+/* Named event counters of the handle since dbg_create (they are not reset by a build):
+ * "extract_presplit_fallbacks": builds whose pre-split extraction overflowed a sub-segment and ran again without the split.
+ * "extract_presplit_rehists": builds whose level 1 took another width than the pre-split extraction had counted its
+ *   records for, so that the level ran its histogram pass after all.
+ * DBG_E_ARG for an unknown name. */
+int dbg_get_counter(dbg_t *h, const char *name, uint64_t *out);
 
 /* ---- exports: two-call pattern, sizes from dbg_get_sizes; NULL pointers are skipped */
 /* keys[n_nodes], stamps[n_nodes], counts[n_nodes*4] (by base code), flags[n_nodes]; table order */

@@ -26,7 +26,7 @@ SYMBOLS = (
     "dbg_synth_reads", "dbg_reads_checksum", "dbg_copy_reads", "dbg_reads_device", "dbg_build", "dbg_refine_edge_order", "dbg_export_orders",
     "dbg_get_alphabet", "dbg_export_keepmask", "dbg_export_dict_order",
     "dbg_prune", "dbg_remove_tips",
-    "dbg_mark_pull_reads", "dbg_walk", "dbg_get_sizes", "dbg_get_stats", "dbg_export_nodes", "dbg_export_keys_hi",
+    "dbg_mark_pull_reads", "dbg_walk", "dbg_get_sizes", "dbg_get_stats", "dbg_get_counter", "dbg_export_nodes", "dbg_export_keys_hi",
     "dbg_export_succ",
     "dbg_export_csr", "dbg_export_pull_ranks", "dbg_export_pull_reads", "dbg_export_contigs",
     "dbg_export_contig_index", "dbg_export_contig_text", "dbg_device_views", "dbg_shard_extract", "dbg_shard_bucket_counts", "dbg_shard_record_layout", "dbg_shard_build", "dbg_shard_answer", "dbg_shard_apply",
@@ -68,6 +68,9 @@ class IngestStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+COUNTERS = ("extract_presplit_fallbacks", "extract_presplit_rehists")  # dbg_get_counter names that Graph.stats() reports
 
 
 class DbgError(RuntimeError):
@@ -127,6 +130,7 @@ def load_library():
         "dbg_walk": (C.c_int, [H, C.c_int, C.c_uint64]),
         "dbg_get_sizes": (C.c_int, [H, C.POINTER(Sizes)]),
         "dbg_get_stats": (C.c_int, [H, C.POINTER(Stats)]),
+        "dbg_get_counter": (C.c_int, [H, C.c_char_p, C.POINTER(C.c_uint64)]),
         "dbg_export_nodes": (C.c_int, [H, vp, vp, vp, vp]),
         "dbg_export_keys_hi": (C.c_int, [H, vp]),
         "dbg_export_dict_order": (C.c_int, [H, vp]),
@@ -359,7 +363,12 @@ class Graph:
     def stats(self):
         s = Stats()
         self._chk(self._lib.dbg_get_stats(self._h, C.byref(s)))
-        return s.as_dict()
+        d = s.as_dict()
+        for name in COUNTERS:  # event counters of the handle, not of the last call
+            v = C.c_uint64()
+            self._chk(self._lib.dbg_get_counter(self._h, name.encode(), C.byref(v)))
+            d[name] = v.value
+        return d
 
     # ---- exports
     def alphabet(self):

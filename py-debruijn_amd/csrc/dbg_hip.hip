@@ -41,6 +41,16 @@
 
 using namespace dbgk;
 
+#ifndef DBG_L1_WIDE_FROM
+#define DBG_L1_WIDE_FROM 20  // total bucket bits from which level 1 of the multisplit takes 10 bits instead of 9 (11..20)
+#endif
+#ifndef DBG_PS_WG_PER_CU
+#define DBG_PS_WG_PER_CU DBG_EXW_WAVES  // extraction workgroups per CU of a pre-split extraction
+#endif
+#ifndef DBG_EXTRACT_PRESPLIT
+#define DBG_EXTRACT_PRESPLIT 4  // default of option "extract_presplit" 
+#endif
+
 // ------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------
@@ -152,6 +162,9 @@ struct dbg {
     int target_distinct = 0;  // option: mean distinct k-mers per bucket the auto geometry aims at (0 = default)
     int shard_stamp64 = 0;    // option: dbg_shard_extract hands out 64-bit rank-local stamps even below 2 GiB of reads (tests)
     int extract_generic = 0;  // option: 1 = the window-minimum-through-LDS extraction kernels instead of the per-window register ones (A/B, tests)
+    int extract_presplit = DBG_EXTRACT_PRESPLIT;  // option: dbg_build's extraction pre-splits its records by this many top bits of the bucket hash (0: off)
+    uint64_t presplit_rehists = 0;  // builds whose level 1 took another width than the pre-split extraction counted for, so it ran its histogram pass (dbg_get_counter)
+    uint64_t presplit_fallbacks = 0;  // builds whose pre-split extraction overflowed a sub-segment and ran again without the split (dbg_get_counter)
     uint64_t sk_n_ranges = 0, sk_n_buckets = 0;
     SkGeom sk_geom{};            // hash -> bucket mapping of the last partitioned build (k_succ_resolve)
     void *shard_state = nullptr;  // ShardState (multi-GPU builds)
@@ -2418,6 +2431,7 @@ extern "C" int dbg_set_option(dbg_t *h, const char *name, int64_t value) {
     if (n == "target_distinct" && value >= 0 && value <= 4096) { h->target_distinct = (int)value; return DBG_OK; }
     if (n == "shard_stamp64" && (value == 0 || value == 1)) { h->shard_stamp64 = (int)value; return DBG_OK; }
     if (n == "extract_generic" && (value == 0 || value == 1)) { h->extract_generic = (int)value; return DBG_OK; }
+    if (n == "extract_presplit" && value >= 0 && value <= SK_PS_MAX_F0) { h->extract_presplit = (int)value; return DBG_OK; }
     if (n == "refine_streaming" && (value == 0 || value == 1)) { h->refine_streaming = value != 0; return DBG_OK; }
     if (n == "walk_jump_min_nodes" && value >= 0) { h->walk_jump_min = (uint64_t)value; return DBG_OK; }
     if (n == "wide_engine" && (value == 0 || value == 1)) { h->wide_engine = (int)value; return DBG_OK; }
@@ -3326,6 +3340,15 @@ extern "C" int dbg_get_stats(dbg_t *h, dbg_stats_t *o) {
     return DBG_OK;
 }
 
+extern "C" int dbg_get_counter(dbg_t *h, const char *name, uint64_t *out) {
+    if (!h || !name || !out) return DBG_E_ARG;
+    const std::string n(name);
+    if (n == "extract_presplit_rehists") { *out = h->presplit_rehists; return DBG_OK; }
+    if (n == "extract_presplit_fallbacks") { *out = h->presplit_fallbacks; return DBG_OK; }
+    h->err = "unknown counter: " + n;
+    return DBG_E_ARG;
+}
+
 #define D2H(h, dst, src, bytes)                                                                       do {                                                                                                  if ((dst) && (bytes)) HIPCHK(h, hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, (h)->stream));     } while (0)
 
 extern "C" int dbg_export_nodes(dbg_t *h, uint64_t *keys, uint64_t *stamps, uint32_t *counts, uint8_t *flags) {
@@ -3546,13 +3569,21 @@ static int multisplit_level(dbg *h, const uint64_t *p_start, const uint64_t *p_c
                             uint64_t *out_w0, uint64_t *out_w1, ST *out_st, int shift, int nb, uint64_t *c_start,
                             uint64_t *c_cnt, dbg::Buf &b_scpre, dbg::Buf &b_cmat, dbg::Buf &b_offs, int fbits = 0,
                             const uint64_t *seg_add = nullptr, unsigned long long *d_sums = nullptr,
-                            const uint64_t *host_cnt = nullptr) {
+                            const uint64_t *host_cnt = nullptr, const uint32_t *ready_cmat = nullptr) {
     // spg: segments per group (n_seg: all segments form one group; 1: every segment is its own group)
     // host_cnt: the segment counts on the host, when the caller has them: the super-chunk prefix then needs no device scan
+    // ready_cmat: the count matrix, one row per segment, when whoever wrote the segments counted them (the pre-split
+    // extraction): every segment is then exactly one super-chunk, an empty one too, and the histogram pass is not run
     CHK(buf_ensure(h, b_scpre, (uint64_t)(n_seg + 1) * 8));
     uint64_t *sc_pre = (uint64_t *)b_scpre.p;
     uint64_t nsc = 0;
-    if (host_cnt) {
+    if (ready_cmat) {
+        std::vector<uint64_t> &pre = h->host_scpre;
+        pre.resize((size_t)n_seg + 1);
+        for (uint32_t i = 0; i <= n_seg; ++i) pre[i] = i;
+        nsc = n_seg;
+        HIPCHK(h, hipMemcpyAsync(sc_pre, pre.data(), pre.size() * 8, hipMemcpyHostToDevice, h->stream));
+    } else if (host_cnt) {
         std::vector<uint64_t> &pre = h->host_scpre;  // lives in the handle: the upload is asynchronous
         pre.resize((size_t)n_seg + 1);
         for (uint32_t i = 0; i < n_seg; ++i) { pre[i] = nsc; nsc += (host_cnt[i] + MS_SC - 1) / MS_SC; }
@@ -3564,17 +3595,19 @@ static int multisplit_level(dbg *h, const uint64_t *p_start, const uint64_t *p_c
     }
     MsParents P{p_start, p_cnt, sc_pre, n_seg, spg};
     const uint64_t n_log = nsc * (uint64_t)nb;
-    CHK(buf_ensure(h, b_cmat, n_log * 4));
+    if (!ready_cmat) CHK(buf_ensure(h, b_cmat, n_log * 4));
     CHK(buf_ensure(h, b_offs, n_log * 8));
-    uint32_t *cmat = (uint32_t *)b_cmat.p;
+    const uint32_t *cmat = ready_cmat ? ready_cmat : (const uint32_t *)b_cmat.p;
     uint64_t *offs = (uint64_t *)b_offs.p;
     if (nsc) {
-        if (d_sums)
+        if (ready_cmat)
+            ;
+        else if (d_sums)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ms_hist<true>), dim3((unsigned)nsc), dim3(256), 0, h->stream, P, in_w1, shift, nb,
-                               fbits, cmat, d_sums);
+                               fbits, (uint32_t *)b_cmat.p, d_sums);
         else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ms_hist<false>), dim3((unsigned)nsc), dim3(256), 0, h->stream, P, in_w1, shift, nb,
-                               fbits, cmat, (unsigned long long *)nullptr);
+                               fbits, (uint32_t *)b_cmat.p, (unsigned long long *)nullptr);
         HIPCHK(h, hipGetLastError());
         // (the total of the histograms equals `total` by construction; reading it back here would cost a host
         //  synchronisation per level -- k_ms_children takes the ends from `total` itself)
@@ -3594,10 +3627,41 @@ static int multisplit_level(dbg *h, const uint64_t *p_start, const uint64_t *p_c
     return DBG_OK;
 }
 
+// Provisional bucket geometry of a build, before anything was sampled: T bits in all, l1 of them at level 1.
+// target: mean distinct k-mers per final bucket; own: the shards the buckets are spread over.
+static void sk_provisional_bits(const dbg *h, uint64_t n_inst, double own, double target, int shard_bits, bool presplit_senders,
+                                int *T_out, int *l1_out) {
+    constexpr int T_MAX = 20;  // up to 10 + 10 bits; the estimate may add a third level
+    int T = h->bucket_bits;
+    if (T == 0) {  // auto: assume 40 % of the instances are distinct
+        const double want = (double)n_inst * own * 0.4 / target;
+        while (T < T_MAX && (double)(1ull << T) < want) ++T;
+    }
+    if (T < shard_bits) T = shard_bits;
+    if (presplit_senders) T = std::max(9, T);  // the senders split by 9 bits
+    *T_out = T;
+    *l1_out = T < 9 ? T : (T >= DBG_L1_WIDE_FROM && !presplit_senders ? 10 : 9);
+}
+
+// Mean distinct k-mers per final bucket of a build with CAP-slot LDS tables (table ~1/3 full: measured optimum).  One
+// constant for sk_extract's guess of the level-1 width and for sk_count_from_segments, which chooses it.
+template <int CAP> constexpr double SK_TARGET_DISTINCT = CAP * 0.36;
+
+// What a pre-split extraction (option "extract_presplit") leaves for level 1 of the multisplit: n_wg * 2^f0 sub-segments,
+// group-major (index child * n_wg + workgroup), none longer than one super-chunk.
+struct ExtractSplit {
+    double target = 0.0;            // in: SK_TARGET_DISTINCT of the build (level 1's width is guessed from it)
+    int f0 = 0;                     // 0: the extraction did not split (option off, a kernel without it, or the fallback)
+    uint32_t n_wg = 0;
+    int l1 = 0;                     // the level-1 width cmat was counted for
+    const uint32_t *cmat = nullptr; // level 1's count matrix, one row per sub-segment (nullptr: not counted)
+};
+
 // ---- stage 1: K1 extraction into one private segment per persistent workgroup (arena set 0)
 template <class ST>
 static int sk_extract(dbg *h, int k, uint64_t *w0[2], uint64_t *w1[2], ST *st[2], uint64_t **seg_start_out,
-                      uint64_t **seg_cnt_out, uint32_t *n_seg_out, uint64_t *n_rec_out, int part = 0, int n_parts = 1) {
+                      uint64_t **seg_cnt_out, uint32_t *n_seg_out, uint64_t *n_rec_out, int part = 0, int n_parts = 1,
+                      ExtractSplit *xs = nullptr) {
     const int m = sk_m_for_k(k), w = k - m + 1;
     unsigned long long *sc_dev = (unsigned long long *)h->d_scalars;
     // part p of n_parts: the k-mers whose first base lies in the tiles [T p / n, T (p + 1) / n) (dbg_shard_extract_part)
@@ -3605,20 +3669,55 @@ static int sk_extract(dbg *h, int k, uint64_t *w0[2], uint64_t *w1[2], ST *st[2]
     const uint64_t tile_first = all_tiles * (uint64_t)part / (uint64_t)n_parts;
     const uint64_t tiles = all_tiles * (uint64_t)(part + 1) / (uint64_t)n_parts - tile_first;
     uint64_t sc[8] = {0};
-    const uint32_t n_wg = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(tiles, 1), 2048);
-    CHK(buf_ensure(h, h->ar_misc[0], (uint64_t)n_wg * 4 * 8));
-    uint64_t *seg_start = (uint64_t *)h->ar_misc[0].p, *seg_cnt = seg_start + n_wg, *seg_nk = seg_cnt + n_wg,
-             *seg_ne = seg_nk + n_wg;
-    std::vector<uint64_t> hseg((size_t)n_wg * 4);
-    uint64_t n_rec = 0;
-    Timer t(h->stream);
-    const uint64_t tiles_per_wg = (tiles + n_wg - 1) / n_wg;
+    uint32_t n_wg = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(tiles, 1), 2048);
+    uint64_t tiles_per_wg = (tiles + n_wg - 1) / n_wg;
     // records per position: a window of w k-mers changes its minimizer about every (w + 1) / 2 positions, plus one
-    // record per read; sized at 1.3x that, and the second attempt (one record per position) cannot overflow
+    // record per read; sized at 1.3x that, and the last attempt (one record per position) cannot overflow
     const double density = std::min(1.0, 2.6 / (double)(w + 1) + 1.3 * (double)(h->n_reads + 1) / (double)(h->n_bytes + 1) + 0.01);
     uint64_t seg_cap = (w == 1) ? tiles_per_wg * TILE : (uint64_t)((double)(tiles_per_wg * TILE) * density) + 256;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        const uint64_t rec_cap = seg_cap * n_wg;
+    // pre-split (dbg_build, the register kernels): F0 sub-segments per workgroup, each 1.5x its even share of the
+    // workgroup's capacity and at most one super-chunk -- so many workgroups that this holds.  A skewed read set (low
+    // complexity: a few minimizers, so a few children) overflows a sub-segment; the build then extracts without the split.
+    int f0 = (xs && n_parts == 1 && tiles && m == SK_MAX_M && w <= 19 && !h->extract_generic) ? h->extract_presplit : 0;
+    constexpr double PS_SLACK = 1.5;
+    const uint32_t n_wg_plain = n_wg;
+    const uint64_t seg_cap_plain = seg_cap;
+    uint64_t n_seg = n_wg;
+    int ps_l1 = 0;
+    if (f0) {
+        const uint64_t F0 = 1ull << f0;
+        const double per_tile = (w == 1 ? 1.0 : density) * TILE * PS_SLACK / (double)F0;  // sub-segment records a tile may need
+        const uint64_t tpw_max = std::max<uint64_t>(1, (uint64_t)((double)(MS_SC - 64) / per_tile));
+        // as few workgroups as that allows, but one resident wave of them (DBG_EXW_WAVES per CU) where there are the tiles:
+        // long sub-segments -- level 1 runs one scatter workgroup per sub-segment, and 1 000 records do not pay for one
+        // (768 on the 256 CUs of an MI355X; DESIGN.md 3 has 1024 and 1536 measured beside it, on that chip only)
+        int n_cu = 0;
+        HIPCHK(h, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
+        n_wg = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(tiles, (uint64_t)n_cu * DBG_PS_WG_PER_CU), (tiles + tpw_max - 1) / tpw_max);
+        tiles_per_wg = (tiles + n_wg - 1) / n_wg;
+        seg_cap = std::min<uint64_t>(MS_SC, (uint64_t)((double)tiles_per_wg * per_tile) + 64);
+        n_seg = (uint64_t)n_wg * F0;
+        // level 1's width as sk_count_from_segments will choose it, from the k-mer instances the reads can hold at most
+        const uint64_t cut = h->n_reads * (uint64_t)(k - 1);
+        int T_guess = 0;
+        sk_provisional_bits(h, h->n_bytes > cut ? h->n_bytes - cut : 0, 1.0, xs->target, 0, false, &T_guess, &ps_l1);
+        if (ps_l1 < f0) ps_l1 = 0;  // fewer level-1 bits than the split took: no count matrix (level 1 runs as one group)
+    }
+    std::vector<uint64_t> hseg;
+    uint64_t *seg_start = nullptr, *seg_cnt = nullptr, *seg_nk = nullptr, *seg_ne = nullptr;
+    uint32_t *ps_cmat = nullptr;
+    uint64_t n_rec = 0;
+    Timer t(h->stream);
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        // segment table: start and count per (sub-)segment, k-mer and edge instances per workgroup
+        CHK(buf_ensure(h, h->ar_misc[0], (n_seg * 2 + (uint64_t)n_wg * 2) * 8));
+        seg_start = (uint64_t *)h->ar_misc[0].p; seg_cnt = seg_start + n_seg; seg_nk = seg_cnt + n_seg; seg_ne = seg_nk + n_wg;
+        hseg.assign((size_t)(n_seg * 2 + (uint64_t)n_wg * 2), 0);
+        if (f0 && ps_l1) {
+            CHK(buf_ensure(h, h->ar_misc[3], n_seg * 4 << (ps_l1 - f0)));
+            ps_cmat = (uint32_t *)h->ar_misc[3].p;
+        }
+        const uint64_t rec_cap = seg_cap * n_seg;
         for (int set = 0; set < 2; ++set) {
             CHK(buf_ensure(h, h->ar_rec[set][0], rec_cap * 8));
             CHK(buf_ensure(h, h->ar_rec[set][1], rec_cap * 8));
@@ -3627,18 +3726,23 @@ static int sk_extract(dbg *h, int k, uint64_t *w0[2], uint64_t *w1[2], ST *st[2]
             w1[set] = (uint64_t *)h->ar_rec[set][1].p;
             st[set] = (ST *)h->ar_rec[set][2].p;
         }
-        for (uint32_t g = 0; g < n_wg; ++g) hseg[g] = (uint64_t)g * seg_cap;
-        HIPCHK(h, hipMemcpyAsync(seg_start, hseg.data(), (size_t)n_wg * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemsetAsync(seg_cnt, 0, (size_t)n_wg * 3 * 8, h->stream));
+        for (uint64_t g = 0; g < n_seg; ++g) hseg[g] = g * seg_cap;
+        HIPCHK(h, hipMemcpyAsync(seg_start, hseg.data(), (size_t)n_seg * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemsetAsync(seg_cnt, 0, (size_t)(n_seg + (uint64_t)n_wg * 2) * 8, h->stream));
         HIPCHK(h, hipMemsetAsync(h->d_scalars, 0, 64 * 8, h->stream));
         if (tiles) {
             // m = 13 (k >= 13): the register kernel, one instantiation per window w = k - 12 in 1..19 -- the kernel that
             // looks the w hashes of every position up in LDS takes 12.5-15.6 ms at k = 23..30 where these take 3.3-3.7
             bool launched = false;
             if (m == SK_MAX_M && !h->extract_generic) {
-#define DBG_EXW_CASE(W_) case W_: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sk_extract_w<ST, W_>), dim3(n_wg), dim3(256), 0, h->stream, \
-                                                      h->d_bases, h->n_bytes, h->d_startbits, tiles, w0[0], w1[0], st[0], seg_cap, seg_cnt, \
-                                                      seg_nk, seg_ne, sc_dev, tile_first); launched = true; break;
+#define DBG_EXW_CASE(W_) case W_: \
+                if (f0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sk_extract_w<ST, W_, true>), dim3(n_wg), dim3(256), 0, h->stream, \
+                                           h->d_bases, h->n_bytes, h->d_startbits, tiles, w0[0], w1[0], st[0], seg_cap, seg_cnt, \
+                                           seg_nk, seg_ne, sc_dev, tile_first, f0, ps_l1, ps_l1 ? ps_cmat : (uint32_t *)nullptr); \
+                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sk_extract_w<ST, W_, false>), dim3(n_wg), dim3(256), 0, h->stream, \
+                                        h->d_bases, h->n_bytes, h->d_startbits, tiles, w0[0], w1[0], st[0], seg_cap, seg_cnt, \
+                                        seg_nk, seg_ne, sc_dev, tile_first, 0, 0, (uint32_t *)nullptr); \
+                launched = true; break;
                 switch (w) {
                     DBG_EXW_CASE(1) DBG_EXW_CASE(2) DBG_EXW_CASE(3) DBG_EXW_CASE(4) DBG_EXW_CASE(5) DBG_EXW_CASE(6) DBG_EXW_CASE(7)
                     DBG_EXW_CASE(8) DBG_EXW_CASE(9) DBG_EXW_CASE(10) DBG_EXW_CASE(11) DBG_EXW_CASE(12) DBG_EXW_CASE(13)
@@ -3654,25 +3758,35 @@ static int sk_extract(dbg *h, int k, uint64_t *w0[2], uint64_t *w1[2], ST *st[2]
             HIPCHK(h, hipGetLastError());
         }
         HIPCHK(h, hipMemcpyAsync(sc, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(hseg.data(), seg_start, (size_t)n_wg * 4 * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(hseg.data() + n_seg, seg_cnt, (size_t)(n_seg + (uint64_t)n_wg * 2) * 8, hipMemcpyDeviceToHost,
+                                 h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if (sc[0] & 1) { h->err = "reads hold a byte outside ACGT"; return DBG_E_ALPHABET; }
         if (!(sc[0] & 4)) break;
-        if (attempt == 1) { h->err = "super-k-mer record buffer overflow"; return DBG_E_CAPACITY; }
+        if (f0) {  // a sub-segment overflowed: today's one segment per workgroup, at its usual size
+            f0 = 0; ps_l1 = 0; ps_cmat = nullptr;
+            ++h->presplit_fallbacks;
+            n_wg = n_wg_plain; n_seg = n_wg;
+            tiles_per_wg = (tiles + n_wg - 1) / n_wg;
+            seg_cap = seg_cap_plain;
+            continue;
+        }
+        if (seg_cap == tiles_per_wg * TILE) { h->err = "super-k-mer record buffer overflow"; return DBG_E_CAPACITY; }
         seg_cap = tiles_per_wg * TILE;  // one record per position: cannot overflow
     }
     h->n_kmer_inst = h->n_edge_inst = 0;
+    for (uint64_t g = 0; g < n_seg; ++g) n_rec += hseg[n_seg + g];
     for (uint32_t g = 0; g < n_wg; ++g) {
-        n_rec += hseg[n_wg + g];
-        h->n_kmer_inst += hseg[2 * n_wg + g];
-        h->n_edge_inst += hseg[3 * n_wg + g];
+        h->n_kmer_inst += hseg[2 * n_seg + g];
+        h->n_edge_inst += hseg[2 * n_seg + n_wg + g];
     }
     h->stats.ms_extract = t.stop();
     h->stats.n_records = n_rec;
-    h->host_seg_cnt.assign(hseg.begin() + n_wg, hseg.begin() + 2 * (size_t)n_wg);
+    h->host_seg_cnt.assign(hseg.begin() + n_seg, hseg.begin() + 2 * (size_t)n_seg);
+    if (xs) { xs->f0 = f0; xs->n_wg = n_wg; xs->l1 = ps_l1; xs->cmat = ps_l1 ? ps_cmat : nullptr; }
     *seg_start_out = seg_start;
     *seg_cnt_out = seg_cnt;
-    *n_seg_out = n_wg;
+    *n_seg_out = (uint32_t)n_seg;
     *n_rec_out = n_rec;
     return DBG_OK;
 }
@@ -3697,28 +3811,23 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
                                   uint64_t n_rec, uint64_t n_inst, uint64_t n_edge_inst, const uint64_t *in_w0,
                                   const uint64_t *in_w1, const ST *in_st, uint64_t *w0[2], uint64_t *w1[2], ST *st[2],
                                   uint64_t node_capacity_hint, int shard_bits, int my_shard,
-                                  const Presplit *pre = nullptr) {
+                                  const Presplit *pre = nullptr, const ExtractSplit *xs = nullptr) {
     // pre: n_inst / n_edge_inst come in as upper bounds (the senders did not count per owner) and are replaced by the
     // exact sums of the level-2 histogram pass before anything is sized from them
+    // xs: the segments are the sub-segments of a pre-split extraction (sk_extract)
     const int m = sk_m_for_k(k);
     unsigned long long *sc_dev = (unsigned long long *)h->d_scalars;
     uint64_t sc[8] = {0};
     // ---- bucket geometry.  Level 1 takes up to 9 bits of the bucket hash; the remaining bits are
     //      chosen after level 1 from a distinct-k-mer estimate on one level-1 bucket (auto mode).
-    constexpr double TARGET_DISTINCT = CAP * 0.36;  // mean distinct k-mers per final bucket (table ~1/3 full: measured optimum)
-    constexpr int T_MAX = 20;                       // provisional geometry: up to 10 + 10 bits; the estimate may add a third level
+    constexpr double TARGET_DISTINCT = SK_TARGET_DISTINCT<CAP>;
     const double own = shard_bits ? (double)(1 << shard_bits) : 1.0;  // buckets are spread over `own` shards
-    int T = h->bucket_bits;
-    const bool auto_T = (T == 0);
-    if (auto_T) {  // provisional: assume 40 % of the instances are distinct
-        const double want = (double)n_inst * own * 0.4 / TARGET_DISTINCT;
-        while (T < T_MAX && (double)(1ull << T) < want) ++T;
-    }
-    if (T < shard_bits) T = shard_bits;
-    if (pre) T = std::max(9, T);  // the senders split by 9 bits
+    const bool auto_T = (h->bucket_bits == 0);
     // level 1 is fixed before the estimate refines the rest; forced geometries take plain bit fields: up to 10 bits at
     // level 2, what is left (the bucket hash has 22 bits) at level 3
-    int l1 = T < 9 ? T : (T >= 20 && !pre ? 10 : 9), l2 = std::min(10, T - l1);
+    int T = 0, l1 = 0;
+    sk_provisional_bits(h, n_inst, own, TARGET_DISTINCT, shard_bits, pre != nullptr, &T, &l1);
+    int l2 = std::min(10, T - l1);
     int nb2 = 0;                                            // children of the second level (0: not decided yet)
     int nb3 = (T - l1 - l2) > 0 ? 1 << (T - l1 - l2) : 1;   // children of the third level
     const int nb1 = 1 << l1;
@@ -3753,9 +3862,18 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
     } else {
         const uint64_t *host_cnt = (h->host_seg_cnt.size() == n_seg && seg_cnt == (const uint64_t *)h->ar_misc[0].p + n_seg)
                                        ? h->host_seg_cnt.data() : nullptr;  // the segments sk_extract just wrote
-        CHK((multisplit_level<ST, true>(h, seg_start, seg_cnt, n_seg, n_seg, n_rec, in_w0, in_w1, in_st, w0[1], w1[1], st[1],
-                                        top - l1, nb1, c1_start, c1_cnt, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], 0, nullptr,
-                                        nullptr, host_cnt)));
+        if (xs && xs->f0 && l1 >= xs->f0) {
+            // pre-split extraction: 2^f0 groups of n_wg sub-segments, each group split by the l1 - f0 low bits of the level-1
+            // digit -- child (group g, digit b) = g * (nb1 >> f0) + b is the level-1 bucket of the one-group split
+            if (xs->l1 != l1) ++h->presplit_rehists;
+            CHK((multisplit_level<ST, true>(h, seg_start, seg_cnt, n_seg, xs->n_wg, n_rec, in_w0, in_w1, in_st, w0[1], w1[1], st[1],
+                                            top - l1, nb1 >> xs->f0, c1_start, c1_cnt, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], 0,
+                                            nullptr, nullptr, host_cnt, xs->l1 == l1 ? xs->cmat : nullptr)));
+        } else {
+            CHK((multisplit_level<ST, true>(h, seg_start, seg_cnt, n_seg, n_seg, n_rec, in_w0, in_w1, in_st, w0[1], w1[1], st[1],
+                                            top - l1, nb1, c1_start, c1_cnt, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], 0, nullptr,
+                                            nullptr, host_cnt)));
+        }
         where = 1;
     }
     if (auto_T && l1 >= 9 && n_rec) {  // refine T from a sample: the first level-1 bucket this shard owns
@@ -4532,9 +4650,11 @@ static int build_sk_t(dbg *h, int k, uint64_t node_capacity_hint) {
     uint64_t *w0[2], *w1[2], *seg_start = nullptr, *seg_cnt = nullptr, n_rec = 0;
     ST *st[2];
     uint32_t n_seg = 0;
-    CHK(sk_extract<ST>(h, k, w0, w1, st, &seg_start, &seg_cnt, &n_seg, &n_rec));
+    ExtractSplit xs;
+    xs.target = SK_TARGET_DISTINCT<CAP>;
+    CHK(sk_extract<ST>(h, k, w0, w1, st, &seg_start, &seg_cnt, &n_seg, &n_rec, 0, 1, &xs));
     return sk_count_from_segments<ST, CAP>(h, k, seg_start, seg_cnt, n_seg, n_rec, h->n_kmer_inst, h->n_edge_inst, w0[0],
-                                           w1[0], st[0], w0, w1, st, node_capacity_hint, 0, 0);
+                                           w1[0], st[0], w0, w1, st, node_capacity_hint, 0, 0, nullptr, &xs);
 }
 
 static int build_sk(dbg *h, int k, uint64_t node_capacity_hint) {

@@ -218,19 +218,40 @@ struct SkLdsW {
 #ifndef DBG_EXW_WAVES
 #define DBG_EXW_WAVES 3
 #endif
-template <class ST, int W>
+// PS (pre-split, option "extract_presplit"): the workgroup writes its records into 2^f0 sub-segments, one per value of the
+// top f0 bits of the bucket hash, laid out group-major (sub-segment (child c, workgroup g) = index c * gridDim.x + g, seg_cap
+// records each) -- level 1 of the multisplit then splits every one of the 2^f0 groups by the remaining l1 - f0 bits only,
+// with pieces 2^f0 times as long.  The place of a record is an LDS cursor per child: one LDS atomic, no barrier.  The
+// workgroup also counts its records by the whole level-1 digit (l1 bits) and leaves that as rows c * gridDim.x + g of
+// level 1's count matrix (cmat, 2^(l1 - f0) entries a row; nullptr: not wanted), which saves the level its histogram pass.
+// A child that outgrows its sub-segment raises the overflow flag; the caller then extracts without the split.
+constexpr int SK_PS_MAX_F0 = 6;
+template <bool PS> struct SkLdsPs {};
+template <> struct SkLdsPs<true> {
+    uint32_t cur[1 << SK_PS_MAX_F0];  // records of this workgroup per child so far
+    uint32_t h1[1024];                // ... per level-1 digit (MS_MAX_NB)
+    uint32_t ovf;
+};
+template <class ST, int W, bool PS = false>
 __global__ __launch_bounds__(256, DBG_EXW_WAVES) void k_sk_extract_w(const char *__restrict__ bases, uint64_t n_bytes,
                                                       const uint32_t *__restrict__ startbits, uint64_t n_tiles,
                                                       uint64_t *rec_w0, uint64_t *rec_w1, ST *rec_st, uint64_t seg_cap,
                                                       uint64_t *seg_cnt, uint64_t *seg_nk, uint64_t *seg_ne,
-                                                      unsigned long long *scalars /* [0] err */, uint64_t tile_first) {
+                                                      unsigned long long *scalars /* [0] err */, uint64_t tile_first,
+                                                      int f0 = 0, int l1 = 0, uint32_t *cmat = nullptr) {
     constexpr int M = SK_MAX_M, K = W + M - 1, NV = 32 + W - 1;
     static_assert(TILE == 256 * 32, "one lane per 32 positions");
     static_assert(K <= 31 && NV + M - 1 <= 64, "window must fit the two 32-base registers");
     __shared__ SkLdsW s;
+    __shared__ SkLdsPs<PS> ps;
     __shared__ uint64_t red[8];
+    if constexpr (PS) {
+        for (int i = threadIdx.x; i < 1024; i += 256) ps.h1[i] = 0;
+        if (threadIdx.x < (1 << SK_PS_MAX_F0)) ps.cur[threadIdx.x] = 0;
+        if (threadIdx.x == 0) ps.ovf = 0;
+    }
     const uint64_t t_beg = tile_first + n_tiles * blockIdx.x / gridDim.x, t_end = tile_first + n_tiles * (blockIdx.x + 1) / gridDim.x;
-    const uint64_t seg0 = (uint64_t)blockIdx.x * seg_cap;
+    const uint64_t seg0 = (uint64_t)blockIdx.x * seg_cap;  // !PS: this workgroup's one segment and the records in it so far
     uint64_t cursor = 0;
     constexpr uint32_t mid_mask = (1u << (K - 1)) - 1u;
     uint64_t n_k = 0, n_e = 0;
@@ -239,6 +260,9 @@ __global__ __launch_bounds__(256, DBG_EXW_WAVES) void k_sk_extract_w(const char 
     for (uint64_t tile = t_beg; tile < t_end; ++tile) {
         const uint64_t tile0 = tile * TILE;
         __syncthreads();
+        if constexpr (PS) {
+            if (ps.ovf) { overflow = true; break; }  // uniform: raised while the previous tile was written
+        }
         const uint32_t bad = load_tile(s.t, bases, n_bytes, startbits, tile0);
         if (bad) atomicOr(&scalars[0], 1ull);
         __syncthreads();
@@ -308,9 +332,12 @@ __global__ __launch_bounds__(256, DBG_EXW_WAVES) void k_sk_extract_w(const char 
         }
         __syncthreads();
         const uint32_t nrec = s.nrec;
-        if (cursor + nrec > seg_cap) { overflow = true; break; }
-        const uint64_t gbase = seg0 + cursor;
-        cursor += nrec;
+        uint64_t gbase = 0;
+        if constexpr (!PS) {
+            if (cursor + nrec > seg_cap) { overflow = true; break; }
+            gbase = seg0 + cursor;
+            cursor += nrec;
+        }
         {  // dense work list of record starts: this lane's 32 positions
             uint32_t sm = smask;
             uint32_t li = s.wpre[threadIdx.x >> 1] + ((threadIdx.x & 1) ? __popc((uint32_t)s.sbits[threadIdx.x >> 1]) : 0);
@@ -350,20 +377,37 @@ __global__ __launch_bounds__(256, DBG_EXW_WAVES) void k_sk_extract_w(const char 
             const uint32_t mp = j + s.minp[j];
             const uint32_t bh = bucket_hash22((uint32_t)(window32(s.t, mp) >> (64 - 2 * M)));
             const uint64_t w1 = (hi & (~0ull << SK_META_BITS)) | ((uint64_t)bh << 6) | ((uint64_t)(len - 1) << 1) | has_succ;
-            const uint64_t o = gbase + r;
+            uint64_t o = gbase + r;  // PS: replaced below
+            if constexpr (PS) {
+                const uint32_t c = bh >> (SK_BUCKET_BITS - f0);
+                const uint32_t rk = atomicAdd(&ps.cur[c], 1u);  // rank inside the child's sub-segment
+                if (cmat) atomicAdd(&ps.h1[bh >> (SK_BUCKET_BITS - l1)], 1u);
+                if (rk >= seg_cap) { ps.ovf = 1; continue; }
+                o = ((uint64_t)c * gridDim.x + blockIdx.x) * seg_cap + rk;
+            }
             rec_w0[o] = w0;
             rec_w1[o] = w1;
             rec_st[o] = (ST)((p << 1) | (s0 ^ 1u));
         }
     }
-    if (overflow && threadIdx.x == 0) atomicOr(&scalars[0], 4ull);
     n_k = wave_sum_u64(n_k);
     n_e = wave_sum_u64(n_e);
     __syncthreads();
+    if constexpr (PS) {
+        if (ps.ovf) overflow = true;  // ... while the last tile was written
+        if (threadIdx.x < (1 << f0))
+            seg_cnt[(uint64_t)threadIdx.x * gridDim.x + blockIdx.x] = min(ps.cur[threadIdx.x], (uint32_t)seg_cap);
+        if (cmat) {  // row (child c, this workgroup) holds the digits c * nbg .. (c + 1) * nbg - 1
+            const int nbg = 1 << (l1 - f0);
+            for (int d = threadIdx.x; d < (1 << l1); d += 256)
+                cmat[((uint64_t)(d >> (l1 - f0)) * gridDim.x + blockIdx.x) * nbg + (d & (nbg - 1))] = ps.h1[d];
+        }
+    }
+    if (overflow && threadIdx.x == 0) atomicOr(&scalars[0], 4ull);
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = n_k; red[4 + (threadIdx.x >> 6)] = n_e; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        seg_cnt[blockIdx.x] = cursor;
+        if constexpr (!PS) seg_cnt[blockIdx.x] = cursor;
         seg_nk[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
         seg_ne[blockIdx.x] = red[4] + red[5] + red[6] + red[7];
     }

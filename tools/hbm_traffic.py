@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/rNN_hbm_traffic_pmc.json from the FETCH_SIZE and WRITE_SIZE passes of tools/profile_round.sh.
+"""profiles/rNN_hbm_traffic_pmc.json from the per-kernel json (tools/pmc_summary.py) of a FETCH_SIZE and a WRITE_SIZE pass.
 
 Per kernel and launch: FETCH_SIZE doubled (MI355X_MICROARCH.md: on gfx950 it tallies 128-byte requests at 64 bytes),
 WRITE_SIZE as read, both in GB; plus the hash of the kernel sources the numbers were measured on -- bench.py reports
@@ -25,5 +25,5 @@ for name in sorted(set(fetch) | set(write)):
                  "hbm_read_GB_corrected_x2": 2 * fk * 1024 / 1e9, "hbm_write_GB": wk * 1024 / 1e9})
 rows.sort(key=lambda r: -(r["hbm_read_GB_corrected_x2"] + r["hbm_write_GB"]))
 print(json.dumps({"kernel_source_hash": bench.kernel_source_hash(), "command": "python3 bench.py --steps 2 --warmup 1 "
-                  "--no-cpu-baseline --no-extras under rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes)",
+                  "under rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (counters only, one pass each)",
                   "kernels": rows}, indent=1))

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Collects the evidence bench.py's roofline block cites (run on the GPU box through gpurun):
-#   kernel-trace stats of the default bench command, then separate --pmc passes for HBM traffic and LDS counters.
+#   kernel-trace stats of the default bench command, then separate counters-only --pmc passes for HBM traffic and LDS counters.
 # Output: gpurun_out/prof_<tag>/...; tools/pmc_summary.py turns the counter csv files into per-kernel json.
 set -uo pipefail
 TAG=${1:-r02}
@@ -11,7 +11,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/
 echo "stats rc=$?"
 for pass in FETCH_SIZE WRITE_SIZE "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_ANY" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM SQ_INSTS_SMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS"; do
   name=$(echo "$pass" | cut -d' ' -f1)
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $pass --output-format csv -d "$OUT/pmc_$name" -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > "$OUT/pmc_$name.log" 2>&1
+  timeout -k 10 300 rocprofv3 --pmc $pass --output-format csv -d "$OUT/pmc_$name" -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras > "$OUT/pmc_$name.log" 2>&1
   echo "pmc $name rc=$?"
   python3 tools/pmc_summary.py "$OUT/pmc_$name" > "$OUT/pmc_$name.json"
 done
