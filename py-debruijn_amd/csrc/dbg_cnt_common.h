@@ -67,12 +67,12 @@ __device__ inline void cnt_take_reservation(LDS &s, const OUT &orr, unsigned lon
     const unsigned long long base = got & 0xFFFFFFFFull, eb = got >> 32;
     s.gbase = base;
     s.ebase = eb;
-    if (base + n_local > orr.node_cap || base + n_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], 16ull); s.fail = 1; }
-    if (eb + n_edges_local > orr.edge_cap || eb + n_edges_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], 16ull); s.fail = 1; }
+    if (base + n_local > orr.node_cap || base + n_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], STATUS_NODE_EDGE_CAP); s.fail = 1; }
+    if (eb + n_edges_local > orr.edge_cap || eb + n_edges_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], STATUS_NODE_EDGE_CAP); s.fail = 1; }
     uint64_t ri = bucket;
     if (cur_mask) {
         ri = orr.n_buckets + atomicAdd(&orr.scalars[6], 1ull);
-        if (ri >= orr.range_cap || ri >= 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], 32ull); s.fail = 1; }
+        if (ri >= orr.range_cap || ri >= 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], STATUS_RANGE_CAP); s.fail = 1; }
     }
     s.ri = ri;
     if (!s.fail) {

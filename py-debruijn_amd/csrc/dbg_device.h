@@ -9,6 +9,26 @@ namespace dbgk {
 constexpr uint64_t EMPTY_KEY = ~0ull;
 constexpr uint32_t NO_NODE = 0xFFFFFFFFu;
 
+// Status bits of word 0 of a handle's scalar block (scalars[0]): kernels raise them with atomicOr, the host tests them after
+// the stream has drained.  A bit means what its launch sequence says: three values serve two sequences that never run together.
+enum Status : unsigned long long {
+    STATUS_BAD_BASE = 1,            // reads hold a byte outside ACGT
+    STATUS_BAD_START = 1,           //   (walk) a start node is not a splitter
+    STATUS_TABLE_FULL = 2,          // global hash table full
+    STATUS_SEGMENT_FULL = 4,        // an extraction segment overflowed
+    STATUS_BUCKET_TOO_BIG = 8,      // a bucket could not be split to fit the LDS table
+    STATUS_NODE_EDGE_CAP = 16,      // node or edge arrays too small
+    STATUS_RANGE_CAP = 32,          // range list overflow
+    STATUS_WIDE_COUNTER16 = 32,     //   (global-table engine, two-word k-mers) a 16-bit successor counter is full
+    STATUS_QUERY_CAP = 64,          // query list overflow
+    STATUS_SUCC_MISSING = 128,      // a successor k-mer (an edge endpoint) was not found
+    STATUS_REMOTE_UNRESOLVED = 256, // a successor owned by another shard or part came back unresolved
+    STATUS_COUNTER16 = 512,         // LDS engines: a 16-bit successor counter overflowed
+    STATUS_BAD_GATHERED_ID = 512,   //   (dbg_import_graph) a gathered successor id does not fit the shard sizes
+    STATUS_CLAIM_STUCK = 1024,      // two-word count kernels: an LDS slot claim never completed
+    STATUS_INCONSISTENT = 2048,     // a count kernel's two totals of a bucket disagree
+};
+
 // One hash slot: 32 bytes, so the key probe, the stamp min and the successor
 // counter add of one record touch a single 128-byte line.
 struct __attribute__((aligned(32))) Slot {

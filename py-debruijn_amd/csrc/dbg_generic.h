@@ -75,13 +75,13 @@ __global__ __launch_bounds__(256) void k_g_insert(const char *__restrict__ bases
         const unsigned long long stamp = (p << 1) | (s0 ^ 1u);
         bool full = false;
         const uint64_t slot = gen_insert(nodes, mask, key, occ, &full);
-        if (full) { atomicOr(&scalars[0], 2ull); continue; }
+        if (full) { atomicOr(&scalars[0], STATUS_TABLE_FULL); continue; }
         atomicMin(&nodes[slot].stamp, stamp);
         ++n_k;
         if (!sk) {
             const uint64_t ekey = (key << GEN_BITS) | lut[(uint8_t)bases[p + k]];
             const uint64_t es = gen_insert(edges, mask, ekey, eocc, &full);
-            if (full) { atomicOr(&scalars[0], 2ull); continue; }
+            if (full) { atomicOr(&scalars[0], STATUS_TABLE_FULL); continue; }
             atomicAdd(&edges[es].count, 1u);
             atomicMin(&edges[es].stamp, (unsigned long long)p);
             ++n_e;
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void k_g_edges(const GenEdgeSlot *edges, uint6
     const uint64_t kmask = (1ull << (GEN_BITS * k)) - 1;
     const uint32_t code = (uint32_t)(ekey & (GEN_D - 1));
     const uint32_t src = gen_find(nodes, mask, ekey >> GEN_BITS), dst = gen_find(nodes, mask, ekey & kmask);
-    if (src == NO_NODE || dst == NO_NODE) { atomicOr(&scalars[0], 128ull); return; }
+    if (src == NO_NODE || dst == NO_NODE) { atomicOr(&scalars[0], STATUS_SUCC_MISSING); return; }
     const uint64_t o = (uint64_t)src * GEN_D + code;
     cnt[o] = edges[i].count;
     succ[o] = dst;

@@ -71,14 +71,14 @@ __global__ __launch_bounds__(256) void k_gr_insert(const char *__restrict__ base
         const uint64_t hv = gr_hash(bases, p, k);
         const unsigned long long stamp = (p << 1) | (s0 ^ 1u);
         if (gr_insert<1>(ntab, mask, hash_shift, hv, ((hv & 0xFFFFull) << 48) | stamp, bases, p, k, nocc) < 0) {
-            atomicOr(&scalars[0], 2ull);
+            atomicOr(&scalars[0], STATUS_TABLE_FULL);
             continue;
         }
         ++n_k;
         if (!sk) {
             const uint64_t he = gr_hash(bases, p, k + 1);
             const int64_t es = gr_insert<0>(etab, mask, hash_shift, he, ((he & 0xFFFFull) << 48) | p, bases, p, k + 1, eocc);
-            if (es < 0) { atomicOr(&scalars[0], 2ull); continue; }
+            if (es < 0) { atomicOr(&scalars[0], STATUS_TABLE_FULL); continue; }
             atomicAdd(&ecount[es], 1u);
             ++n_e;
         }
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(256) void k_gr_edges(const unsigned long long *__re
     const uint32_t code = lut[(uint8_t)bases[q + k]];
     const uint32_t src = gr_find(ntab, mask, hash_shift, bases, stamps, q, k);
     const uint32_t dst = gr_find(ntab, mask, hash_shift, bases, stamps, q + 1, k);
-    if (src == NO_NODE || dst == NO_NODE || code >= (uint32_t)GEN_D) { atomicOr(&scalars[0], 128ull); return; }
+    if (src == NO_NODE || dst == NO_NODE || code >= (uint32_t)GEN_D) { atomicOr(&scalars[0], STATUS_SUCC_MISSING); return; }
     const uint64_t o = (uint64_t)src * GEN_D + code;
     cnt[o] = ecount[i];
     succ[o] = dst;

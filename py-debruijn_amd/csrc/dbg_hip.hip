@@ -41,6 +41,20 @@
 
 using namespace dbgk;
 
+// Slots of the arena h->ar_misc: one meaning each, in every build path of the super-k-mer engines
+enum MiscSlot {
+    MISC_SEGMENTS,      // segment table: what the extraction wrote, or the (bucket, sender) segments a shard received
+    MISC_L1_CHILDREN,   // children of multisplit level 1 (start, count)
+    MISC_MS_SCPRE,      // multisplit_level's scratch: super-chunk prefix,
+    MISC_MS_CMAT,       // ... count matrix (a pre-split extraction writes level 1's itself),
+    MISC_MS_OFFS,       // ... scanned offsets
+    MISC_BUCKETS,       // final buckets (start, count)
+    MISC_RANGES,        // SkRange per bucket and per hash sub-range
+    MISC_QUERY_SEGS,    // segments of the cross-bucket queries' owner / target split
+    MISC_ESTIMATE_SET,  // hash set of the distinct-k-mer estimate
+    MISC_SLOTS
+};
+
 #ifndef DBG_L1_WIDE_FROM
 #define DBG_L1_WIDE_FROM 20  // total bucket bits from which level 1 of the multisplit takes 10 bits instead of 9 (11..20)
 #endif
@@ -156,7 +170,7 @@ struct dbg {
         void *p = nullptr;
         uint64_t bytes = 0;
     };
-    Buf ar_rec[2][3], ar_q[2][3], ar_node[8], ar_misc[9], ar_csr[4], ar_dir, ar_l2, ar_scan, ar_shard[6], ar_walk[3], ar_wide[6], ar_refine[4], ar_tips[4], ar_part[4][3] /* records of dbg_shard_extract_part, per part */;
+    Buf ar_rec[2][3], ar_q[2][3], ar_node[8], ar_misc[MISC_SLOTS], ar_csr[4], ar_dir, ar_l2, ar_scan, ar_shard[6], ar_walk[3], ar_wide[6], ar_refine[4], ar_tips[4], ar_part[4][3] /* records of dbg_shard_extract_part, per part */;
     int sk_T = 0, sk_l1 = 0, sk_l2 = 0, sk_nb2 = 0 /* scaled second level, 0 = power of two */, sk_cap = 0;
     bool refine_streaming = false;  // option (tests): dbg_refine_edge_order always takes the pass over the reads
     int target_distinct = 0;  // option: mean distinct k-mers per bucket the auto geometry aims at (0 = default)
@@ -496,7 +510,7 @@ __global__ __launch_bounds__(256) void k_count(const char *__restrict__ bases, u
     __shared__ TileLds t;
     const uint64_t tile0 = (uint64_t)blockIdx.x * TILE;
     const uint32_t bad = load_tile(t, bases, n_bytes, startbits, tile0);
-    if (bad) atomicOr(&scalars[0], 1ull);
+    if (bad) atomicOr(&scalars[0], STATUS_BAD_BASE);
     __syncthreads();
 
     const uint32_t mid_mask = (k >= 2) ? ((1u << (k - 1)) - 1u) : 0u;
@@ -531,7 +545,7 @@ __global__ __launch_bounds__(256) void k_count(const char *__restrict__ bases, u
             if (cur == kmer) { found = true; break; }
             slot = (slot + 1) & cap_mask;
         }
-        if (!found) { atomicOr(&scalars[0], 2ull); continue; }  // table full
+        if (!found) { atomicOr(&scalars[0], STATUS_TABLE_FULL); continue; }  // table full
         if (!sk) atomicAdd(&tab[slot].cnt[b], 1u);
         atomicMin(&tab[slot].stamp, (unsigned long long)stamp);
     }
@@ -1462,7 +1476,7 @@ __global__ __launch_bounds__(256) void k_jump_start_ranks(const uint32_t *__rest
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_starts) return;
     const uint32_t r = n_list ? jump_rank(list, n_list, starts[i]) : 0u;
-    if (!n_list || list[r] != starts[i]) atomicOr(&scalars[0], 1ull);
+    if (!n_list || list[r] != starts[i]) atomicOr(&scalars[0], STATUS_BAD_START);
     rank[i] = r;
 }
 
@@ -2301,7 +2315,7 @@ static int build_genref(dbg *h, int k) {
         uint64_t sc[4] = {0, 0, 0, 0};
         if (hipMemcpyAsync(sc, h->d_scalars, 32, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "generic count failed"; rc = DBG_E_HIP; break; }
-        if (sc[0] & 2) { h->err = "generic engine: hash table full"; rc = DBG_E_CAPACITY; break; }
+        if (sc[0] & STATUS_TABLE_FULL) { h->err = "generic engine: hash table full"; rc = DBG_E_CAPACITY; break; }
         h->n_kmer_inst = sc[1];
         h->n_edge_inst = sc[2];
         h->stats.ms_count = t_count.stop();
@@ -2337,7 +2351,7 @@ static int build_genref(dbg *h, int k) {
         }
         if (hipMemcpyAsync(sc, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "generic graph assembly failed"; rc = DBG_E_HIP; break; }
-        if (sc[0] & 128) { h->err = "internal: edge endpoint missing from the node table"; rc = DBG_E_HIP; break; }
+        if (sc[0] & STATUS_SUCC_MISSING) { h->err = "internal: edge endpoint missing from the node table"; rc = DBG_E_HIP; break; }
         h->stats.ms_succ = t_c.stop();
         h->order_exact = true;  // ranks come from per-edge first-seen positions already
     } while (0);
@@ -2376,7 +2390,7 @@ static int build_generic(dbg *h, int k) {
         uint64_t sc[4] = {0, 0, 0, 0};
         if (hipMemcpyAsync(sc, h->d_scalars, 32, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "generic count failed"; rc = DBG_E_HIP; break; }
-        if (sc[0] & 2) { h->err = "generic engine: hash table full"; rc = DBG_E_CAPACITY; break; }
+        if (sc[0] & STATUS_TABLE_FULL) { h->err = "generic engine: hash table full"; rc = DBG_E_CAPACITY; break; }
         h->n_kmer_inst = sc[1];
         h->n_edge_inst = sc[2];
         h->stats.ms_count = t_count.stop();
@@ -2412,7 +2426,7 @@ static int build_generic(dbg *h, int k) {
         }
         if (hipMemcpyAsync(sc, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "generic graph assembly failed"; rc = DBG_E_HIP; break; }
-        if (sc[0] & 128) { h->err = "internal: edge endpoint missing from the node table"; rc = DBG_E_HIP; break; }
+        if (sc[0] & STATUS_SUCC_MISSING) { h->err = "internal: edge endpoint missing from the node table"; rc = DBG_E_HIP; break; }
         h->stats.ms_succ = t_c.stop();
         h->order_exact = true;  // ranks come from per-edge first-seen positions already
     } while (0);
@@ -2497,9 +2511,9 @@ static int build_wide_once(dbg *h, int k, uint64_t table_capacity_hint, bool pac
         hipError_t e = hipMemcpyAsync(sc, h->d_scalars, 32, hipMemcpyDeviceToHost, h->stream);
         h->stats.ms_count = tc.stop();
         if (e != hipSuccess || hipGetLastError() != hipSuccess) { h->err = "k_wcount failed"; rc = DBG_E_HIP; break; }
-        if (sc[0] & 1) { h->err = "reads hold a byte outside ACGT"; rc = DBG_E_ALPHABET; break; }
-        if (sc[0] & 2) { h->err = "hash table capacity exceeded"; rc = DBG_E_CAPACITY; break; }
-        if (sc[0] & 32) { *overflow = true; rc = DBG_E_CAPACITY; h->err = "successor counter overflow"; break; }
+        if (sc[0] & STATUS_BAD_BASE) { h->err = "reads hold a byte outside ACGT"; rc = DBG_E_ALPHABET; break; }
+        if (sc[0] & STATUS_TABLE_FULL) { h->err = "hash table capacity exceeded"; rc = DBG_E_CAPACITY; break; }
+        if (sc[0] & STATUS_WIDE_COUNTER16) { *overflow = true; rc = DBG_E_CAPACITY; h->err = "successor counter overflow"; break; }
         h->n_kmer_inst = sc[1];
         h->n_edge_inst = sc[2];
 
@@ -2666,8 +2680,8 @@ extern "C" int dbg_build(dbg_t *h, int k, uint64_t table_capacity_hint) {
         HIPCHK(h, hipMemcpyAsync(sc, h->d_scalars, 32, hipMemcpyDeviceToHost, h->stream));
         h->stats.ms_count = t.stop();
     }
-    if (sc[0] & 1) { h->err = "reads hold a byte outside ACGT"; free_build(h); return DBG_E_ALPHABET; }
-    if (sc[0] & 2) { h->err = "hash table capacity exceeded"; free_build(h); return DBG_E_CAPACITY; }
+    if (sc[0] & STATUS_BAD_BASE) { h->err = "reads hold a byte outside ACGT"; free_build(h); return DBG_E_ALPHABET; }
+    if (sc[0] & STATUS_TABLE_FULL) { h->err = "hash table capacity exceeded"; free_build(h); return DBG_E_CAPACITY; }
     h->n_kmer_inst = sc[1];
     h->n_edge_inst = sc[2];
 
@@ -2724,7 +2738,7 @@ extern "C" int dbg_refine_edge_order(dbg_t *h) {
     if (h->sk_src.valid && !h->d_keys_hi && h->sk_n_ranges && !h->refine_streaming) {  // partitioned build: per range, from the bucket's own records
         unsigned long long *flag = (unsigned long long *)(h->d_scalars + 48);
         HIPCHK(h, hipMemsetAsync(flag, 0, 8, h->stream));
-        const SkRange *ranges = (const SkRange *)h->ar_misc[6].p;
+        const SkRange *ranges = (const SkRange *)h->ar_misc[MISC_RANGES].p;
         if (h->sk_src.st_bytes == 4)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sk_refine<uint32_t>), dim3((unsigned)h->sk_n_ranges), dim3(256), 0, h->stream, ranges,
                                h->sk_src.b_start, h->sk_src.b_cnt, h->sk_src.w0, h->sk_src.w1, (const uint32_t *)h->sk_src.st,
@@ -3092,7 +3106,7 @@ extern "C" int dbg_mark_pull_reads(dbg_t *h) {
         if (h->D != GEN_D && h->sk_src.valid && h->sk_n_ranges && !h->refine_streaming) {  // partitioned build: per range
             unsigned long long *flag = (unsigned long long *)(h->d_scalars + 48);
             HIPCHK(h, hipMemsetAsync(flag, 0, 8, h->stream));
-            const SkRange *ranges = (const SkRange *)h->ar_misc[6].p;
+            const SkRange *ranges = (const SkRange *)h->ar_misc[MISC_RANGES].p;
             if (h->sk_src.st_bytes == 4)
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sk_pull<uint32_t>), dim3((unsigned)h->sk_n_ranges), dim3(256), 0, h->stream,
                                    ranges, h->sk_src.b_start, h->sk_src.b_cnt, h->sk_src.w0, h->sk_src.w1,
@@ -3234,7 +3248,7 @@ static int walk_impl(dbg *h, const G &g, int final_mode, uint64_t max_chars) {
                 uint64_t sc0 = 0;
                 if (hipMemcpyAsync(&sc0, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
                     hipStreamSynchronize(h->stream) != hipSuccess) { h->err = "walk: list ranking failed on the device"; rc = DBG_E_HIP; break; }
-                if (sc0 & 1) { h->err = "internal: a start node is not a splitter"; rc = DBG_E_HIP; break; }
+                if (sc0 & STATUS_BAD_START) { h->err = "internal: a start node is not a splitter"; rc = DBG_E_HIP; break; }
             }
             jump[0] = jump[1] = nullptr;  // arena-owned
         } else {
@@ -3629,8 +3643,9 @@ static int multisplit_level(dbg *h, const uint64_t *p_start, const uint64_t *p_c
 
 // Provisional bucket geometry of a build, before anything was sampled: T bits in all, l1 of them at level 1.
 // target: mean distinct k-mers per final bucket; own: the shards the buckets are spread over.
+// l1_wide_from: the T from which level 1 takes 10 bits instead of 9.
 static void sk_provisional_bits(const dbg *h, uint64_t n_inst, double own, double target, int shard_bits, bool presplit_senders,
-                                int *T_out, int *l1_out) {
+                                int l1_wide_from, int *T_out, int *l1_out) {
     constexpr int T_MAX = 20;  // up to 10 + 10 bits; the estimate may add a third level
     int T = h->bucket_bits;
     if (T == 0) {  // auto: assume 40 % of the instances are distinct
@@ -3640,11 +3655,11 @@ static void sk_provisional_bits(const dbg *h, uint64_t n_inst, double own, doubl
     if (T < shard_bits) T = shard_bits;
     if (presplit_senders) T = std::max(9, T);  // the senders split by 9 bits
     *T_out = T;
-    *l1_out = T < 9 ? T : (T >= DBG_L1_WIDE_FROM && !presplit_senders ? 10 : 9);
+    *l1_out = T < 9 ? T : (T >= l1_wide_from && !presplit_senders ? 10 : 9);
 }
 
 // Mean distinct k-mers per final bucket of a build with CAP-slot LDS tables (table ~1/3 full: measured optimum).  One
-// constant for sk_extract's guess of the level-1 width and for sk_count_from_segments, which chooses it.
+// constant for sk_extract's guess of the level-1 width and for sk_partition, which chooses it.
 template <int CAP> constexpr double SK_TARGET_DISTINCT = CAP * 0.36;
 
 // What a pre-split extraction (option "extract_presplit") leaves for level 1 of the multisplit: n_wg * 2^f0 sub-segments,
@@ -3697,10 +3712,10 @@ static int sk_extract(dbg *h, int k, uint64_t *w0[2], uint64_t *w1[2], ST *st[2]
         tiles_per_wg = (tiles + n_wg - 1) / n_wg;
         seg_cap = std::min<uint64_t>(MS_SC, (uint64_t)((double)tiles_per_wg * per_tile) + 64);
         n_seg = (uint64_t)n_wg * F0;
-        // level 1's width as sk_count_from_segments will choose it, from the k-mer instances the reads can hold at most
+        // level 1's width as sk_partition will choose it, from the k-mer instances the reads can hold at most
         const uint64_t cut = h->n_reads * (uint64_t)(k - 1);
         int T_guess = 0;
-        sk_provisional_bits(h, h->n_bytes > cut ? h->n_bytes - cut : 0, 1.0, xs->target, 0, false, &T_guess, &ps_l1);
+        sk_provisional_bits(h, h->n_bytes > cut ? h->n_bytes - cut : 0, 1.0, xs->target, 0, false, DBG_L1_WIDE_FROM, &T_guess, &ps_l1);
         if (ps_l1 < f0) ps_l1 = 0;  // fewer level-1 bits than the split took: no count matrix (level 1 runs as one group)
     }
     std::vector<uint64_t> hseg;
@@ -3710,12 +3725,12 @@ static int sk_extract(dbg *h, int k, uint64_t *w0[2], uint64_t *w1[2], ST *st[2]
     Timer t(h->stream);
     for (int attempt = 0; attempt < 3; ++attempt) {
         // segment table: start and count per (sub-)segment, k-mer and edge instances per workgroup
-        CHK(buf_ensure(h, h->ar_misc[0], (n_seg * 2 + (uint64_t)n_wg * 2) * 8));
-        seg_start = (uint64_t *)h->ar_misc[0].p; seg_cnt = seg_start + n_seg; seg_nk = seg_cnt + n_seg; seg_ne = seg_nk + n_wg;
+        CHK(buf_ensure(h, h->ar_misc[MISC_SEGMENTS], (n_seg * 2 + (uint64_t)n_wg * 2) * 8));
+        seg_start = (uint64_t *)h->ar_misc[MISC_SEGMENTS].p; seg_cnt = seg_start + n_seg; seg_nk = seg_cnt + n_seg; seg_ne = seg_nk + n_wg;
         hseg.assign((size_t)(n_seg * 2 + (uint64_t)n_wg * 2), 0);
         if (f0 && ps_l1) {
-            CHK(buf_ensure(h, h->ar_misc[3], n_seg * 4 << (ps_l1 - f0)));
-            ps_cmat = (uint32_t *)h->ar_misc[3].p;
+            CHK(buf_ensure(h, h->ar_misc[MISC_MS_CMAT], n_seg * 4 << (ps_l1 - f0)));
+            ps_cmat = (uint32_t *)h->ar_misc[MISC_MS_CMAT].p;
         }
         const uint64_t rec_cap = seg_cap * n_seg;
         for (int set = 0; set < 2; ++set) {
@@ -3761,8 +3776,8 @@ static int sk_extract(dbg *h, int k, uint64_t *w0[2], uint64_t *w1[2], ST *st[2]
         HIPCHK(h, hipMemcpyAsync(hseg.data() + n_seg, seg_cnt, (size_t)(n_seg + (uint64_t)n_wg * 2) * 8, hipMemcpyDeviceToHost,
                                  h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (sc[0] & 1) { h->err = "reads hold a byte outside ACGT"; return DBG_E_ALPHABET; }
-        if (!(sc[0] & 4)) break;
+        if (sc[0] & STATUS_BAD_BASE) { h->err = "reads hold a byte outside ACGT"; return DBG_E_ALPHABET; }
+        if (!(sc[0] & STATUS_SEGMENT_FULL)) break;
         if (f0) {  // a sub-segment overflowed: today's one segment per workgroup, at its usual size
             f0 = 0; ps_l1 = 0; ps_cmat = nullptr;
             ++h->presplit_fallbacks;
@@ -3802,39 +3817,56 @@ struct Presplit {
     const void *in_st = nullptr;          // device: stamps of the received records (STI: rank-local 32-bit in a sharded build)
 };
 
-// ---- stages 2..: records given as segments of (in_w0, in_w1, in_st) -> node arrays + successors.
-// The ping-pong sets w0/w1/st (arena) must hold n_rec records; n_inst bounds the distinct k-mers.
-// shard_bits > 0: only buckets whose top shard_bits equal my_shard hold records (the caller made
-// sure); successors owned by other shards are left as remote queries in ar_shard[0..1].
-template <class ST, int CAP, class STI = ST>
-static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, const uint64_t *seg_cnt, uint32_t n_seg,
-                                  uint64_t n_rec, uint64_t n_inst, uint64_t n_edge_inst, const uint64_t *in_w0,
-                                  const uint64_t *in_w1, const ST *in_st, uint64_t *w0[2], uint64_t *w1[2], ST *st[2],
-                                  uint64_t node_capacity_hint, int shard_bits, int my_shard,
-                                  const Presplit *pre = nullptr, const ExtractSplit *xs = nullptr) {
-    // pre: n_inst / n_edge_inst come in as upper bounds (the senders did not count per owner) and are replaced by the
-    // exact sums of the level-2 histogram pass before anything is sized from them
-    // xs: the segments are the sub-segments of a pre-split extraction (sk_extract)
-    const int m = sk_m_for_k(k);
-    unsigned long long *sc_dev = (unsigned long long *)h->d_scalars;
-    uint64_t sc[8] = {0};
-    // ---- bucket geometry.  Level 1 takes up to 9 bits of the bucket hash; the remaining bits are
-    //      chosen after level 1 from a distinct-k-mer estimate on one level-1 bucket (auto mode).
-    constexpr double TARGET_DISTINCT = SK_TARGET_DISTINCT<CAP>;
+// What differs between the one-word (k <= 31) and the two-word (32 <= k <= 63) LDS engine in sk_partition: plain values and
+// the launch of the engine's estimate kernel.
+template <class Est>
+struct SkPartitionParams {
+    double target;           // mean distinct k-mers per final bucket the auto geometry aims at
+    int l1_wide_from;        // total bucket bits from which level 1 takes 10 bits instead of 9
+    bool probe_first_owned;  // the estimate outside `pre` samples the first level-1 bucket this shard owns (false: bucket 0)
+    bool sum_instances;      // pre: level 2's histogram pass sums the k-mer and edge instances and the stage reads them back
+                             // (false: the caller counts them later, from the meta words)
+    Est estimate;            // (grid, seg_start, seg_cnt, segment, w0, w1, set, set_mask, out): launches the estimate kernel
+};
+
+// What sk_partition leaves: the final buckets, where their records are, and the geometry that maps a bucket hash to a bucket.
+struct SkPartition {
+    uint64_t *b_start = nullptr, *b_cnt = nullptr;  // device, n_buckets entries each
+    uint64_t n_buckets = 0;
+    int where = 0;                                  // the record set (w0/w1/st index) that holds the partitioned records
+    int l1 = 0, nb2 = 1, fb2 = 0, l2_pow = 0, nb3 = 1, fb3 = 0;  // as in SkGeom
+    double est_distinct = 0.0;                      // distinct k-mers of this shard, from the level-1 sample (0 = unknown)
+    uint64_t n_inst = 0, n_edge_inst = 0;           // the caller's bounds, or the exact sums (sum_instances)
+};
+
+// ---- the partition stage of both LDS engines: records given as segments of (in_w0, in_w1, in_st) -> final buckets in one
+// of the ping-pong sets w0/w1/st (arena), which must hold n_rec records.  n_inst bounds the distinct k-mers.
+// shard_bits > 0: only buckets whose top shard_bits equal my_shard hold records (the caller made sure).
+// host_cnt: the segment counts on the host, when the segments are the ones the extraction just wrote (else nullptr)
+// pre: the records were received split by level 1 (the stage starts at level 2); n_inst / n_edge_inst are upper bounds then
+// xs: the segments are the sub-segments of a pre-split extraction (sk_extract)
+template <class ST, class STI, int STHI, class Est>
+static int sk_partition(dbg *h, const SkPartitionParams<Est> &pp, const uint64_t *seg_start, const uint64_t *seg_cnt,
+                        uint32_t n_seg, const uint64_t *host_cnt, const Presplit *pre, const ExtractSplit *xs, const uint64_t *in_w0,
+                        const uint64_t *in_w1, const ST *in_st, uint64_t *w0[2], uint64_t *w1[2], ST *st[2], int shard_bits,
+                        int my_shard, uint64_t n_rec, uint64_t n_inst, uint64_t n_edge_inst, SkPartition *out) {
+    // ---- bucket geometry.  Level 1 takes up to 9 bits of the bucket hash (10 from pp.l1_wide_from bits on); the remaining
+    //      bits are chosen after level 1 from a distinct-k-mer estimate on one level-1 bucket (auto mode).
     const double own = shard_bits ? (double)(1 << shard_bits) : 1.0;  // buckets are spread over `own` shards
     const bool auto_T = (h->bucket_bits == 0);
     // level 1 is fixed before the estimate refines the rest; forced geometries take plain bit fields: up to 10 bits at
     // level 2, what is left (the bucket hash has 22 bits) at level 3
     int T = 0, l1 = 0;
-    sk_provisional_bits(h, n_inst, own, TARGET_DISTINCT, shard_bits, pre != nullptr, &T, &l1);
+    sk_provisional_bits(h, n_inst, own, pp.target, shard_bits, pre != nullptr, pp.l1_wide_from, &T, &l1);
     int l2 = std::min(10, T - l1);
     int nb2 = 0;                                            // children of the second level (0: not decided yet)
     int nb3 = (T - l1 - l2) > 0 ? 1 << (T - l1 - l2) : 1;   // children of the third level
     const int nb1 = 1 << l1;
-    CHK(buf_ensure(h, h->ar_misc[1], (uint64_t)nb1 * 16));
-    uint64_t *c1_start = (uint64_t *)h->ar_misc[1].p, *c1_cnt = c1_start + nb1;
+    CHK(buf_ensure(h, h->ar_misc[MISC_L1_CHILDREN], (uint64_t)nb1 * 16));
+    uint64_t *c1_start = (uint64_t *)h->ar_misc[MISC_L1_CHILDREN].p, *c1_cnt = c1_start + nb1;
+    dbg::Buf &ms_scpre = h->ar_misc[MISC_MS_SCPRE], &ms_cmat = h->ar_misc[MISC_MS_CMAT], &ms_offs = h->ar_misc[MISC_MS_OFFS];
     int where = 0;
-    double est_distinct = 0.0;  // distinct k-mers of this shard, from the level-1 sample (0 = unknown)
+    double est_distinct = 0.0;
     const int top = 6 + SK_BUCKET_BITS;
     Timer t_part(h->stream);
     // presplit: the level-2 input segments, bucket-major: segment (bucket b, sender r) = index (b - b_lo) * n_senders + r
@@ -3844,7 +3876,8 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
     uint32_t ps_n = 0;
     if (pre) {
         ps_n = (uint32_t)(bps * pre->n_senders);
-        std::vector<uint64_t> hs((size_t)ps_n * 3);
+        std::vector<uint64_t> &hs = h->host_scpre;  // lives in the handle: no allocation per build
+        hs.assign((size_t)ps_n * 3, 0);
         for (int r = 0; r < pre->n_senders; ++r) {
             uint64_t at = pre->recv_off[r];
             for (int b = 0; b < bps; ++b) {
@@ -3855,47 +3888,42 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
                 at += pre->counts[(size_t)r * bps + b];
             }
         }
-        CHK(buf_ensure(h, h->ar_misc[0], (uint64_t)ps_n * 3 * 8));
-        ps_start = (uint64_t *)h->ar_misc[0].p; ps_cnt = ps_start + ps_n; ps_add = ps_cnt + ps_n;
+        CHK(buf_ensure(h, h->ar_misc[MISC_SEGMENTS], (uint64_t)ps_n * 3 * 8));
+        ps_start = (uint64_t *)h->ar_misc[MISC_SEGMENTS].p; ps_cnt = ps_start + ps_n; ps_add = ps_cnt + ps_n;
         HIPCHK(h, hipMemcpyAsync(ps_start, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));  // hs goes out of scope
+        // the upload must have left the staging vector: the next multisplit_level refills h->host_scpre with its prefix
+        HIPCHK(h, hipStreamSynchronize(h->stream));
     } else {
-        const uint64_t *host_cnt = (h->host_seg_cnt.size() == n_seg && seg_cnt == (const uint64_t *)h->ar_misc[0].p + n_seg)
-                                       ? h->host_seg_cnt.data() : nullptr;  // the segments sk_extract just wrote
         if (xs && xs->f0 && l1 >= xs->f0) {
             // pre-split extraction: 2^f0 groups of n_wg sub-segments, each group split by the l1 - f0 low bits of the level-1
             // digit -- child (group g, digit b) = g * (nb1 >> f0) + b is the level-1 bucket of the one-group split
             if (xs->l1 != l1) ++h->presplit_rehists;
             CHK((multisplit_level<ST, true>(h, seg_start, seg_cnt, n_seg, xs->n_wg, n_rec, in_w0, in_w1, in_st, w0[1], w1[1], st[1],
-                                            top - l1, nb1 >> xs->f0, c1_start, c1_cnt, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], 0,
-                                            nullptr, nullptr, host_cnt, xs->l1 == l1 ? xs->cmat : nullptr)));
+                                            top - l1, nb1 >> xs->f0, c1_start, c1_cnt, ms_scpre, ms_cmat, ms_offs, 0, nullptr, nullptr,
+                                            host_cnt, xs->l1 == l1 ? xs->cmat : nullptr)));
         } else {
             CHK((multisplit_level<ST, true>(h, seg_start, seg_cnt, n_seg, n_seg, n_rec, in_w0, in_w1, in_st, w0[1], w1[1], st[1],
-                                            top - l1, nb1, c1_start, c1_cnt, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], 0, nullptr,
-                                            nullptr, host_cnt)));
+                                            top - l1, nb1, c1_start, c1_cnt, ms_scpre, ms_cmat, ms_offs, 0, nullptr, nullptr, host_cnt)));
         }
         where = 1;
     }
-    if (auto_T && l1 >= 9 && n_rec) {  // refine T from a sample: the first level-1 bucket this shard owns
-        const uint32_t probe_bucket = shard_bits ? (uint32_t)my_shard << (l1 - shard_bits) : 0u;
+    if (auto_T && l1 >= 9 && n_rec) {  // refine T from a sample: one level-1 bucket
+        const uint32_t probe_bucket = (pp.probe_first_owned && shard_bits) ? (uint32_t)my_shard << (l1 - shard_bits) : 0u;
         const uint64_t inst_bucket = (uint64_t)((double)n_inst * own / nb1) * 2 + 1024;
         uint64_t set_cap = 1024;
         while (set_cap < inst_bucket * 2) set_cap <<= 1;
-        CHK(buf_ensure(h, h->ar_misc[8], set_cap * 8));
-        HIPCHK(h, hipMemsetAsync(h->ar_misc[8].p, 0xFF, set_cap * 8, h->stream));
-        HIPCHK(h, hipMemsetAsync(h->d_scalars + 40, 0, 16, h->stream));
+        CHK(buf_ensure(h, h->ar_misc[MISC_ESTIMATE_SET], set_cap * 8));
+        unsigned long long *set = (unsigned long long *)h->ar_misc[MISC_ESTIMATE_SET].p;
+        unsigned long long *d_est = (unsigned long long *)(h->d_scalars + SC_ESTIMATE);
+        HIPCHK(h, hipMemsetAsync(set, 0xFF, set_cap * 8, h->stream));
+        HIPCHK(h, hipMemsetAsync(d_est, 0, 16, h->stream));
         if (pre) {  // the probe bucket's records sit in one segment per sender
-            for (int r = 0; r < pre->n_senders; ++r)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_estimate_distinct<ST>), dim3(128), dim3(256), 0, h->stream, ps_start, ps_cnt,
-                                   (uint32_t)r, in_w0, in_w1, k, (unsigned long long *)h->ar_misc[8].p, set_cap - 1,
-                                   (unsigned long long *)(h->d_scalars + 40));
+            for (int r = 0; r < pre->n_senders; ++r) pp.estimate(128u, ps_start, ps_cnt, (uint32_t)r, in_w0, in_w1, set, set_cap - 1, d_est);
         } else {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_estimate_distinct<ST>), dim3(512), dim3(256), 0, h->stream, c1_start, c1_cnt,
-                               probe_bucket, w0[1], w1[1], k, (unsigned long long *)h->ar_misc[8].p, set_cap - 1,
-                               (unsigned long long *)(h->d_scalars + 40));
+            pp.estimate(512u, c1_start, c1_cnt, probe_bucket, w0[1], w1[1], set, set_cap - 1, d_est);
         }
         uint64_t est[2] = {0, 0};
-        HIPCHK(h, hipMemcpyAsync(est, h->d_scalars + 40, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(est, d_est, 16, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if (est[0]) {
             double distinct = (double)n_inst * own * (double)est[1] / (double)est[0];
@@ -3907,7 +3935,7 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
             est_distinct = distinct / own;
             // the second level takes any number of children up to 1024 (all hash bits below level 1, scaled): the
             // bucket count follows the estimate instead of jumping by powers of two
-            const double want = distinct / ((double)h->target_distinct > 0 ? (double)h->target_distinct : TARGET_DISTINCT);
+            const double want = distinct / ((double)h->target_distinct > 0 ? (double)h->target_distinct : pp.target);
             const double want2 = std::max<double>(1.0, std::ceil(want / nb1));
             if (want2 <= 1024.0) {
                 nb2 = (int)want2;
@@ -3926,12 +3954,10 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
     const int fb2 = (nb3 == 1 && ((nb2 > 0 && (nb2 & (nb2 - 1)) != 0) || (auto_T && l1 >= 9 && nb2 > 1))) ? SK_BUCKET_BITS - l1 : 0;
     const uint64_t n_l2 = l2 > 0 ? (uint64_t)nb1 * (uint64_t)nb2 : (uint64_t)nb1;  // buckets after level 2
     const uint64_t n_buckets = n_l2 * (uint64_t)nb3;
-    T = 0;
-    while ((1ull << T) < n_buckets) ++T;  // only for reporting
     const int l2_pow = (fb2 || l2 == 0) ? 0 : (int)std::lround(std::log2((double)nb2));  // second level as plain bits
     const int fb3 = nb3 > 1 ? SK_BUCKET_BITS - l1 - l2_pow : 0;  // level 3: the hash bits below levels 1 and 2, scaled into [0, nb3)
-    CHK(buf_ensure(h, h->ar_misc[5], n_buckets * 16));
-    uint64_t *b_start = (uint64_t *)h->ar_misc[5].p, *b_cnt = b_start + n_buckets;
+    CHK(buf_ensure(h, h->ar_misc[MISC_BUCKETS], n_buckets * 16));
+    uint64_t *b_start = (uint64_t *)h->ar_misc[MISC_BUCKETS].p, *b_cnt = b_start + n_buckets;
     uint64_t *l2_start = b_start, *l2_cnt = b_cnt;  // children of level 2: the final buckets unless a third level follows
     if (nb3 > 1) {
         CHK(buf_ensure(h, h->ar_l2, n_l2 * 16));
@@ -3942,23 +3968,27 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
         const int sh2 = fb2 ? top - SK_BUCKET_BITS : top - l1 - l2_pow;
         if (pre) {
             // only the level-1 buckets this shard owns have records: their children sit at [b_lo * nb2, ...)
+            unsigned long long *d_sums = (unsigned long long *)(h->d_scalars + SC_L2_SUMS);
             HIPCHK(h, hipMemsetAsync(b_start, 0, n_buckets * 16, h->stream));
             if (nb3 > 1) HIPCHK(h, hipMemsetAsync(l2_start, 0, n_l2 * 16, h->stream));
-            HIPCHK(h, hipMemsetAsync(h->d_scalars + 56, 0, 16, h->stream));
-            CHK((multisplit_level<ST, true, STI>(h, ps_start, ps_cnt, ps_n, (uint32_t)pre->n_senders, n_rec, in_w0, in_w1,
-                                                      (const STI *)pre->in_st, w0[0], w1[0], st[0], sh2, nb2, l2_start + b_lo * nb2,
-                                                      l2_cnt + b_lo * nb2, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], fb2,
-                                                      ps_add, (unsigned long long *)(h->d_scalars + 56))));
-            uint64_t sums[2] = {0, 0};
-            HIPCHK(h, hipMemcpyAsync(sums, h->d_scalars + 56, 16, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(h, hipStreamSynchronize(h->stream));
-            n_inst = sums[0];
-            n_edge_inst = sums[1];
-            h->n_kmer_inst = n_inst;
-            h->n_edge_inst = n_edge_inst;
+            HIPCHK(h, hipMemsetAsync(d_sums, 0, 16, h->stream));
+            // this level adds the sender's stamp base (ps_add); STHI: 4-byte wire stamps whose high bits travel in the meta words
+            CHK((multisplit_level<ST, true, STI, STHI>(h, ps_start, ps_cnt, ps_n, (uint32_t)pre->n_senders, n_rec, in_w0, in_w1,
+                                                       (const STI *)pre->in_st, w0[0], w1[0], st[0], sh2, nb2, l2_start + b_lo * nb2,
+                                                       l2_cnt + b_lo * nb2, ms_scpre, ms_cmat, ms_offs, fb2, ps_add,
+                                                       pp.sum_instances ? d_sums : (unsigned long long *)nullptr)));
+            if (pp.sum_instances) {
+                uint64_t sums[2] = {0, 0};
+                HIPCHK(h, hipMemcpyAsync(sums, d_sums, 16, hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                n_inst = sums[0];
+                n_edge_inst = sums[1];
+                h->n_kmer_inst = n_inst;
+                h->n_edge_inst = n_edge_inst;
+            }
         } else {
             CHK((multisplit_level<ST, true>(h, c1_start, c1_cnt, (uint32_t)nb1, 1, n_rec, w0[1], w1[1], st[1], w0[0], w1[0],
-                                            st[0], sh2, nb2, l2_start, l2_cnt, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], fb2)));
+                                            st[0], sh2, nb2, l2_start, l2_cnt, ms_scpre, ms_cmat, ms_offs, fb2)));
         }
         where = 0;
         if (nb3 > 1) {  // third level: every level-2 child (of the groups this build owns) is split once more
@@ -3971,7 +4001,7 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
             const uint64_t p_lo = pre ? b_lo * nb2 : 0, p_n = pre ? (uint64_t)bps * nb2 : n_l2;
             CHK((multisplit_level<ST, true>(h, l2_start + p_lo, l2_cnt + p_lo, (uint32_t)p_n, 1, n_rec, w0[0], w1[0], st[0], w0[1],
                                             w1[1], st[1], top - SK_BUCKET_BITS, nb3, b_start + p_lo * nb3, b_cnt + p_lo * nb3,
-                                            h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], fb3)));
+                                            ms_scpre, ms_cmat, ms_offs, fb3)));
             where = 1;
         }
     } else {
@@ -3980,6 +4010,39 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
     }
     h->stats.ms_partition = t_part.stop();
     h->stats.n_buckets = n_buckets;
+    *out = SkPartition{b_start, b_cnt, n_buckets, where, l1, l2 > 0 ? nb2 : 1, fb2, l2_pow, nb3, fb3, est_distinct, n_inst, n_edge_inst};
+    return DBG_OK;
+}
+
+// ---- stages 2..: records given as segments of (in_w0, in_w1, in_st) -> node arrays + successors.
+// The ping-pong sets w0/w1/st (arena) must hold n_rec records; n_inst bounds the distinct k-mers.
+// shard_bits > 0: only buckets whose top shard_bits equal my_shard hold records (the caller made
+// sure); successors owned by other shards are left as remote queries in ar_shard[0..1].
+// host_cnt, pre, xs: see sk_partition
+template <class ST, int CAP, class STI = ST>
+static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, const uint64_t *seg_cnt, uint32_t n_seg,
+                                  const uint64_t *host_cnt, uint64_t n_rec, uint64_t n_inst, uint64_t n_edge_inst,
+                                  const uint64_t *in_w0, const uint64_t *in_w1, const ST *in_st, uint64_t *w0[2], uint64_t *w1[2],
+                                  ST *st[2], uint64_t node_capacity_hint, int shard_bits, int my_shard,
+                                  const Presplit *pre = nullptr, const ExtractSplit *xs = nullptr) {
+    const int m = sk_m_for_k(k);
+    unsigned long long *sc_dev = (unsigned long long *)h->d_scalars;
+    uint64_t sc[8] = {0};
+    auto estimate = [h, k](unsigned grid, const uint64_t *s_start, const uint64_t *s_cnt, uint32_t seg, const uint64_t *rw0,
+                           const uint64_t *rw1, unsigned long long *set, uint64_t set_mask, unsigned long long *d_est) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_estimate_distinct<ST>), dim3(grid), dim3(256), 0, h->stream, s_start, s_cnt, seg, rw0,
+                           rw1, k, set, set_mask, d_est);
+    };
+    const SkPartitionParams<decltype(estimate)> pp{SK_TARGET_DISTINCT<CAP>, DBG_L1_WIDE_FROM, true, true, estimate};
+    SkPartition P;
+    CHK((sk_partition<ST, STI, 0>(h, pp, seg_start, seg_cnt, n_seg, host_cnt, pre, xs, in_w0, in_w1, in_st, w0, w1, st, shard_bits,
+                                  my_shard, n_rec, n_inst, n_edge_inst, &P)));
+    n_inst = P.n_inst;  // pre: the bounds that came in are replaced by the exact sums before anything is sized from them
+    n_edge_inst = P.n_edge_inst;
+    uint64_t *const b_start = P.b_start, *const b_cnt = P.b_cnt;
+    const uint64_t n_buckets = P.n_buckets;
+    const int where = P.where;
+    const double est_distinct = P.est_distinct;
 
     // ---- K5: per-bucket counting.  Node and edge arrays are sized from the distinct-k-mer estimate (58 B per node:
     //      the worst case "every instance distinct" would not fit the HBM beyond ~3e9 instances); if the estimate
@@ -4017,8 +4080,8 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
     uint64_t *qk[2], *qm[2];
     uint32_t *qc[2];
     const uint64_t range_cap = n_buckets + 4096 + n_inst / (CAP / 4);
-    CHK(buf_ensure(h, h->ar_misc[6], range_cap * sizeof(SkRange)));
-    SkRange *ranges = (SkRange *)h->ar_misc[6].p;
+    CHK(buf_ensure(h, h->ar_misc[MISC_RANGES], range_cap * sizeof(SkRange)));
+    SkRange *ranges = (SkRange *)h->ar_misc[MISC_RANGES].p;
     // buckets this build owns (a shard or a pass owns 1 / 2^shard_bits of the level-1 groups): only they get a directory
     const uint64_t own_cnt = n_buckets >> shard_bits, own_lo = (uint64_t)my_shard * own_cnt;
     CHK(buf_ensure(h, h->ar_dir, (own_cnt + (range_cap - n_buckets)) * (CAP / 64) * sizeof(SkDirEnt)));
@@ -4062,8 +4125,8 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
             (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device);
             const unsigned grid = (unsigned)std::min<uint64_t>(n_buckets, (uint64_t)n_cu);  // persistent, one workgroup per CU
             SkCount2Args a2{out, b_start, b_cnt, w0[where], w1[where], (const void *)st[where], n_buckets, split_recs, k};
-            SkCount2Args *d_a2 = (SkCount2Args *)(h->d_scalars + 64);
-            static_assert(sizeof(SkCount2Args) <= (SK2_QUERY_CURSOR - 64) * 8, "the query cursor sits behind the descriptor");
+            SkCount2Args *d_a2 = (SkCount2Args *)(h->d_scalars + SC_DESCRIPTOR);
+            static_assert(sizeof(SkCount2Args) <= (SK2_QUERY_CURSOR - SC_DESCRIPTOR) * 8, "the query cursor sits behind the descriptor");
             HIPCHK(h, hipMemcpyAsync(d_a2, &a2, sizeof(a2), hipMemcpyHostToDevice, h->stream));
             HIPCHK(h, hipMemsetAsync(h->d_scalars + SK2_QUERY_CURSOR, 0, 8, h->stream));
             hipLaunchKernelGGL(kern2, dim3(grid), dim3(Cnt2Cfg<ST>::NT), lds2, h->stream, (const SkCount2Args *)d_a2);
@@ -4080,7 +4143,7 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
             const unsigned grid = (unsigned)std::min<uint64_t>(n_buckets, (uint64_t)n_cu * per_cu);  // persistent
             // descriptor in device memory (see fresh_args): words 64.. of the scalar block are reserved for it
             static_assert(sizeof(SkCountOut) <= 64 * 8, "descriptor slot");
-            SkCountOut *d_out = (SkCountOut *)(h->d_scalars + 64);
+            SkCountOut *d_out = (SkCountOut *)(h->d_scalars + SC_DESCRIPTOR);
             HIPCHK(h, hipMemcpyAsync(d_out, &out, sizeof(out), hipMemcpyHostToDevice, h->stream));
             hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, h->stream, b_start, b_cnt, w0[where], w1[where],
                                st[where], k, m, n_buckets, (const SkCountOut *)d_out, split_recs, h->phase_limit);
@@ -4095,26 +4158,26 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
         if (h->phase_limit) { h->err = "ablation run (phase_limit set): timing only"; return DBG_E_ARG; }
         // buckets that had to be split by hash sub-range turn in-bucket successors into queries:
         // the usual bound (one query per record) no longer holds, retry with the safe one
-        if (sc[0] & (8 | 32)) break;  // not a sizing problem
+        if (sc[0] & (STATUS_BUCKET_TOO_BIG | STATUS_RANGE_CAP)) break;  // not a sizing problem
         bool again = false;
-        if (use_count2 && (sc[0] & (512 | 2048))) {
+        if (use_count2 && (sc[0] & (STATUS_COUNTER16 | STATUS_INCONSISTENT))) {
             // (a wrapped 16-bit counter reads 0 twice: k_sk_count3 then reports the overflow AND a mismatch of its two counts)
-            if ((sc[0] & 2048) && !(sc[0] & 512)) { h->err = "internal: k_sk_count2 / k_sk_count3 counted a bucket's nodes, edges or queries inconsistently"; return DBG_E_HIP; }
+            if ((sc[0] & STATUS_INCONSISTENT) && !(sc[0] & STATUS_COUNTER16)) { h->err = "internal: k_sk_count2 / k_sk_count3 counted a bucket's nodes, edges or queries inconsistently"; return DBG_E_HIP; }
             use_count2 = false;  // an edge seen more than 65 535 times: the kernel with 32-bit counters
             ++extra_attempts;
             again = true;
         }
-        if ((sc[0] & 16) && (node_cap < node_cap_max || edge_cap < edge_cap_max) && !node_capacity_hint) {
+        if ((sc[0] & STATUS_NODE_EDGE_CAP) && (node_cap < node_cap_max || edge_cap < edge_cap_max) && !node_capacity_hint) {
             node_cap = node_cap_max;  // the estimate was low
             edge_cap = edge_cap_max;
             again = true;
         }
-        if ((sc[0] & 64) && q_cap < n_edge_inst + 1024) { q_cap = n_edge_inst + 1024; again = true; }
+        if ((sc[0] & STATUS_QUERY_CAP) && q_cap < n_edge_inst + 1024) { q_cap = n_edge_inst + 1024; again = true; }
         if (!again || attempt == 2 + extra_attempts) break;
     }
-    if (sc[0] & 8) { h->err = "a bucket could not be split to fit the LDS table"; return DBG_E_CAPACITY; }
-    if (sc[0] & 16) { h->err = "node/edge capacity exceeded"; return DBG_E_CAPACITY; }
-    if (sc[0] & (32 | 64)) { h->err = "range/query list overflow"; return DBG_E_CAPACITY; }
+    if (sc[0] & STATUS_BUCKET_TOO_BIG) { h->err = "a bucket could not be split to fit the LDS table"; return DBG_E_CAPACITY; }
+    if (sc[0] & STATUS_NODE_EDGE_CAP) { h->err = "node/edge capacity exceeded"; return DBG_E_CAPACITY; }
+    if (sc[0] & (STATUS_RANGE_CAP | STATUS_QUERY_CAP)) { h->err = "range/query list overflow"; return DBG_E_CAPACITY; }
     h->n_nodes = sc[4] & 0xFFFFFFFFull;
     h->n_edges = sc[4] >> 32;
     {
@@ -4126,7 +4189,7 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
     uint64_t n_q = sc[5];
     const uint64_t n_ranges = n_buckets + sc[6];
     h->stats.n_queries = n_q;
-    SkGeom geom{k, m, l1, l2 > 0 ? nb2 : 1, fb2, l2_pow, nb3, fb3, shard_bits, my_shard, own_lo, own_cnt};
+    SkGeom geom{k, m, P.l1, P.nb2, P.fb2, P.l2_pow, P.nb3, P.fb3, shard_bits, my_shard, own_lo, own_cnt};
 
     // ---- K6: successors that live in another bucket.  Of this shard: the asker looks them up through the target
     //      range's directory (k_succ_resolve).  Of another shard: grouped by owner and parked for the exchange.
@@ -4137,14 +4200,14 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
         if (shard_bits && n_q) {  // group by owner shard = top shard_bits of the bucket hash
             hipLaunchKernelGGL(k_q_bucket, dim3(grid_for(n_q, 256)), dim3(256), 0, h->stream, qk[0], qm[0], n_q, k, m);
             HIPCHK(h, hipGetLastError());
-            CHK(buf_ensure(h, h->ar_misc[7], 512 * 16 + 16));
-            uint64_t *q_seg = (uint64_t *)h->ar_misc[7].p;  // [0..1]: one input segment; [2..]: per-owner children
+            CHK(buf_ensure(h, h->ar_misc[MISC_QUERY_SEGS], 512 * 16 + 16));
+            uint64_t *q_seg = (uint64_t *)h->ar_misc[MISC_QUERY_SEGS].p;  // [0..1]: one input segment; [2..]: per-owner children
             const int nsh = 1 << shard_bits;
             HIPCHK(h, hipMemcpyAsync(q_seg, root, 16, hipMemcpyHostToDevice, h->stream));
             uint64_t *o_start = q_seg + 2, *o_cnt = o_start + nsh;
             CHK((multisplit_level<uint32_t, true>(h, q_seg, q_seg + 1, 1, 1, n_q, qk[0], qm[0], qc[0], qk[1], qm[1], qc[1],
-                                                  40 + SK_BUCKET_BITS - shard_bits, nsh, o_start, o_cnt, h->ar_misc[2],
-                                                  h->ar_misc[3], h->ar_misc[4])));
+                                                  40 + SK_BUCKET_BITS - shard_bits, nsh, o_start, o_cnt, h->ar_misc[MISC_MS_SCPRE],
+                                                  h->ar_misc[MISC_MS_CMAT], h->ar_misc[MISC_MS_OFFS])));
             ShardState &sh = shard_of(h);
             sh.q_start.assign(nsh, 0);
             sh.q_cnt.assign(nsh, 0);
@@ -4172,13 +4235,13 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
             // written, a histogram pass) costs more than the resolver gains: 3.09 vs 2.05 ms at 3.7e7 queries.
             hipLaunchKernelGGL(k_q_bucket, dim3(grid_for(n_q, 256)), dim3(256), 0, h->stream, qk[0], qm[0], n_q, k, m);
             HIPCHK(h, hipGetLastError());
-            CHK(buf_ensure(h, h->ar_misc[7], 1024 * 16 + 16));
-            uint64_t *q_seg = (uint64_t *)h->ar_misc[7].p;
+            CHK(buf_ensure(h, h->ar_misc[MISC_QUERY_SEGS], 1024 * 16 + 16));
+            uint64_t *q_seg = (uint64_t *)h->ar_misc[MISC_QUERY_SEGS].p;
             HIPCHK(h, hipMemcpyAsync(q_seg, root, 16, hipMemcpyHostToDevice, h->stream));
             uint64_t *o_start = q_seg + 2, *o_cnt = o_start + 512;
             CHK((multisplit_level<uint32_t, true>(h, q_seg, q_seg + 1, 1, 1, n_q, qk[0], qm[0], qc[0], qk[1], qm[1], qc[1],
-                                                  40 + SK_BUCKET_BITS - 9, 512, o_start, o_cnt, h->ar_misc[2], h->ar_misc[3],
-                                                  h->ar_misc[4])));
+                                                  40 + SK_BUCKET_BITS - 9, 512, o_start, o_cnt, h->ar_misc[MISC_MS_SCPRE], h->ar_misc[MISC_MS_CMAT],
+                                                  h->ar_misc[MISC_MS_OFFS])));
             qset = 1;
             q_meta = qm[1];
         }
@@ -4189,12 +4252,14 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
             HIPCHK(h, hipGetLastError());
             HIPCHK(h, hipMemcpyAsync(sc, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
-            if (sc[0] & 128) { h->err = "internal: a successor k-mer was not found in its bucket"; return DBG_E_HIP; }
+            if (sc[0] & STATUS_SUCC_MISSING) { h->err = "internal: a successor k-mer was not found in its bucket"; return DBG_E_HIP; }
         }
         h->stats.ms_succ = t.stop();
     }
     // geometry the answer stage of a sharded build needs again
-    h->sk_T = T; h->sk_l1 = l1; h->sk_l2 = l2_pow; h->sk_nb2 = fb2 ? nb2 : 0; h->sk_n_ranges = n_ranges; h->sk_cap = CAP;
+    int T = 0;
+    while ((1ull << T) < n_buckets) ++T;  // only for reporting
+    h->sk_T = T; h->sk_l1 = P.l1; h->sk_l2 = P.l2_pow; h->sk_nb2 = P.fb2 ? P.nb2 : 0; h->sk_n_ranges = n_ranges; h->sk_cap = CAP;
     h->sk_geom = geom; h->sk_n_buckets = n_buckets;
     if (!shard_bits) {
         h->sk_src.w0 = w0[where]; h->sk_src.w1 = w1[where]; h->sk_src.st = st[where]; h->sk_src.st_bytes = (int)sizeof(ST);
@@ -4204,8 +4269,8 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
     return DBG_OK;
 }
 
-// ---- two-word k-mers on the super-k-mer engine (dbg_wsk.h): extraction -> two or three multisplit levels -> k_wsk_gather
-//      -> k_wsk_count -> k_wsucc_resolve.  The geometry logic is that of sk_count_from_segments.
+// ---- two-word k-mers on the super-k-mer engine (dbg_wsk.h): extraction -> sk_partition (two or three multisplit levels, the
+//      stage the one-word engine runs, with this engine's SkPartitionParams) -> k_wsk_gather -> k_wsk_count -> k_wsucc_resolve.
 
 __global__ __launch_bounds__(256) void k_wsk_iota128(uint64_t n, uint64_t *w0) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -4232,8 +4297,8 @@ static int wsk_extract(dbg *h, int k, uint64_t **pk_out, uint64_t *w0[2], uint64
     const uint64_t tiles = all_tiles * (uint64_t)(part + 1) / (uint64_t)n_parts - tile_first;
     const bool reg_kernel = (w >= 20 && w <= 51) && !h->extract_generic;  // k = 32..63: the register kernel (256 threads, several workgroups per CU)
     const uint32_t n_wg = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(tiles, 1), reg_kernel ? 2048 : 1024);
-    CHK(buf_ensure(h, h->ar_misc[0], (uint64_t)n_wg * 4 * 8));
-    uint64_t *seg_start = (uint64_t *)h->ar_misc[0].p, *seg_cnt = seg_start + n_wg, *seg_nk = seg_cnt + n_wg, *seg_ne = seg_nk + n_wg;
+    CHK(buf_ensure(h, h->ar_misc[MISC_SEGMENTS], (uint64_t)n_wg * 4 * 8));
+    uint64_t *seg_start = (uint64_t *)h->ar_misc[MISC_SEGMENTS].p, *seg_cnt = seg_start + n_wg, *seg_nk = seg_cnt + n_wg, *seg_ne = seg_nk + n_wg;
     std::vector<uint64_t> hseg((size_t)n_wg * 4);
     uint64_t n_rec = 0;
     Timer t(h->stream);
@@ -4278,8 +4343,8 @@ static int wsk_extract(dbg *h, int k, uint64_t **pk_out, uint64_t *w0[2], uint64
         HIPCHK(h, hipMemcpyAsync(sc, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(hseg.data(), seg_start, (size_t)n_wg * 4 * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (sc[0] & 1) { h->err = "reads hold a byte outside ACGT"; return DBG_E_ALPHABET; }
-        if (!(sc[0] & 4)) break;
+        if (sc[0] & STATUS_BAD_BASE) { h->err = "reads hold a byte outside ACGT"; return DBG_E_ALPHABET; }
+        if (!(sc[0] & STATUS_SEGMENT_FULL)) break;
         if (attempt == 1) { h->err = "super-k-mer record buffer overflow"; return DBG_E_CAPACITY; }
         seg_cap = tiles_per_wg * TILE;
     }
@@ -4302,151 +4367,35 @@ static int wsk_extract(dbg *h, int k, uint64_t **pk_out, uint64_t *w0[2], uint64
 // left unresolved (the gathered graph resolves every successor anyway, dbg_import_graph).
 template <class ST, class STI>
 static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_start, const uint64_t *seg_cnt, uint32_t n_seg,
-                     uint64_t n_rec, uint64_t n_inst, uint64_t n_edge_inst, const uint64_t *in_w0, const uint64_t *in_w1,
-                     const ST *in_st, uint64_t *w0[2], uint64_t *w1[2], ST *st[2], int shard_bits, int my_shard,
+                     const uint64_t *host_cnt, uint64_t n_rec, uint64_t n_inst, uint64_t n_edge_inst, const uint64_t *in_w0,
+                     const uint64_t *in_w1, const ST *in_st, uint64_t *w0[2], uint64_t *w1[2], ST *st[2], int shard_bits, int my_shard,
                      const Presplit *pre) {
     const int m = SK_MAX_M, w = k - m + 1;
     unsigned long long *sc_dev = (unsigned long long *)h->d_scalars;
     uint64_t sc[8] = {0};
-    const double own = shard_bits ? (double)(1 << shard_bits) : 1.0;
-    // ---- bucket geometry
     // mean distinct k-mers per final bucket.  Lower than the one-word engine's 0.36 * slots: one minimizer occurrence brings
     // ~320 nodes at k = 63, so bucket sizes vary like a Poisson count of a handful of loci, and a bucket that outgrows the
     // table is counted in hash sub-ranges (measured, 10 M x 150 bp: k = 63 30.2 / 30.5 / 31.0 / 32.9 / 35.5 ms of count
     // kernel at 1100 / 900 / 1000 / 1475 / 1700; k = 47 and k = 32 best at 1000 as well)
     constexpr double TARGET_DISTINCT = 1000.0;
-    int T = h->bucket_bits;
-    const bool auto_T = (T == 0);
-    if (auto_T) {
-        const double want = (double)n_inst * own * 0.4 / TARGET_DISTINCT;
-        while (T < 20 && (double)(1ull << T) < want) ++T;
-    }
-    if (T < shard_bits) T = shard_bits;
-    if (pre) T = std::max(9, T);
     // 10 bits at level 1 from 2^18 buckets on (single GPU): a third level over half a million tiny segments costs more
     // than it splits; the senders of a sharded build split by 9 bits, there the third level takes what is left
-    int l1 = pre ? 9 : (T < 9 ? T : (T >= 18 ? 10 : 9)), l2 = std::min(10, T - l1);
-    int nb2 = 0, nb3 = (T - l1 - l2) > 0 ? 1 << (T - l1 - l2) : 1;
-    const int nb1 = 1 << l1;
-    CHK(buf_ensure(h, h->ar_misc[1], (uint64_t)nb1 * 16));
-    uint64_t *c1_start = (uint64_t *)h->ar_misc[1].p, *c1_cnt = c1_start + nb1;
-    int where = 1;
-    double est_distinct = 0.0;
-    const int top = 6 + SK_BUCKET_BITS;
-    Timer t_part(h->stream);
-    const int bps = pre ? nb1 >> shard_bits : 0;
-    const uint64_t b_lo = pre ? (uint64_t)my_shard * bps : 0;
-    uint64_t *ps_start = nullptr, *ps_cnt = nullptr, *ps_add = nullptr;
-    uint32_t ps_n = 0;
-    if (pre) {
-        ps_n = (uint32_t)(bps * pre->n_senders);
-        std::vector<uint64_t> &hs = h->host_scpre;  // lives in the handle: the upload is asynchronous
-        hs.assign((size_t)ps_n * 3, 0);
-        for (int r = 0; r < pre->n_senders; ++r) {
-            uint64_t at = pre->recv_off[r];
-            for (int b = 0; b < bps; ++b) {
-                const size_t i = (size_t)b * pre->n_senders + r;
-                hs[i] = at;
-                hs[ps_n + i] = pre->counts[(size_t)r * bps + b];
-                hs[2 * (size_t)ps_n + i] = pre->stamp_add[r];
-                at += pre->counts[(size_t)r * bps + b];
-            }
-        }
-        CHK(buf_ensure(h, h->ar_misc[0], (uint64_t)ps_n * 3 * 8));
-        ps_start = (uint64_t *)h->ar_misc[0].p; ps_cnt = ps_start + ps_n; ps_add = ps_cnt + ps_n;
-        HIPCHK(h, hipMemcpyAsync(ps_start, hs.data(), hs.size() * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    } else {
-        CHK((multisplit_level<ST, true>(h, seg_start, seg_cnt, n_seg, n_seg, n_rec, in_w0, in_w1, in_st, w0[1], w1[1], st[1], top - l1,
-                                        nb1, c1_start, c1_cnt, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], 0, nullptr, nullptr,
-                                        h->host_seg_cnt.size() == n_seg ? h->host_seg_cnt.data() : nullptr)));
-    }
-    if (auto_T && l1 >= 9 && n_rec) {
-        const uint64_t inst_bucket = (uint64_t)((double)n_inst * own / nb1) * 2 + 1024;
-        uint64_t set_cap = 1024;
-        while (set_cap < inst_bucket * 2) set_cap <<= 1;
-        CHK(buf_ensure(h, h->ar_misc[8], set_cap * 8));
-        HIPCHK(h, hipMemsetAsync(h->ar_misc[8].p, 0xFF, set_cap * 8, h->stream));
-        HIPCHK(h, hipMemsetAsync(h->d_scalars + 40, 0, 16, h->stream));
-        if (pre) {
-            for (int r = 0; r < pre->n_senders; ++r)
-                hipLaunchKernelGGL(k_wsk_estimate, dim3(128), dim3(256), 0, h->stream, ps_start, ps_cnt, (uint32_t)r, in_w0, in_w1, k, pk,
-                                   (unsigned long long *)h->ar_misc[8].p, set_cap - 1, (unsigned long long *)(h->d_scalars + 40));
-        } else {
-            hipLaunchKernelGGL(k_wsk_estimate, dim3(512), dim3(256), 0, h->stream, c1_start, c1_cnt, 0u, w0[1], w1[1], k, pk,
-                               (unsigned long long *)h->ar_misc[8].p, set_cap - 1, (unsigned long long *)(h->d_scalars + 40));
-        }
-        uint64_t est[2] = {0, 0};
-        HIPCHK(h, hipMemcpyAsync(est, h->d_scalars + 40, 16, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (est[0]) {
-            double distinct = (double)n_inst * own * (double)est[1] / (double)est[0];
-            if (pre) {  // scale the sample by records: the instance total is not known yet
-                uint64_t probe_recs = 0;
-                for (int r = 0; r < pre->n_senders; ++r) probe_recs += pre->counts[(size_t)r * bps];
-                distinct = probe_recs ? (double)est[1] * (double)n_rec / (double)probe_recs * own : 0.0;
-            }
-            est_distinct = distinct / own;
-            const double want = distinct / ((double)h->target_distinct > 0 ? (double)h->target_distinct : TARGET_DISTINCT);
-            const double want2 = std::max<double>(1.0, std::ceil(want / nb1));
-            if (want2 <= 1024.0) { nb2 = (int)want2; nb3 = 1; }
-            else { nb2 = 1024; nb3 = (int)std::min<double>((double)(1 << (SK_BUCKET_BITS - l1 - 10)), std::ceil(want2 / 1024.0)); }
-            l2 = nb2 > 1 ? 1 : 0;
-        }
-    }
-    if (nb2 == 0 && l2 > 0) nb2 = 1 << l2;
-    if (pre && l2 == 0) { l2 = 1; nb2 = 1; }
-    if (l2 == 0) nb3 = 1;
-    const int fb2 = (nb3 == 1 && ((nb2 > 0 && (nb2 & (nb2 - 1)) != 0) || (auto_T && l1 >= 9 && nb2 > 1))) ? SK_BUCKET_BITS - l1 : 0;
-    const uint64_t n_l2 = l2 > 0 ? (uint64_t)nb1 * (uint64_t)nb2 : (uint64_t)nb1;
-    const uint64_t n_buckets = n_l2 * (uint64_t)nb3;
-    const int l2_pow = (fb2 || l2 == 0) ? 0 : (int)std::lround(std::log2((double)nb2));
-    const int fb3 = nb3 > 1 ? SK_BUCKET_BITS - l1 - l2_pow : 0;
-    CHK(buf_ensure(h, h->ar_misc[5], n_buckets * 16));
-    uint64_t *b_start = (uint64_t *)h->ar_misc[5].p, *b_cnt = b_start + n_buckets;
-    uint64_t *l2_start = b_start, *l2_cnt = b_cnt;
-    if (nb3 > 1) {
-        CHK(buf_ensure(h, h->ar_l2, n_l2 * 16));
-        l2_start = (uint64_t *)h->ar_l2.p;
-        l2_cnt = l2_start + n_l2;
-    }
-    if (l2 > 0) {
-        const int sh2 = fb2 ? top - SK_BUCKET_BITS : top - l1 - l2_pow;
-        if (pre) {
-            HIPCHK(h, hipMemsetAsync(b_start, 0, n_buckets * 16, h->stream));
-            if (nb3 > 1) HIPCHK(h, hipMemsetAsync(l2_start, 0, n_l2 * 16, h->stream));
-            HIPCHK(h, hipMemsetAsync(h->d_scalars + 56, 0, 16, h->stream));
-            // records received by value with 4-byte stamps (a sharded build): the stamps' bits 61..32 come in the meta
-            // words (WREC_ST_HI) and join the stamps here, where the sender's stamp base is added
-            constexpr int sthi = (sizeof(STI) == 4 && sizeof(ST) == 8) ? WREC_ST_HI : 0;
-            CHK((multisplit_level<ST, true, STI, sthi>(h, ps_start, ps_cnt, ps_n, (uint32_t)pre->n_senders, n_rec, in_w0, in_w1,
-                                                       (const STI *)pre->in_st, w0[0], w1[0], st[0], sh2, nb2, l2_start + b_lo * nb2,
-                                                       l2_cnt + b_lo * nb2, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], fb2, ps_add,
-                                                       (unsigned long long *)nullptr)));
-        } else {
-            CHK((multisplit_level<ST, true>(h, c1_start, c1_cnt, (uint32_t)nb1, 1, n_rec, w0[1], w1[1], st[1], w0[0], w1[0], st[0], sh2,
-                                            nb2, l2_start, l2_cnt, h->ar_misc[2], h->ar_misc[3], h->ar_misc[4], fb2)));
-        }
-        where = 0;
-        if (nb3 > 1) {
-            if (!w0[1]) {  // callers that start at level 2 may bring one record set only
-                CHK(buf_ensure(h, h->ar_rec[1][0], (n_rec + 16) * 8));
-                CHK(buf_ensure(h, h->ar_rec[1][1], (n_rec + 16) * 8));
-                CHK(buf_ensure(h, h->ar_rec[1][2], (n_rec + 16) * sizeof(ST)));
-                w0[1] = (uint64_t *)h->ar_rec[1][0].p; w1[1] = (uint64_t *)h->ar_rec[1][1].p; st[1] = (ST *)h->ar_rec[1][2].p;
-            }
-            const uint64_t p_lo = pre ? b_lo * nb2 : 0, p_n = pre ? (uint64_t)bps * nb2 : n_l2;
-            CHK((multisplit_level<ST, true>(h, l2_start + p_lo, l2_cnt + p_lo, (uint32_t)p_n, 1, n_rec, w0[0], w1[0], st[0], w0[1], w1[1],
-                                            st[1], top - SK_BUCKET_BITS, nb3, b_start + p_lo * nb3, b_cnt + p_lo * nb3, h->ar_misc[2],
-                                            h->ar_misc[3], h->ar_misc[4], fb3)));
-            where = 1;
-        }
-    } else {
-        HIPCHK(h, hipMemcpyAsync(b_start, c1_start, (size_t)nb1 * 8, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(b_cnt, c1_cnt, (size_t)nb1 * 8, hipMemcpyDeviceToDevice, h->stream));
-    }
-    h->stats.ms_partition = t_part.stop();
-    h->stats.n_buckets = n_buckets;
+    constexpr int L1_WIDE_FROM = 18;
+    // records received by value with 4-byte stamps (a sharded build): the stamps' bits 61..32 come in the meta
+    // words (WREC_ST_HI) and join the stamps at level 2, where the sender's stamp base is added
+    constexpr int sthi = (sizeof(STI) == 4 && sizeof(ST) == 8) ? WREC_ST_HI : 0;
+    auto estimate = [h, k, pk](unsigned grid, const uint64_t *s_start, const uint64_t *s_cnt, uint32_t seg, const uint64_t *rw0,
+                               const uint64_t *rw1, unsigned long long *set, uint64_t set_mask, unsigned long long *d_est) {
+        hipLaunchKernelGGL(k_wsk_estimate, dim3(grid), dim3(256), 0, h->stream, s_start, s_cnt, seg, rw0, rw1, k, pk, set, set_mask, d_est);
+    };
+    const SkPartitionParams<decltype(estimate)> pp{TARGET_DISTINCT, L1_WIDE_FROM, false, false, estimate};
+    SkPartition P;
+    CHK((sk_partition<ST, STI, sthi>(h, pp, seg_start, seg_cnt, n_seg, host_cnt, pre, nullptr, in_w0, in_w1, in_st, w0, w1, st,
+                                     shard_bits, my_shard, n_rec, n_inst, n_edge_inst, &P)));
+    uint64_t *const b_start = P.b_start, *const b_cnt = P.b_cnt;
+    const uint64_t n_buckets = P.n_buckets;
+    const int where = P.where;
+    const double est_distinct = P.est_distinct;
     // the records' bases, aligned, in bucket order (k_wsk_gather)
     CHK(buf_ensure(h, h->ar_wide[2], (n_rec + 1) * 32));
     uint4 *rec_b = (uint4 *)h->ar_wide[2].p;
@@ -4481,8 +4430,8 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
     uint64_t q_cap = 2 * n_rec + 1024;  // one per record, more where a bucket is counted in hash sub-ranges
     const uint64_t own_cnt = n_buckets >> shard_bits, own_lo = (uint64_t)my_shard * own_cnt;
     const uint64_t range_cap = n_buckets + 4096 + n_inst / (WCAP / 4);
-    CHK(buf_ensure(h, h->ar_misc[6], range_cap * sizeof(SkRange)));
-    SkRange *ranges = (SkRange *)h->ar_misc[6].p;
+    CHK(buf_ensure(h, h->ar_misc[MISC_RANGES], range_cap * sizeof(SkRange)));
+    SkRange *ranges = (SkRange *)h->ar_misc[MISC_RANGES].p;
     CHK(buf_ensure(h, h->ar_dir, (own_cnt + (range_cap - n_buckets)) * (WCAP / 64) * sizeof(SkDirEnt)));
     SkDirEnt *dirs = (SkDirEnt *)h->ar_dir.p;
     uint64_t *q_lo = nullptr, *q_hi = nullptr;
@@ -4529,7 +4478,7 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
             if (est_distinct > 0.0) split_recs = (uint32_t)std::min<double>(1e9, std::max<double>(16.0, (WCAP * 0.80) / (est_distinct / (double)n_rec)));
             // descriptor in device memory (see fresh_args): words 64.. of the scalar block are reserved for it
             static_assert(sizeof(WSkCountOut) <= 64 * 8, "descriptor slot");
-            WSkCountOut *d_out = (WSkCountOut *)(h->d_scalars + 64);
+            WSkCountOut *d_out = (WSkCountOut *)(h->d_scalars + SC_DESCRIPTOR);
             HIPCHK(h, hipMemcpyAsync(d_out, &out, sizeof(out), hipMemcpyHostToDevice, h->stream));
             hipLaunchKernelGGL(kern, dim3(grid), dim3(WCNT_NT), lds, h->stream, b_start, b_cnt, w0[where], w1[where], st[where],
                                (const uint4 *)rec_b, k, n_buckets, (const WSkCountOut *)d_out, split_recs);
@@ -4538,18 +4487,18 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
         h->stats.count_launches = n_rec ? (uint64_t)(attempt + 1) : 0;
         HIPCHK(h, hipMemcpyAsync(sc, h->d_scalars, 64, hipMemcpyDeviceToHost, h->stream));
         h->stats.ms_count = t.stop();
-        if (sc[0] & (8 | 32 | 512 | 2048)) break;
+        if (sc[0] & (STATUS_BUCKET_TOO_BIG | STATUS_RANGE_CAP | STATUS_COUNTER16 | STATUS_INCONSISTENT)) break;
         bool again = false;
-        if ((sc[0] & 16) && (node_cap < node_cap_max || edge_cap < edge_cap_max)) { node_cap = node_cap_max; edge_cap = edge_cap_max; again = true; }
-        if ((sc[0] & 64) && q_cap < n_edge_inst + 1024) { q_cap = n_edge_inst + 1024; again = true; }
+        if ((sc[0] & STATUS_NODE_EDGE_CAP) && (node_cap < node_cap_max || edge_cap < edge_cap_max)) { node_cap = node_cap_max; edge_cap = edge_cap_max; again = true; }
+        if ((sc[0] & STATUS_QUERY_CAP) && q_cap < n_edge_inst + 1024) { q_cap = n_edge_inst + 1024; again = true; }
         if (!again || attempt == 2) break;
     }
-    if (sc[0] & 1024) { h->err = "two-word count kernel: an LDS slot claim never completed"; return DBG_E_HIP; }
-    if (sc[0] & 512) { h->err = "16-bit successor counter overflow"; return DBG_E_CAPACITY; }
-    if (sc[0] & 2048) { h->err = "internal: k_wsk_count2 counted a bucket's nodes or edges inconsistently"; return DBG_E_HIP; }  // (after 512: a wrapped counter reads 0 twice)
-    if (sc[0] & 8) { h->err = "a bucket could not be split to fit the LDS table"; return DBG_E_CAPACITY; }
-    if (sc[0] & 16) { h->err = "node/edge capacity exceeded"; return DBG_E_CAPACITY; }
-    if (sc[0] & (32 | 64)) { h->err = "range/query list overflow"; return DBG_E_CAPACITY; }
+    if (sc[0] & STATUS_CLAIM_STUCK) { h->err = "two-word count kernel: an LDS slot claim never completed"; return DBG_E_HIP; }
+    if (sc[0] & STATUS_COUNTER16) { h->err = "16-bit successor counter overflow"; return DBG_E_CAPACITY; }
+    if (sc[0] & STATUS_INCONSISTENT) { h->err = "internal: k_wsk_count2 counted a bucket's nodes or edges inconsistently"; return DBG_E_HIP; }  // (after STATUS_COUNTER16: a wrapped counter reads 0 twice)
+    if (sc[0] & STATUS_BUCKET_TOO_BIG) { h->err = "a bucket could not be split to fit the LDS table"; return DBG_E_CAPACITY; }
+    if (sc[0] & STATUS_NODE_EDGE_CAP) { h->err = "node/edge capacity exceeded"; return DBG_E_CAPACITY; }
+    if (sc[0] & (STATUS_RANGE_CAP | STATUS_QUERY_CAP)) { h->err = "range/query list overflow"; return DBG_E_CAPACITY; }
     h->n_nodes = sc[4] & 0xFFFFFFFFull;
     h->n_edges = sc[4] >> 32;
     {
@@ -4561,7 +4510,7 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
     uint64_t n_q = sc[5];
     const uint64_t n_ranges = n_buckets + sc[6];
     h->stats.n_queries = n_q;
-    SkGeom geom{k, m, l1, l2 > 0 ? nb2 : 1, fb2, l2_pow, nb3, fb3, shard_bits, my_shard, own_lo, own_cnt};
+    SkGeom geom{k, m, P.l1, P.nb2, P.fb2, P.l2_pow, P.nb3, P.fb3, shard_bits, my_shard, own_lo, own_cnt};
     {
         // successors in another bucket.  Of this shard: through the target range's directory.  Of another shard: grouped
         // by owner and parked as (lo, hi) pairs for the exchange (dbg_shard_answer / dbg_shard_apply), as for k <= 31.
@@ -4579,15 +4528,15 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
             uint32_t *s_col = (uint32_t *)h->ar_q[1][2].p;
             hipLaunchKernelGGL(k_wq_bucket, dim3(grid_for(n_q, 256)), dim3(256), 0, h->stream, q_lo, q_hi, q_meta, n_q, k, m);
             HIPCHK(h, hipGetLastError());
-            CHK(buf_ensure(h, h->ar_misc[7], 512 * 16 + 16));
-            uint64_t *q_seg = (uint64_t *)h->ar_misc[7].p;
+            CHK(buf_ensure(h, h->ar_misc[MISC_QUERY_SEGS], 512 * 16 + 16));
+            uint64_t *q_seg = (uint64_t *)h->ar_misc[MISC_QUERY_SEGS].p;
             const int nsh = 1 << shard_bits;
             const uint64_t root[2] = {0, n_q};
             HIPCHK(h, hipMemcpyAsync(q_seg, root, 16, hipMemcpyHostToDevice, h->stream));
             uint64_t *o_start = q_seg + 2, *o_cnt = o_start + nsh;
             CHK((multisplit_level<uint32_t, true>(h, q_seg, q_seg + 1, 1, 1, n_q, q_lo, q_meta, q_col, s_lo, s_meta, s_col,
-                                                  40 + SK_BUCKET_BITS - shard_bits, nsh, o_start, o_cnt, h->ar_misc[2],
-                                                  h->ar_misc[3], h->ar_misc[4])));
+                                                  40 + SK_BUCKET_BITS - shard_bits, nsh, o_start, o_cnt, h->ar_misc[MISC_MS_SCPRE],
+                                                  h->ar_misc[MISC_MS_CMAT], h->ar_misc[MISC_MS_OFFS])));
             ShardState &sh = shard_of(h);
             sh.q_start.assign(nsh, 0);
             sh.q_cnt.assign(nsh, 0);
@@ -4615,7 +4564,7 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
             HIPCHK(h, hipGetLastError());
             HIPCHK(h, hipMemcpyAsync(sc, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
-            if (sc[0] & 128) { h->err = "internal: a successor k-mer was not found in its bucket"; return DBG_E_HIP; }
+            if (sc[0] & STATUS_SUCC_MISSING) { h->err = "internal: a successor k-mer was not found in its bucket"; return DBG_E_HIP; }
         }
         h->stats.ms_succ = t.stop();
     }
@@ -4631,7 +4580,7 @@ static int build_wsk_t(dbg *h, int k) {
     ST *st[2];
     uint32_t n_seg = 0;
     CHK(wsk_extract<ST>(h, k, &pk, w0, w1, st, &seg_start, &seg_cnt, &n_seg, &n_rec));
-    return wsk_count<ST, ST>(h, k, pk, seg_start, seg_cnt, n_seg, n_rec, h->n_kmer_inst, h->n_edge_inst, w0[0], w1[0], st[0], w0, w1, st,
+    return wsk_count<ST, ST>(h, k, pk, seg_start, seg_cnt, n_seg, h->host_seg_cnt.data(), n_rec, h->n_kmer_inst, h->n_edge_inst, w0[0], w1[0], st[0], w0, w1, st,
                              0, 0, nullptr);
 }
 
@@ -4653,7 +4602,7 @@ static int build_sk_t(dbg *h, int k, uint64_t node_capacity_hint) {
     ExtractSplit xs;
     xs.target = SK_TARGET_DISTINCT<CAP>;
     CHK(sk_extract<ST>(h, k, w0, w1, st, &seg_start, &seg_cnt, &n_seg, &n_rec, 0, 1, &xs));
-    return sk_count_from_segments<ST, CAP>(h, k, seg_start, seg_cnt, n_seg, n_rec, h->n_kmer_inst, h->n_edge_inst, w0[0],
+    return sk_count_from_segments<ST, CAP>(h, k, seg_start, seg_cnt, n_seg, h->host_seg_cnt.data(), n_rec, h->n_kmer_inst, h->n_edge_inst, w0[0],
                                            w1[0], st[0], w0, w1, st, node_capacity_hint, 0, 0, nullptr, &xs);
 }
 
@@ -4708,7 +4657,7 @@ __global__ __launch_bounds__(256) void k_apply_remote(const uint32_t *__restrict
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t a = ans[i];
-    if (a == NO_NODE || a >= (1u << 29)) { atomicOr(&scalars[0], 256ull); return; }
+    if (a == NO_NODE || a >= (1u << 29)) { atomicOr(&scalars[0], STATUS_REMOTE_UNRESOLVED); return; }
     col[qcol[i]] = tag | a;
 }
 
@@ -4749,7 +4698,7 @@ static int shard_extract_wide(dbg *h, int k, int n_shards, uint64_t *send_counts
     HIPCHK(h, hipMemcpyAsync(sc, h->d_scalars, 64 * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
-    if (sc[0] & 1) { h->err = "reads hold a byte outside ACGT"; return DBG_E_ALPHABET; }
+    if (sc[0] & STATUS_BAD_BASE) { h->err = "reads hold a byte outside ACGT"; return DBG_E_ALPHABET; }
     h->n_kmer_inst = sc[1];
     h->n_edge_inst = sc[2];
     uint64_t offs[8] = {0}, total = 0;
@@ -4811,7 +4760,7 @@ static int shard_build_wide(dbg *h, int k, int n_shards, int my_shard, const uin
     HIPCHK(h, hipMemcpyAsync(&sc0, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream));
     h->stats.ms_count = tc.stop();
     HIPCHK(h, hipGetLastError());
-    if (sc0 & 2) { h->err = "hash table capacity exceeded"; return DBG_E_CAPACITY; }
+    if (sc0 & STATUS_TABLE_FULL) { h->err = "hash table capacity exceeded"; return DBG_E_CAPACITY; }
     h->stats.count_launches = (uint64_t)n_shards;
     uint64_t n_edge = 0;
     CHK(reduce_sum(h, n_rec, HasSuccBit{t_st}, &n_edge));
@@ -4885,12 +4834,12 @@ static int shard_extract_wsk(dbg *h, int k, int n_shards, uint64_t *send_counts,
         if (sizeof(ST) == 4) st[1] = (ST *)st_out;  // (64-bit stamps stay in the record arena until the gather splits them)
     }
     const int nb1 = 512;
-    CHK(buf_ensure(h, h->ar_misc[1], (uint64_t)nb1 * 16));
-    uint64_t *c1_start = (uint64_t *)h->ar_misc[1].p, *c1_cnt = c1_start + nb1;
+    CHK(buf_ensure(h, h->ar_misc[MISC_L1_CHILDREN], (uint64_t)nb1 * 16));
+    uint64_t *c1_start = (uint64_t *)h->ar_misc[MISC_L1_CHILDREN].p, *c1_cnt = c1_start + nb1;
     Timer t(h->stream);
     CHK((multisplit_level<ST, true>(h, seg_start, seg_cnt, n_seg, n_seg, n_rec, w0[0], w1[0], st[0], w0[1], w1[1], st[1],
-                                    6 + SK_BUCKET_BITS - 9, nb1, c1_start, c1_cnt, h->ar_misc[2], h->ar_misc[3],
-                                    h->ar_misc[4], 0, nullptr, nullptr, h->host_seg_cnt.data())));
+                                    6 + SK_BUCKET_BITS - 9, nb1, c1_start, c1_cnt, h->ar_misc[MISC_MS_SCPRE], h->ar_misc[MISC_MS_CMAT],
+                                    h->ar_misc[MISC_MS_OFFS], 0, nullptr, nullptr, h->host_seg_cnt.data())));
     std::vector<uint64_t> cnt(nb1);
     HIPCHK(h, hipMemcpyAsync(cnt.data(), c1_cnt, nb1 * 8, hipMemcpyDeviceToHost, h->stream));
     dbg::Buf &b_rb = n_parts > 1 ? h->ar_part[part][0] : h->ar_wide[2];
@@ -4965,7 +4914,7 @@ static int shard_build_wsk(dbg *h, int k, int n_shards, int my_shard, const uint
     pre.in_st = d_st32;
     const int w = k - SK_MAX_M + 1;
     Timer t_total(h->stream);
-    int rc = wsk_count<uint64_t, uint32_t>(h, k, d_rb, nullptr, nullptr, 0, n_rec, n_rec * (uint64_t)w, n_rec * (uint64_t)w, in_w0, d_w1,
+    int rc = wsk_count<uint64_t, uint32_t>(h, k, d_rb, nullptr, nullptr, 0, nullptr, n_rec, n_rec * (uint64_t)w, n_rec * (uint64_t)w, in_w0, d_w1,
                                            (const uint64_t *)nullptr, w0, w1, st, shard_bits, my_shard, &pre);
     if (rc != DBG_OK) { const std::string keep = h->err; free_build(h); h->err = keep; return rc; }
     // successors owned by other shards: (lo, hi) pairs grouped by owner (two words per query)
@@ -5004,12 +4953,12 @@ static int shard_extract_sk(dbg *h, int k, int n_shards, uint64_t *send_counts, 
     }
     // group by the 9 top bits of the bucket hash: owners are contiguous ranges of those 512 groups
     const int nb1 = 512;
-    CHK(buf_ensure(h, h->ar_misc[1], (uint64_t)nb1 * 16));
-    uint64_t *c1_start = (uint64_t *)h->ar_misc[1].p, *c1_cnt = c1_start + nb1;
+    CHK(buf_ensure(h, h->ar_misc[MISC_L1_CHILDREN], (uint64_t)nb1 * 16));
+    uint64_t *c1_start = (uint64_t *)h->ar_misc[MISC_L1_CHILDREN].p, *c1_cnt = c1_start + nb1;
     Timer t(h->stream);
     CHK((multisplit_level<ST, true>(h, seg_start, seg_cnt, n_seg, n_seg, n_rec, w0[0], w1[0], st[0], w0[1], w1[1],
-                                    st[1], 6 + SK_BUCKET_BITS - 9, nb1, c1_start, c1_cnt, h->ar_misc[2],
-                                    h->ar_misc[3], h->ar_misc[4])));
+                                    st[1], 6 + SK_BUCKET_BITS - 9, nb1, c1_start, c1_cnt, h->ar_misc[MISC_MS_SCPRE],
+                                    h->ar_misc[MISC_MS_CMAT], h->ar_misc[MISC_MS_OFFS])));
     std::vector<uint64_t> cnt(nb1);
     HIPCHK(h, hipMemcpyAsync(cnt.data(), c1_cnt, nb1 * 8, hipMemcpyDeviceToHost, h->stream));
     h->stats.ms_partition = t.stop();
@@ -5143,38 +5092,38 @@ extern "C" int dbg_shard_build(dbg_t *h, int k, int n_shards, int my_shard, cons
         pre.in_st = d_st32;
         const int w = k - sk_m_for_k(k) + 1;  // a record holds at most w k-mers
         if (stamp_bytes == 8)  // senders that hold 2 GiB of reads or more
-            rc = sk_count_from_segments<uint64_t, 4096, uint64_t>(h, k, nullptr, nullptr, 0, n_rec, n_rec * (uint64_t)w,
+            rc = sk_count_from_segments<uint64_t, 4096, uint64_t>(h, k, nullptr, nullptr, 0, nullptr, n_rec, n_rec * (uint64_t)w,
                                                                   n_rec * (uint64_t)w, (const uint64_t *)d_w0, (const uint64_t *)d_w1,
                                                                   (const uint64_t *)nullptr, w0, w1, st, 0, shard_bits, my_shard, &pre);
         else
-            rc = sk_count_from_segments<uint64_t, 4096, uint32_t>(h, k, nullptr, nullptr, 0, n_rec, n_rec * (uint64_t)w,
+            rc = sk_count_from_segments<uint64_t, 4096, uint32_t>(h, k, nullptr, nullptr, 0, nullptr, n_rec, n_rec * (uint64_t)w,
                                                                   n_rec * (uint64_t)w, (const uint64_t *)d_w0, (const uint64_t *)d_w1,
                                                                   (const uint64_t *)nullptr, w0, w1, st, 0, shard_bits, my_shard, &pre);
         n_inst = h->n_kmer_inst;
         n_edge = h->n_edge_inst;
     } else {
         if (stamp_bytes == 8) { h->err = "64-bit rank-local stamps need sender_bucket_counts (the receiver starts at level 2)"; return DBG_E_ARG; }
-        CHK(buf_ensure(h, h->ar_misc[0], (uint64_t)n_shards * 16));
-        uint64_t *seg_start = (uint64_t *)h->ar_misc[0].p, *seg_cnt = seg_start + n_shards;
+        CHK(buf_ensure(h, h->ar_misc[MISC_SEGMENTS], (uint64_t)n_shards * 16));
+        uint64_t *seg_start = (uint64_t *)h->ar_misc[MISC_SEGMENTS].p, *seg_cnt = seg_start + n_shards;
         HIPCHK(h, hipMemcpyAsync(seg_start, seg.data(), seg.size() * 8, hipMemcpyHostToDevice, h->stream));
         // the rebased stamps of the received records go to ar_shard[2]
         CHK(buf_ensure(h, h->ar_shard[2], (n_rec + 16) * 8));
         uint64_t *st64 = (uint64_t *)h->ar_shard[2].p;
-        HIPCHK(h, hipMemsetAsync(h->d_scalars + 56, 0, 16, h->stream));
+        HIPCHK(h, hipMemsetAsync(h->d_scalars + SC_L2_SUMS, 0, 16, h->stream));
         for (int r = 0; r < n_shards; ++r) {
             if (!recv_counts[r]) continue;
             const unsigned grid = (unsigned)std::min<uint64_t>(grid_for(recv_counts[r], 256), 8192);
             hipLaunchKernelGGL(k_stamp_globalize, dim3(grid), dim3(256), 0, h->stream, (const uint32_t *)d_st32 + seg[r],
                                (const uint64_t *)d_w1 + seg[r], recv_counts[r], stamp_base[r] << 1, st64 + seg[r],
-                               (unsigned long long *)(h->d_scalars + 56));
+                               (unsigned long long *)(h->d_scalars + SC_L2_SUMS));
         }
         HIPCHK(h, hipGetLastError());
         uint64_t sums[2] = {0, 0};
-        HIPCHK(h, hipMemcpyAsync(sums, h->d_scalars + 56, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(sums, h->d_scalars + SC_L2_SUMS, 16, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         n_inst = sums[0];
         n_edge = sums[1];
-        rc = sk_count_from_segments<uint64_t, 4096>(h, k, seg_start, seg_cnt, (uint32_t)n_shards, n_rec, n_inst, n_edge,
+        rc = sk_count_from_segments<uint64_t, 4096>(h, k, seg_start, seg_cnt, (uint32_t)n_shards, nullptr, n_rec, n_inst, n_edge,
                                                     (const uint64_t *)d_w0, (const uint64_t *)d_w1, st64, w0, w1, st, 0,
                                                     shard_bits, my_shard);
     }
@@ -5196,7 +5145,7 @@ extern "C" int dbg_shard_answer(dbg_t *h, const void *d_q_keys, uint64_t n, void
     unsigned long long *sc_dev = (unsigned long long *)h->d_scalars;
     HIPCHK(h, hipMemsetAsync(d_answers, 0xFF, n * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_scalars, 0, 8, h->stream));
-    const SkRange *ranges = (const SkRange *)h->ar_misc[6].p;
+    const SkRange *ranges = (const SkRange *)h->ar_misc[MISC_RANGES].p;
     const SkDirEnt *dirs = (const SkDirEnt *)h->ar_dir.p;
     if (!ranges || !dirs || h->sk_cap != 4096) { h->err = "dbg_shard_build must run first"; return DBG_E_ARG; }
     if (h->k > 31) {  // two-word k-mers: the keys come as (lo, hi) pairs
@@ -5212,7 +5161,7 @@ extern "C" int dbg_shard_answer(dbg_t *h, const void *d_q_keys, uint64_t n, void
     uint64_t sc0 = 0;
     HIPCHK(h, hipMemcpyAsync(&sc0, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (sc0 & 128) { h->err = "a queried successor k-mer is not a node of this shard"; return DBG_E_HIP; }
+    if (sc0 & STATUS_SUCC_MISSING) { h->err = "a queried successor k-mer is not a node of this shard"; return DBG_E_HIP; }
     return DBG_OK;
 }
 
@@ -5232,11 +5181,11 @@ __global__ __launch_bounds__(256) void k_import_fix(uint64_t n_nodes, const uint
     for (int b = 0; b < 4; ++b) {
         edges += c[b];
         if (s[b] == NO_NODE) {
-            if (c[b]) atomicOr(&scalars[0], 512ull);  // a counted successor without a node
+            if (c[b]) atomicOr(&scalars[0], STATUS_BAD_GATHERED_ID);  // a counted successor without a node
             continue;
         }
         const uint64_t id = shard_base[s[b] >> 29] + (s[b] & ((1u << 29) - 1));
-        if (id >= n_nodes) { atomicOr(&scalars[0], 512ull); s[b] = NO_NODE; continue; }
+        if (id >= n_nodes) { atomicOr(&scalars[0], STATUS_BAD_GATHERED_ID); s[b] = NO_NODE; continue; }
         s[b] = (uint32_t)id;
     }
     reinterpret_cast<uint4 *>(succ)[i] = make_uint4(s[0], s[1], s[2], s[3]);
@@ -5339,7 +5288,7 @@ extern "C" int dbg_import_graph(dbg_t *h, int k, int n_shards, const uint64_t *s
     uint64_t sc[4] = {0, 0, 0, 0};
     HIPCHK(h, hipMemcpyAsync(sc, h->d_scalars, 32, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (sc[0] & 512) { h->err = "gathered successor ids do not fit the shard sizes"; free_build(h); return DBG_E_ARG; }
+    if (sc[0] & STATUS_BAD_GATHERED_ID) { h->err = "gathered successor ids do not fit the shard sizes"; free_build(h); return DBG_E_ARG; }
     h->n_edge_inst = sc[2];
     h->n_kmer_inst = 0;  // not carried by the shards
     int rc = finish_graph(h);
@@ -5367,7 +5316,7 @@ extern "C" int dbg_shard_apply(dbg_t *h, const void *d_answers) {
     uint64_t sc0 = 0;
     HIPCHK(h, hipMemcpyAsync(&sc0, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (sc0 & 256) { h->err = "a remote successor came back unresolved"; return DBG_E_HIP; }
+    if (sc0 & STATUS_REMOTE_UNRESOLVED) { h->err = "a remote successor came back unresolved"; return DBG_E_HIP; }
     h->stats.ms_succ += t.stop();
     return finish_graph(h);
 }
@@ -5423,7 +5372,7 @@ static int part_compact(dbg *sub, uint64_t n_dir_entries) {
     CHK(buf_shrink(sub, sub->ar_csr[1], ne * 4));
     CHK(buf_shrink(sub, sub->ar_csr[2], ne * 4));
     CHK(buf_shrink(sub, sub->ar_dir, n_dir_entries * sizeof(SkDirEnt)));
-    CHK(buf_shrink(sub, sub->ar_misc[6], sub->sk_n_ranges * sizeof(SkRange)));
+    CHK(buf_shrink(sub, sub->ar_misc[MISC_RANGES], sub->sk_n_ranges * sizeof(SkRange)));
     sub->d_keys = (uint64_t *)sub->ar_node[0].p;
     sub->d_stamps_st = sub->ar_node[st_slot].p;
     if (sub->stamps_st_bytes == 8) sub->d_stamps = (uint64_t *)sub->d_stamps_st;
@@ -5433,7 +5382,8 @@ static int part_compact(dbg *sub, uint64_t n_dir_entries) {
     sub->d_ecnt = (uint32_t *)sub->ar_csr[2].p;
     for (auto &lvl : sub->ar_rec) for (auto &b : lvl) buf_free(sub, b);
     for (auto &lvl : sub->ar_q) for (auto &b : lvl) buf_free(sub, b);
-    for (int i : {0, 1, 2, 3, 4, 5, 7, 8}) buf_free(sub, sub->ar_misc[i]);
+    for (int i = 0; i < MISC_SLOTS; ++i)
+        if (i != MISC_RANGES) buf_free(sub, sub->ar_misc[i]);  // the ranges stay: the answer stage reads them
     buf_free(sub, sub->ar_scan);
     sub->sk_src.valid = false;
     return DBG_OK;
@@ -5481,7 +5431,7 @@ __global__ __launch_bounds__(256) void k_apply_part(const uint32_t *__restrict__
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t a = ans[i];
-    if (a == NO_NODE) { atomicOr(&scalars[0], 256ull); return; }
+    if (a == NO_NODE) { atomicOr(&scalars[0], STATUS_REMOTE_UNRESOLVED); return; }
     col[qcol[i]] = a;
     col_owner[qcol[i]] = owner;
 }
@@ -5566,10 +5516,10 @@ static int multipass_parts(dbg *h, int k, int n_virtual, int v_first, int n_pass
         pre.in_st = in_st;
         int rc = DBG_OK;
         if (n_rec_p && pk) {
-            rc = wsk_count<ST, STI>(sub, k, pk, nullptr, nullptr, 0, n_rec_p, n_rec_p * (uint64_t)w, n_rec_p * (uint64_t)w, in_w0,
+            rc = wsk_count<ST, STI>(sub, k, pk, nullptr, nullptr, 0, nullptr, n_rec_p, n_rec_p * (uint64_t)w, n_rec_p * (uint64_t)w, in_w0,
                                     in_w1, (const ST *)nullptr, pw0, pw1, pst, shard_bits, v_first + p, &pre);
         } else if (n_rec_p)
-            rc = sk_count_from_segments<ST, 4096, STI>(sub, k, nullptr, nullptr, 0, n_rec_p, n_rec_p * (uint64_t)w, n_rec_p * (uint64_t)w,
+            rc = sk_count_from_segments<ST, 4096, STI>(sub, k, nullptr, nullptr, 0, nullptr, n_rec_p, n_rec_p * (uint64_t)w, n_rec_p * (uint64_t)w,
                                                        in_w0, in_w1, (const ST *)nullptr, pw0, pw1, pst, 0, shard_bits, v_first + p, &pre);
         if (rc != DBG_OK) { h->err = "pass " + std::to_string(p) + ": " + sub->err; return rc; }
         if (n_rec_p && n_passes > 1) {  // parts parked side by side: cut to size (one part: the estimate's slack may stay)
@@ -5623,7 +5573,7 @@ static int multipass_parts(dbg *h, int k, int n_virtual, int v_first, int n_pass
         uint64_t sc0 = 0;
         HIPCHK(h, hipMemcpyAsync(&sc0, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (sc0 & 256) { h->err = "a successor in another part came back unresolved"; return DBG_E_HIP; }
+        if (sc0 & STATUS_REMOTE_UNRESOLVED) { h->err = "a successor in another part came back unresolved"; return DBG_E_HIP; }
         ms_succ += t.stop();
     }
     h->n_nodes = mp->base[n_passes];
@@ -5642,14 +5592,14 @@ static int build_multipass_t(dbg *h, int k, int n_passes) {
     uint32_t n_seg = 0;
     CHK(sk_extract<ST>(h, k, w0, w1, st, &seg_start, &seg_cnt, &n_seg, &n_rec));
     const int nb1 = 512;
-    CHK(buf_ensure(h, h->ar_misc[1], (uint64_t)nb1 * 16));
-    uint64_t *c1_start = (uint64_t *)h->ar_misc[1].p, *c1_cnt = c1_start + nb1;
+    CHK(buf_ensure(h, h->ar_misc[MISC_L1_CHILDREN], (uint64_t)nb1 * 16));
+    uint64_t *c1_start = (uint64_t *)h->ar_misc[MISC_L1_CHILDREN].p, *c1_cnt = c1_start + nb1;
     std::vector<uint64_t> cnt(nb1), start(nb1);
     {
         Timer t(h->stream);
         CHK((multisplit_level<ST, true>(h, seg_start, seg_cnt, n_seg, n_seg, n_rec, w0[0], w1[0], st[0], w0[1], w1[1], st[1],
-                                        6 + SK_BUCKET_BITS - 9, nb1, c1_start, c1_cnt, h->ar_misc[2], h->ar_misc[3],
-                                        h->ar_misc[4])));
+                                        6 + SK_BUCKET_BITS - 9, nb1, c1_start, c1_cnt, h->ar_misc[MISC_MS_SCPRE], h->ar_misc[MISC_MS_CMAT],
+                                        h->ar_misc[MISC_MS_OFFS])));
         HIPCHK(h, hipMemcpyAsync(cnt.data(), c1_cnt, nb1 * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(start.data(), c1_start, nb1 * 8, hipMemcpyDeviceToHost, h->stream));
         h->stats.ms_partition = t.stop();
@@ -5669,14 +5619,14 @@ static int build_multipass_wsk(dbg *h, int k, int n_passes) {
     uint32_t n_seg = 0;
     CHK(wsk_extract<ST>(h, k, &pk, w0, w1, st, &seg_start, &seg_cnt, &n_seg, &n_rec));
     const int nb1 = 512;
-    CHK(buf_ensure(h, h->ar_misc[1], (uint64_t)nb1 * 16));
-    uint64_t *c1_start = (uint64_t *)h->ar_misc[1].p, *c1_cnt = c1_start + nb1;
+    CHK(buf_ensure(h, h->ar_misc[MISC_L1_CHILDREN], (uint64_t)nb1 * 16));
+    uint64_t *c1_start = (uint64_t *)h->ar_misc[MISC_L1_CHILDREN].p, *c1_cnt = c1_start + nb1;
     std::vector<uint64_t> cnt(nb1), start(nb1);
     {
         Timer t(h->stream);
         CHK((multisplit_level<ST, true>(h, seg_start, seg_cnt, n_seg, n_seg, n_rec, w0[0], w1[0], st[0], w0[1], w1[1], st[1],
-                                        6 + SK_BUCKET_BITS - 9, nb1, c1_start, c1_cnt, h->ar_misc[2], h->ar_misc[3],
-                                        h->ar_misc[4], 0, nullptr, nullptr, h->host_seg_cnt.data())));
+                                        6 + SK_BUCKET_BITS - 9, nb1, c1_start, c1_cnt, h->ar_misc[MISC_MS_SCPRE], h->ar_misc[MISC_MS_CMAT],
+                                        h->ar_misc[MISC_MS_OFFS], 0, nullptr, nullptr, h->host_seg_cnt.data())));
         HIPCHK(h, hipMemcpyAsync(cnt.data(), c1_cnt, nb1 * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(start.data(), c1_start, nb1 * 8, hipMemcpyDeviceToHost, h->stream));
         h->stats.ms_partition = t.stop();
@@ -5863,7 +5813,7 @@ extern "C" int dbg_multipass_finish(dbg_t *h) {
     for (dbg *sub : mp->part) { buf_free(sub, sub->ar_shard[0]); buf_free(sub, sub->ar_shard[3]); }
     h->arena_freed = true;
     if (mp->n_passes > 1) pool_trim(h);
-    if (sc0 & 256) { h->err = "a successor owned by another rank came back unresolved"; return DBG_E_HIP; }
+    if (sc0 & STATUS_REMOTE_UNRESOLVED) { h->err = "a successor owned by another rank came back unresolved"; return DBG_E_HIP; }
     return DBG_OK;
 }
 
@@ -6218,7 +6168,7 @@ extern "C" int dbg_part_cross_targets(dbg_t *h, int part, uint64_t *counts, void
     if (!sub->n_nodes) return DBG_OK;
     if (!mp->pflags[part]) { h->err = "dbg_part_prune must run first"; return DBG_E_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
-    unsigned long long *cur = (unsigned long long *)(h->d_scalars + 64);  // 64 words: the descriptor slot is free outside a build
+    unsigned long long *cur = (unsigned long long *)(h->d_scalars + SC_DESCRIPTOR);  // 64 words: the descriptor slot is free outside a build
     HIPCHK(h, hipMemsetAsync(cur, 0, 64 * 8, h->stream));
     const int me = mp->v_first + part;
     hipLaunchKernelGGL(k_part_cross, dim3(grid_for(sub->n_nodes, 256 * PART_CROSS_TILES)), dim3(256), 0, h->stream, sub->n_nodes, me, sub->d_flags,

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void k_sk_extract(const char *__restrict__ bas
         const uint64_t tile0 = tile * TILE;
         __syncthreads();  // LDS of the previous tile is free
         const uint32_t bad = load_tile(s.t, bases, n_bytes, startbits, tile0);
-        if (bad) atomicOr(&scalars[0], 1ull);
+        if (bad) atomicOr(&scalars[0], STATUS_BAD_BASE);
         __syncthreads();
         for (int j = threadIdx.x; j < TILE + HALO - 32; j += 256)
             s.hm[j] = (uint16_t)mmer_hash16((uint32_t)(window32(s.t, j) >> (64 - 2 * m)));
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void k_sk_extract(const char *__restrict__ bas
             rec_st[o] = (ST)((p << 1) | (s0 ^ 1u));
         }
     }
-    if (overflow && threadIdx.x == 0) atomicOr(&scalars[0], 4ull);
+    if (overflow && threadIdx.x == 0) atomicOr(&scalars[0], STATUS_SEGMENT_FULL);
     n_k = wave_sum_u64(n_k);
     n_e = wave_sum_u64(n_e);
     __syncthreads();
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256, DBG_EXW_WAVES) void k_sk_extract_w(const char 
             if (ps.ovf) { overflow = true; break; }  // uniform: raised while the previous tile was written
         }
         const uint32_t bad = load_tile(s.t, bases, n_bytes, startbits, tile0);
-        if (bad) atomicOr(&scalars[0], 1ull);
+        if (bad) atomicOr(&scalars[0], STATUS_BAD_BASE);
         __syncthreads();
         // ---- register phase
         const uint64_t wa = window32(s.t, j0), wb = window32(s.t, j0 + 32);
@@ -403,7 +403,7 @@ __global__ __launch_bounds__(256, DBG_EXW_WAVES) void k_sk_extract_w(const char 
                 cmat[((uint64_t)(d >> (l1 - f0)) * gridDim.x + blockIdx.x) * nbg + (d & (nbg - 1))] = ps.h1[d];
         }
     }
-    if (overflow && threadIdx.x == 0) atomicOr(&scalars[0], 4ull);
+    if (overflow && threadIdx.x == 0) atomicOr(&scalars[0], STATUS_SEGMENT_FULL);
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = n_k; red[4 + (threadIdx.x >> 6)] = n_e; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1073,7 +1073,7 @@ __global__ __launch_bounds__((CntCfg<ST, CAP>::NT)) void k_sk_count(const uint64
             if (s.overflow) {  // split this hash sub-range in two and retry (nothing was written out)
                 const uint32_t bit = cur_mask + 1;  // masks are 2^j - 1
                 if (stk_n + 2 > CNT_STACK || bit >= (1u << 20)) {
-                    if (threadIdx.x == 0) atomicOr(&fresh_args(outp)->scalars[0], 8ull);  // bucket cannot be split further
+                    if (threadIdx.x == 0) atomicOr(&fresh_args(outp)->scalars[0], STATUS_BUCKET_TOO_BIG);  // bucket cannot be split further
                     failed = true;
                     break;
                 }
@@ -1202,12 +1202,12 @@ __global__ __launch_bounds__((CntCfg<ST, CAP>::NT)) void k_sk_count(const uint64
                 const unsigned long long base = got & 0xFFFFFFFFull, eb = got >> 32;
                 s.gbase = base;
                 s.ebase = eb;
-                if (base + n_local > orr.node_cap || base + n_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], 16ull); s.fail = 1; }
-                if (eb + n_edges_local > orr.edge_cap || eb + n_edges_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], 16ull); s.fail = 1; }
+                if (base + n_local > orr.node_cap || base + n_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], STATUS_NODE_EDGE_CAP); s.fail = 1; }
+                if (eb + n_edges_local > orr.edge_cap || eb + n_edges_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], STATUS_NODE_EDGE_CAP); s.fail = 1; }
                 uint64_t ri = bucket;
                 if (cur_mask) {
                     ri = orr.n_buckets + atomicAdd(&orr.scalars[6], 1ull);
-                    if (ri >= orr.range_cap || ri >= 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], 32ull); s.fail = 1; }
+                    if (ri >= orr.range_cap || ri >= 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], STATUS_RANGE_CAP); s.fail = 1; }
                 }
                 s.ri = ri;
                 if (!s.fail) {
@@ -1278,7 +1278,7 @@ __global__ __launch_bounds__((CntCfg<ST, CAP>::NT)) void k_sk_count(const uint64
             // ---- queries out (the cursor has had the whole node pass to come back)
             if (threadIdx.x == 64 && nq) {
                 s.qbase = qgot;
-                if (qgot + nq > (*fresh_args(outp)).q_cap || qgot + nq > 0xFFFFFFF0ull) { atomicOr(&(*fresh_args(outp)).scalars[0], 64ull); s.fail = 1; }
+                if (qgot + nq > (*fresh_args(outp)).q_cap || qgot + nq > 0xFFFFFFF0ull) { atomicOr(&(*fresh_args(outp)).scalars[0], STATUS_QUERY_CAP); s.fail = 1; }
             }
             __syncthreads();
             CNT_TICK(12);
@@ -1420,7 +1420,7 @@ __global__ __launch_bounds__(256) void k_succ_resolve(const uint64_t *__restrict
         }
         if (have) id = dir_find<CAP>(dirs, g.own_cnt + (ri - n_buckets), keys, n_nodes, key);
     }
-    if (id == NO_NODE) { atomicOr(&scalars[0], 128ull); return; }  // every successor k-mer exists as a node
+    if (id == NO_NODE) { atomicOr(&scalars[0], STATUS_SUCC_MISSING); return; }  // every successor k-mer exists as a node
     out[q_col ? q_col[i] : i] = id | id_tag;
 }
 

@@ -70,6 +70,11 @@ struct Cnt2Cfg {
     static constexpr int PEND = sizeof(ST) == 8 ? 2048 : 4096;  // edges waiting for a successor lookup
 };
 
+// Words of the handle's scalar block that the host addresses by number during a build (word 0 holds the Status bits,
+// dbg_device.h).  Outside a build the words are free: dbg_build_from_walk keeps a cursor in word 40, the walk one in word 64.
+constexpr int SC_ESTIMATE = 40;    // (instances, distinct k-mers) of the estimate kernel
+constexpr int SC_L2_SUMS = 56;     // (k-mer, edge) instances summed by a level-2 histogram pass or k_stamp_globalize
+constexpr int SC_DESCRIPTOR = 64;  // words 64..: the count kernels' descriptor (fresh_args)
 // the query cursor of this kernel: far from the node / edge cursor (word 4) -- atomics on one cache line queue up behind each other
 constexpr int SK2_QUERY_CURSOR = 120;
 constexpr uint32_t HINT_VALID = 0x8000u;   // hint half of a counter word: the successor's slot is in bits 11:0
@@ -184,7 +189,7 @@ __global__ __launch_bounds__(1024) void k_sk_count2(const SkCount2Args *__restri
         if (!fl_nq || s.fail) return;  // (a failed pass -- no room in the query list -- ends the kernel at the next check)
         const auto &oq = fresh_args2(argp)->out;
         const uint64_t qbase = s.qbase;
-        if (s.n_q2 != fl_nq && threadIdx.x == 0) { atomicOr(&oq.scalars[0], 2048ull); s.fail = 1; }  // internal: query totals disagree
+        if (s.n_q2 != fl_nq && threadIdx.x == 0) { atomicOr(&oq.scalars[0], STATUS_INCONSISTENT); s.fail = 1; }  // internal: query totals disagree
         for (uint32_t i = threadIdx.x; i < min(fl_nq, (uint32_t)QS); i += NT) {
             oq.q_key[qbase + i] = s.qs_key[i];
             oq.q_col[qbase + i] = s.qs_col[i];
@@ -495,7 +500,7 @@ __global__ __launch_bounds__(1024) void k_sk_count2(const SkCount2Args *__restri
             if (s.overflow) {  // split this hash sub-range in two and retry (nothing was written out)
                 const uint32_t bit = cur_mask + 1;
                 if (stk_n + 2 > CNT_STACK || bit >= (1u << 20)) {
-                    if (threadIdx.x == 0) atomicOr(&fresh_args2(argp)->out.scalars[0], 8ull);
+                    if (threadIdx.x == 0) atomicOr(&fresh_args2(argp)->out.scalars[0], STATUS_BUCKET_TOO_BIG);
                     failed = true;
                     break;
                 }
@@ -588,12 +593,12 @@ __global__ __launch_bounds__(1024) void k_sk_count2(const SkCount2Args *__restri
                 const unsigned long long base = got & 0xFFFFFFFFull, eb = got >> 32;
                 s.gbase = base;
                 s.ebase = eb;
-                if (base + n_local > orr.node_cap || base + n_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], 16ull); s.fail = 1; }
-                if (eb + n_edges_local > orr.edge_cap || eb + n_edges_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], 16ull); s.fail = 1; }
+                if (base + n_local > orr.node_cap || base + n_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], STATUS_NODE_EDGE_CAP); s.fail = 1; }
+                if (eb + n_edges_local > orr.edge_cap || eb + n_edges_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], STATUS_NODE_EDGE_CAP); s.fail = 1; }
                 uint64_t ri = bucket;
                 if (cur_mask) {
                     ri = orr.n_buckets + atomicAdd(&orr.scalars[6], 1ull);
-                    if (ri >= orr.range_cap || ri >= 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], 32ull); s.fail = 1; }
+                    if (ri >= orr.range_cap || ri >= 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], STATUS_RANGE_CAP); s.fail = 1; }
                 }
                 s.ri = ri;
                 if (!s.fail) {
@@ -613,7 +618,7 @@ __global__ __launch_bounds__(1024) void k_sk_count2(const SkCount2Args *__restri
             const uint32_t nq = s.n_q;
             unsigned long long qgot = 0;
             if (threadIdx.x == 64 && nq) qgot = atomicAdd(&fresh_args2(argp)->out.scalars[SK2_QUERY_CURSOR], (unsigned long long)nq);
-            if (s.n_list != s.n_new && threadIdx.x == 0) { atomicOr(&fresh_args2(argp)->out.scalars[0], 2048ull); s.fail = 1; }  // internal: the insert's totals are off
+            if (s.n_list != s.n_new && threadIdx.x == 0) { atomicOr(&fresh_args2(argp)->out.scalars[0], STATUS_INCONSISTENT); s.fail = 1; }  // internal: the insert's totals are off
             if (s.fail) { failed = true; break; }  // written before the barrier above
             const uint64_t gbase = s.gbase, ebase = s.ebase;
             uint32_t unst = 0;  // queries of this thread that found no room in the staging: bit (u * 4 + base)
@@ -693,7 +698,7 @@ __global__ __launch_bounds__(1024) void k_sk_count2(const SkCount2Args *__restri
             if (threadIdx.x == 64 && nq) {
                 s.qbase = qgot;
                 const auto &oq = fresh_args2(argp)->out;
-                if (qgot + nq > oq.q_cap || qgot + nq > 0xFFFFFFF0ull) { atomicOr(&oq.scalars[0], 64ull); s.fail = 1; }
+                if (qgot + nq > oq.q_cap || qgot + nq > 0xFFFFFFF0ull) { atomicOr(&oq.scalars[0], STATUS_QUERY_CAP); s.fail = 1; }
             }
             fl_nq = nq;        // the staged queries leave after the next barrier every thread passes (flush_queries)
             fl_unst = unst;
@@ -701,7 +706,7 @@ __global__ __launch_bounds__(1024) void k_sk_count2(const SkCount2Args *__restri
             clean = true;
         }
         if (failed) {
-            if (s.fail == 2 && threadIdx.x == 0) atomicOr(&fresh_args2(argp)->out.scalars[0], 512ull);  // 16-bit counter overflow
+            if (s.fail == 2 && threadIdx.x == 0) atomicOr(&fresh_args2(argp)->out.scalars[0], STATUS_COUNTER16);  // 16-bit counter overflow
             return;
         }
     }

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(1024) void k_sk_count3(const SkCount2Args *__restri
                                       __builtin_amdgcn_readfirstlane((uint32_t)fl_got);
         const uint32_t at = (wave - (uint32_t)(NT / 64 - FLW)) * 64 + lane;
         if (qb + fl_cnt > oq.q_cap || qb + fl_cnt > 0xFFFFFFF0ull) {
-            if (lane == 0) { atomicOr(&oq.scalars[0], 64ull); s.fail = 1; }
+            if (lane == 0) { atomicOr(&oq.scalars[0], STATUS_QUERY_CAP); s.fail = 1; }
         } else if (lane < fl_cnt) {
             oq.q_key[qb + lane] = s.qs_key[at];
             oq.q_col[qb + lane] = s.qs_col[at];
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(1024) void k_sk_count3(const SkCount2Args *__restri
                     {   // the previous iteration's counter add has long returned: 0 in its field = first instance of that edge
                         const uint32_t was = (p_old >> p_shf) & 0xFFFFu;
                         my_new += won + (was == 0 ? 0x10000u : 0u);
-                        if (check16 && was + p_mult > 0xFFFFu) atomicOr(&fresh_args2(argp)->out.scalars[0], 512ull);
+                        if (check16 && was + p_mult > 0xFFFFu) atomicOr(&fresh_args2(argp)->out.scalars[0], STATUS_COUNTER16);
                     }
                     const bool good = act && ok;
                     const uint32_t nxt = from_next_lane(good ? slot : 0xFFFFu, 0xFFFFu);
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(1024) void k_sk_count3(const SkCount2Args *__restri
                 {   // the last iteration's add
                     const uint32_t was = (p_old >> p_shf) & 0xFFFFu;
                     my_new += was == 0 ? 0x10000u : 0u;
-                    if (check16 && was + p_mult > 0xFFFFu) atomicOr(&fresh_args2(argp)->out.scalars[0], 512ull);
+                    if (check16 && was + p_mult > 0xFFFFu) atomicOr(&fresh_args2(argp)->out.scalars[0], STATUS_COUNTER16);
                 }
             }
             {
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(1024) void k_sk_count3(const SkCount2Args *__restri
             if (over) {  // split this hash sub-range in two and retry (nothing was written out)
                 const uint32_t bit = cur_mask + 1;
                 if (stk_n + 2 > CNT_STACK || bit >= (1u << 20)) {
-                    if (threadIdx.x == 0) atomicOr(&fresh_args2(argp)->out.scalars[0], 8ull);
+                    if (threadIdx.x == 0) atomicOr(&fresh_args2(argp)->out.scalars[0], STATUS_BUCKET_TOO_BIG);
                     failed = true;
                     break;
                 }
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(1024) void k_sk_count3(const SkCount2Args *__restri
             __syncthreads();
             CNT_TICK(10);
             if (s.n_local != n_new) {  // uniform: the insert and the list phase disagree about this bucket
-                if (threadIdx.x == 0) atomicOr(&fresh_args2(argp)->out.scalars[0], 2048ull);
+                if (threadIdx.x == 0) atomicOr(&fresh_args2(argp)->out.scalars[0], STATUS_INCONSISTENT);
                 failed = true;
                 break;
             }
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(1024) void k_sk_count3(const SkCount2Args *__restri
                     s.qs_col[qi] = (uint32_t)e;
                 } else {
                     const unsigned long long g = atomicAdd(&ow.scalars[SK2_QUERY_CURSOR], 1ull);
-                    if (g >= ow.q_cap || g >= 0xFFFFFFF0ull) { atomicOr(&ow.scalars[0], 64ull); return; }
+                    if (g >= ow.q_cap || g >= 0xFFFFFFF0ull) { atomicOr(&ow.scalars[0], STATUS_QUERY_CAP); return; }
                     ow.q_key[g] = sk;
                     ow.q_col[g] = (uint32_t)e;
                 }
@@ -475,7 +475,7 @@ __global__ __launch_bounds__(1024) void k_sk_count3(const SkCount2Args *__restri
                         const unsigned long long g = g0 + lanes_below(md);
                         if (direct) {
                             if (g >= ow.q_cap || g >= 0xFFFFFFF0ull) {
-                                atomicOr(&ow.scalars[0], 64ull);
+                                atomicOr(&ow.scalars[0], STATUS_QUERY_CAP);
                             } else {
                                 ow.q_key[g] = sk;
                                 ow.q_col[g] = (uint32_t)e;

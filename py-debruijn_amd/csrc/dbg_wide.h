@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void k_wcount(const char *__restrict__ bases, 
     __shared__ TileLds t;
     const uint64_t tile0 = (uint64_t)blockIdx.x * TILE;
     const uint32_t bad = load_tile(t, bases, n_bytes, startbits, tile0);
-    if (bad) atomicOr(&scalars[0], 1ull);
+    if (bad) atomicOr(&scalars[0], STATUS_BAD_BASE);
     __syncthreads();
     uint64_t n_k = 0, n_e = 0;
     for (int j = threadIdx.x; j < TILE; j += 256) {
@@ -188,14 +188,14 @@ __global__ __launch_bounds__(256) void k_wcount(const char *__restrict__ bases, 
             }
             slot = wnext(slot, cap);
         }
-        if (!found) { atomicOr(&scalars[0], 2ull); continue; }  // table full
+        if (!found) { atomicOr(&scalars[0], STATUS_TABLE_FULL); continue; }  // table full
         if (explicit_edge != W_EMPTY && (explicit_edge & 4ull)) {
             const uint32_t nx = (uint32_t)(explicit_edge & 3ull);
             if (tcnt) {
                 atomicAdd(&tcnt[slot * 4 + nx], 1u);
             } else {  // four 16-bit counters in the slot's spare word: same sector as the probe, no second random access
                 const unsigned long long old = atomicAdd(&tab[slot].pad, 1ull << (16 * nx));
-                if (((old >> (16 * nx)) & 0xFFFFull) == 0xFFFFull) atomicOr(&scalars[0], 32ull);  // rebuild with 32-bit counters
+                if (((old >> (16 * nx)) & 0xFFFFull) == 0xFFFFull) atomicOr(&scalars[0], STATUS_WIDE_COUNTER16);  // rebuild with 32-bit counters
             }
         }
     }
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(256) void k_ws_extract(const char *__restrict__ bas
     __shared__ unsigned long long base[8];
     const uint64_t tile0 = (uint64_t)blockIdx.x * TILE;
     const uint32_t bad = load_tile(t, bases, n_bytes, startbits, tile0);
-    if (bad && !EMIT) atomicOr(&scalars[0], 1ull);
+    if (bad && !EMIT) atomicOr(&scalars[0], STATUS_BAD_BASE);
     if (threadIdx.x < 8) cnt[threadIdx.x] = 0;
     __syncthreads();
     uint32_t slot_of_round[TILE / 256];  // owner | rank << 3, 0xFFFFFFFF: no instance
@@ -481,7 +481,7 @@ __global__ __launch_bounds__(256) void k_ws_insert(const uint64_t *__restrict__ 
         }
         slot = wnext(slot, cap);
     }
-    atomicOr(&scalars[0], 2ull);  // table full
+    atomicOr(&scalars[0], STATUS_TABLE_FULL);  // table full
 }
 
 // gathered graph: every node into a fresh table (keys are distinct: claim the first free slot); k_wsucc then resolves

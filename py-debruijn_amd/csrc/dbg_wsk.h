@@ -119,7 +119,7 @@ __global__ __launch_bounds__(WSK_NT) void k_wsk_extract(const char *__restrict__
         const uint64_t tile0 = tile * TILE;
         __syncthreads();
         const uint32_t bad = load_tile(s.t, bases, n_bytes, startbits, tile0);
-        if (bad) atomicOr(&scalars[0], 1ull);
+        if (bad) atomicOr(&scalars[0], STATUS_BAD_BASE);
         __syncthreads();
         for (int j = threadIdx.x; j < WSK_NH; j += WSK_NT)
             s.ma[j] = (mmer_hash16((uint32_t)(window32(s.t, j) >> (64 - 2 * m))) << 16) | (uint32_t)j;
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(WSK_NT) void k_wsk_extract(const char *__restrict__
             rec_st[o] = (ST)((p << 1) | (s0 ^ 1u));
         }
     }
-    if (overflow && threadIdx.x == 0) atomicOr(&scalars[0], 4ull);
+    if (overflow && threadIdx.x == 0) atomicOr(&scalars[0], STATUS_SEGMENT_FULL);
     n_k = wave_sum_u64(n_k);
     n_e = wave_sum_u64(n_e);
     __syncthreads();
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256, 2) void k_wsk_extract_w(const char *__restrict
         const uint64_t tile0 = tile * TILE;
         __syncthreads();
         const uint32_t bad = load_tile(s.t, bases, n_bytes, startbits, tile0);
-        if (bad) atomicOr(&scalars[0], 1ull);
+        if (bad) atomicOr(&scalars[0], STATUS_BAD_BASE);
         __syncthreads();
         // ---- register phase
         const uint64_t wv[4] = {window32(s.t, j0), window32(s.t, j0 + 32), window32(s.t, j0 + 64), 0};
@@ -412,7 +412,7 @@ __global__ __launch_bounds__(256, 2) void k_wsk_extract_w(const char *__restrict
             rec_st[o] = (ST)((p << 1) | (s0 ^ 1u));
         }
     }
-    if (overflow && threadIdx.x == 0) atomicOr(&scalars[0], 4ull);
+    if (overflow && threadIdx.x == 0) atomicOr(&scalars[0], STATUS_SEGMENT_FULL);
     n_k = wave_sum_u64(n_k);
     n_e = wave_sum_u64(n_e);
     __syncthreads();
@@ -772,7 +772,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count(const uint64_t *__restric
                         }
                         if ((cur & ~W_PEND) == key.hi) {  // this k-mer or one that shares its high word
                             if (cur & W_PEND) {
-                                if (++spins >= (1 << 16)) atomicOr(&wfresh_args(outp)->scalars[0], 1024ull);  // a claim that never completes: fail loudly
+                                if (++spins >= (1 << 16)) atomicOr(&wfresh_args(outp)->scalars[0], STATUS_CLAIM_STUCK);  // a claim that never completes: fail loudly
                                 continue;
                             }
                             if (wlds_load(&s.klo[slot]) == key.lo) { ok = true; break; }
@@ -787,7 +787,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count(const uint64_t *__restric
                             atomicAdd(&s.cnt2[slot * 2 + (b >> 1)], mult << shf);  // and nobody waits for the old value
                         } else {
                             const uint32_t old = atomicAdd(&s.cnt2[slot * 2 + (b >> 1)], mult << shf);
-                            if (((old >> shf) & 0xFFFFu) + mult > 0xFFFFu) atomicOr(&wfresh_args(outp)->scalars[0], 512ull);  // 16-bit counter overflow
+                            if (((old >> shf) & 0xFFFFu) + mult > 0xFFFFu) atomicOr(&wfresh_args(outp)->scalars[0], STATUS_COUNTER16);  // 16-bit counter overflow
                         }
                     }
                     atomicMin(&s.stamp[slot], stamp);
@@ -807,7 +807,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count(const uint64_t *__restric
             if (s.overflow) {  // split this hash sub-range in two and retry (nothing was written out)
                 const uint32_t bit = cur_mask + 1;
                 if (stk_n + 2 > CNT_STACK || bit >= (1u << 20)) {
-                    if (threadIdx.x == 0) atomicOr(&wfresh_args(outp)->scalars[0], 8ull);
+                    if (threadIdx.x == 0) atomicOr(&wfresh_args(outp)->scalars[0], STATUS_BUCKET_TOO_BIG);
                     failed = true;
                     break;
                 }
@@ -927,12 +927,12 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count(const uint64_t *__restric
                 const unsigned long long base = got & 0xFFFFFFFFull, eb = got >> 32;
                 s.gbase = base;
                 s.ebase = eb;
-                if (base + n_local > orr.node_cap || base + n_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], 16ull); s.fail = 1; }
-                if (eb + n_edges_local > orr.edge_cap || eb + n_edges_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], 16ull); s.fail = 1; }
+                if (base + n_local > orr.node_cap || base + n_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], STATUS_NODE_EDGE_CAP); s.fail = 1; }
+                if (eb + n_edges_local > orr.edge_cap || eb + n_edges_local > 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], STATUS_NODE_EDGE_CAP); s.fail = 1; }
                 uint64_t ri = bucket;
                 if (cur_mask) {
                     ri = orr.n_buckets + atomicAdd(&orr.scalars[6], 1ull);
-                    if (ri >= orr.range_cap || ri >= 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], 32ull); s.fail = 1; }
+                    if (ri >= orr.range_cap || ri >= 0xFFFFFFF0ull) { atomicOr(&orr.scalars[0], STATUS_RANGE_CAP); s.fail = 1; }
                 }
                 s.ri = ri;
                 if (!s.fail) {
@@ -1003,7 +1003,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count(const uint64_t *__restric
             const auto &oq = *wfresh_args(outp);
             if (threadIdx.x == 64 && nq) {
                 s.qbase = qgot;
-                if (qgot + nq > oq.q_cap || qgot + nq > 0xFFFFFFF0ull) { atomicOr(&oq.scalars[0], 64ull); s.fail = 1; }
+                if (qgot + nq > oq.q_cap || qgot + nq > 0xFFFFFFF0ull) { atomicOr(&oq.scalars[0], STATUS_QUERY_CAP); s.fail = 1; }
             }
             __syncthreads();
             CNT_TICK(12);
@@ -1120,7 +1120,7 @@ __global__ __launch_bounds__(256) void k_wsucc_resolve(const uint64_t *__restric
             if (have) id = wdir_find(dirs, g.own_cnt + (ri - n_buckets), keys, keys_hi, n_nodes, key);
         }
     }
-    if (id == NO_NODE) { atomicOr(&scalars[0], 128ull); return; }  // every successor k-mer exists as a node of its owner
+    if (id == NO_NODE) { atomicOr(&scalars[0], STATUS_SUCC_MISSING); return; }  // every successor k-mer exists as a node of its owner
     out[q_col ? q_col[i] : i] = id | id_tag;
 }
 

@@ -142,7 +142,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
                                       __builtin_amdgcn_readfirstlane((uint32_t)fl_got);
         const uint32_t at = (wave - (uint32_t)(WCNT_NT / 64 - FLW)) * 64 + lane;
         if (qb + fl_cnt > oq.q_cap || qb + fl_cnt > 0xFFFFFFF0ull) {
-            if (lane == 0) { atomicOr(&oq.scalars[0], 64ull); s.fail = 1; }
+            if (lane == 0) { atomicOr(&oq.scalars[0], STATUS_QUERY_CAP); s.fail = 1; }
         } else if (lane < fl_cnt) {
             oq.q_lo[qb + lane] = s.q_lo[at];
             oq.q_hi[qb + lane] = s.q_hi[at];
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
                             }
                             if ((cur & ~W_PEND) == key.hi) {  // this k-mer or one that shares its high word
                                 if (cur & W_PEND) {
-                                    if (++spins >= (1 << 16)) atomicOr(&wfresh_args(outp)->scalars[0], 1024ull);  // a claim that never completes: fail loudly
+                                    if (++spins >= (1 << 16)) atomicOr(&wfresh_args(outp)->scalars[0], STATUS_CLAIM_STUCK);  // a claim that never completes: fail loudly
                                     continue;
                                 }
                                 if (wlds_load(&s.klo[slot]) == key.lo) { ok = true; break; }
@@ -334,7 +334,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
                     {
                         const uint32_t was = (p_old >> p_shf) & 0xFFFFu;
                         my_new += won + (was == 0 ? 0x10000u : 0u);
-                        if (!small_bucket && was + p_mult > 0xFFFFu) atomicOr(&wfresh_args(outp)->scalars[0], 512ull);  // 16-bit counter overflow
+                        if (!small_bucket && was + p_mult > 0xFFFFu) atomicOr(&wfresh_args(outp)->scalars[0], STATUS_COUNTER16);  // 16-bit counter overflow
                     }
                     const bool good = act && ok;
                     const uint32_t nxt = from_next_lane(good ? slot : 0xFFFFu, 0xFFFFu);
@@ -352,7 +352,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
                 {   // the last iteration's add
                     const uint32_t was = (p_old >> p_shf) & 0xFFFFu;
                     my_new += was == 0 ? 0x10000u : 0u;
-                    if (!small_bucket && was + p_mult > 0xFFFFu) atomicOr(&wfresh_args(outp)->scalars[0], 512ull);
+                    if (!small_bucket && was + p_mult > 0xFFFFu) atomicOr(&wfresh_args(outp)->scalars[0], STATUS_COUNTER16);
                 }
 #ifdef DBG_CNT_PROF
 #if DBG_CNT_PROF == 1
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
             if (over) {  // split this hash sub-range in two and retry (nothing was written out)
                 const uint32_t bit = cur_mask + 1;
                 if (stk_n + 2 > CNT_STACK || bit >= (1u << 20)) {
-                    if (threadIdx.x == 0) atomicOr(&wfresh_args(outp)->scalars[0], 8ull);
+                    if (threadIdx.x == 0) atomicOr(&wfresh_args(outp)->scalars[0], STATUS_BUCKET_TOO_BIG);
                     failed = true;
                     break;
                 }
@@ -403,7 +403,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
             __syncthreads();
             CNT_TICK(10);
             if (s.n_local != n_new) {  // uniform: the insert and the list phase disagree about this bucket
-                if (threadIdx.x == 0) atomicOr(&wfresh_args(outp)->scalars[0], 2048ull);
+                if (threadIdx.x == 0) atomicOr(&wfresh_args(outp)->scalars[0], STATUS_INCONSISTENT);
                 failed = true;
                 break;
             }
@@ -437,7 +437,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
                     s.q_col[qi] = (uint32_t)e;
                 } else {  // rare: past the staging, one by one
                     const unsigned long long g = atomicAdd(&ow.scalars[5], 1ull);
-                    if (g >= ow.q_cap || g >= 0xFFFFFFF0ull) { atomicOr(&ow.scalars[0], 64ull); return; }
+                    if (g >= ow.q_cap || g >= 0xFFFFFFF0ull) { atomicOr(&ow.scalars[0], STATUS_QUERY_CAP); return; }
                     ow.q_lo[g] = sk.lo;
                     ow.q_hi[g] = sk.hi;
                     ow.q_col[g] = (uint32_t)e;
@@ -553,7 +553,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
                         const unsigned long long g = g0 + lanes_below(md);
                         if (direct) {
                             if (g >= ow.q_cap || g >= 0xFFFFFFF0ull) {
-                                atomicOr(&ow.scalars[0], 64ull);
+                                atomicOr(&ow.scalars[0], STATUS_QUERY_CAP);
                             } else {
                                 ow.q_lo[g] = sk.lo;
                                 ow.q_hi[g] = sk.hi;

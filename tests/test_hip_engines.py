@@ -4,6 +4,10 @@ engine 0: super-k-mer partitioned build (default); engine 1: single global hash 
 Bucket geometries are forced so that the one- and two-level multisplit paths and the LDS
 overflow split (a bucket that does not fit the table) are all exercised at test sizes.
 """
+import functools
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -388,3 +392,68 @@ def test_both_count_kernels_write_the_same_graph(opts):
     for x, y in zip(a[:5], b[:5]):
         assert np.array_equal(x, y)
     assert a[5] == b[5] and a[6] == b[6]
+
+
+# ---- the partition stage's geometry, pinned (tests/golden/aux_partition_geometry.json, recorded once on the commit before the
+#      one-word and the two-word engine came to share the stage): n_buckets and n_queries are deterministic, and so are the
+#      node and edge totals.  The graphs themselves are checked against the C oracle above and in test_multi_gpu / test_hip_multipass.
+GEOMETRY_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "aux_partition_geometry.json")
+with open(GEOMETRY_FILE) as fh:
+    GEOMETRY_ROWS = json.load(fh)["rows"]
+
+
+@functools.lru_cache(maxsize=2)
+def geometry_reads(n_reads):
+    return synth.reads_ascii(23, 20000, n_reads, 100, 0.01)
+
+
+def measure_geometry(row):
+    """What one row of the fixture records, measured: mode "build" (one graph), "shards" (the eight in-process shards of
+    test_multi_gpu's helper: per shard), "shards_plain" (the same without the senders' bucket counts: every shard runs level 1
+    itself and samples the first level-1 bucket it owns) or "multipass" (build_multipass(k, 2)).  The library reports a
+    multi-pass build's buckets and queries summed over the parts only, so those two are sums here and a swap of geometry
+    between the parts would show in the per-part node and edge counts alone."""
+    reads, k = geometry_reads(row["n_reads"]), row["k"]
+    if row["mode"] == "build":
+        g = build(reads, k, **row["opts"])
+        st, sz = g.stats(), g.sizes()
+        g.close()
+        return {"n_buckets": st["n_buckets"], "n_queries": st["n_queries"], "n_nodes": sz["n_nodes"], "n_edges": sz["n_edges"]}
+    if row["mode"] == "multipass":
+        g = _dbg.Graph()
+        g.set_reads(reads.reshape(-1), np.arange(0, reads.size + 1, reads.shape[1], dtype=np.uint64))
+        g.build_multipass(k, 2)
+        st, psz = g.stats(), [g.part_sizes(p) for p in range(2)]
+        g.close()
+        return {"n_buckets": st["n_buckets"], "n_queries": st["n_queries"], "n_nodes": [p["n_nodes"] for p in psz],
+                "n_edges": [p["n_edges"] for p in psz]}
+    import inproc_dist
+    import multi_gpu
+    per = reads.shape[0] // 8
+
+    class WithoutBucketCounts:  # multi_gpu.sharded_build then hands dbg_shard_build no sender_bucket_counts
+        def __init__(self, g):
+            self._g = g
+
+        def __getattr__(self, name):
+            if name == "shard_bucket_counts":
+                raise AttributeError(name)
+            return getattr(self._g, name)
+
+    def one(dist, rank):
+        mine = reads[rank * per:(rank + 1) * per]
+        g = _dbg.Graph(device=0)
+        g.set_reads(mine.reshape(-1), np.arange(0, mine.size + 1, mine.shape[1], dtype=np.uint64))
+        multi_gpu.sharded_build(WithoutBucketCounts(g) if row["mode"] == "shards_plain" else g, k, dist)
+        st, sz = g.stats(), g.sizes()
+        g.close()
+        return st["n_buckets"], st["n_queries"], sz["n_nodes"], sz["n_edges"]
+
+    got = inproc_dist.run_ranks(8, one)
+    return {name: [x[i] for x in got] for i, name in enumerate(("n_buckets", "n_queries", "n_nodes", "n_edges"))}
+
+
+@pytest.mark.parametrize("row", GEOMETRY_ROWS, ids=lambda r: "-".join([r["mode"], str(r["k"])] + [f"{a}{b}" for a, b in r["opts"].items()]))
+def test_partition_geometry_is_the_recorded_one(row):
+    want = {name: row[name] for name in ("n_buckets", "n_queries", "n_nodes", "n_edges")}
+    assert measure_geometry(row) == want
