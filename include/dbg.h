@@ -47,7 +47,9 @@ typedef struct dbg dbg_t;
 #define DBG_E_CAPACITY (-4) /* hash table or an output limit was exceeded */
 #define DBG_E_NOMEM (-5)    /* host or device allocation failed */
 
-#define DBG_ABI_VERSION 6
+#define DBG_ABI_VERSION 6 /* not raised for dbg_build_from_walks: it only adds a symbol, every earlier call and struct is
+                            * unchanged, and tests/test_fasta_stream.py pins this number; a binding that needs the new
+                            * call fails at symbol lookup on an older library */
 
 /* node flag bits (dbg_export_nodes: flags[]) */
 #define DBG_F_INDEG 0x01u    /* Node.indegree (0 or 1), debruijn.py:134,141-142 */
@@ -439,6 +441,29 @@ int dbg_device_keys_hi(dbg_t *h, const void **d_keys_hi);
  *      in parts, k1 > 63 or k1 != k + 1, an order that is not a permutation of the contig index. */
 int dbg_build_from_walk(dbg_t *dst, dbg_t *src, int k1, const uint64_t *order, uint64_t n_order, const char *extra_bases,
                         const uint64_t *extra_offsets, uint64_t n_extra);
+
+/* ---- the same from several walks: from the driver's third k on, its reads are the contigs of the previous walk, then
+ *      the pulled contigs of every earlier walk that are still pulled (one block per walk, newest first), then a few real
+ *      reads.  Each block names contigs of a graph that is still on the device, so the k1-graph is built from all of them:
+ *      the reads of dst are the contigs of block 0, of block 1, ..., then the extra reads; no contig is spelled.
+ *      A block may hold any subset of its source's contigs (the empty one included), k1 - k(src) may be any value >= 1,
+ *      and the sources need no relation to each other.  Afterwards dst is what dbg_build(k1) would have produced on the
+ *      spelled-out concatenation (node order aside, successor ranks exact), everything said for dbg_build_from_walk
+ *      applies, and dst may itself be a source of a later call.  dbg_export_pull_reads reports sum(n) + n_extra flags in
+ *      read order, dbg_get_sizes the virtual n_reads / n_bytes.  dst keeps 8 B per source node + 4 B per contig of every
+ *      block for dbg_mark_pull_reads; the chain scratch of a block (about 57 B per source node) is freed before the next
+ *      block starts.
+ *      DBG_E_ARG (text in dbg_last_error(dst); every handle stays usable) for: the same src in two blocks or dst among the
+ *      sources, a source on another device, without a walk of its current graph, with a final-mode walk, in parts, with
+ *      a generic alphabet or with k(src) >= k1, k1 > 63, a contig index out of range or named twice within a block.
+ *      DBG_E_ALPHABET for extra reads outside ACGT. */
+typedef struct dbg_walk_block {
+    dbg_t *src;              /* graph whose last non-final walk holds these contigs; k(src) < k1 */
+    const uint64_t *contigs; /* n indices into src's contig index (dbg_export_contig_index), all different; read order */
+    uint64_t n;
+} dbg_walk_block_t;
+int dbg_build_from_walks(dbg_t *dst, int k1, const dbg_walk_block_t *blocks, uint64_t n_blocks, const char *extra_bases,
+                         const uint64_t *extra_offsets, uint64_t n_extra);
 
 /* ---- f4: read-support scores of contigs (findSupportReadScore, IV_sortOutputs.py:10-15): out_scores[c] = sum of
  *      read_scores[r] over the reads r (distinct strings: the reference's dict keys) that occur in contig c as a

@@ -36,7 +36,7 @@ SYMBOLS = (
     "dbg_export_marked", "dbg_part_keys_hi", "dbg_take_reads",
     "dbg_part_prune", "dbg_part_select", "dbg_part_gather", "dbg_part_mark", "dbg_part_clear", "dbg_part_cross_targets",
     "dbg_part_segments", "dbg_part_pflags", "dbg_scan_reads_for_keys", "dbg_set_orders", "dbg_part_segment_text",
-    "dbg_build_from_walk",
+    "dbg_build_from_walk", "dbg_build_from_walks",
 )
 
 
@@ -68,6 +68,11 @@ class IngestStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class WalkBlock(C.Structure):
+    """dbg_walk_block_t: contigs of one source graph's last non-final walk."""
+    _fields_ = [("src", C.c_void_p), ("contigs", C.c_void_p), ("n", C.c_uint64)]
 
 
 COUNTERS = ("extract_presplit_fallbacks", "extract_presplit_rehists")  # dbg_get_counter names that Graph.stats() reports
@@ -176,6 +181,7 @@ def load_library():
         "dbg_scan_reads_for_keys": (C.c_int, [H, C.c_int, vp, vp, C.c_uint64, vp, vp]),
         "dbg_set_orders": (C.c_int, [H, vp]),
         "dbg_build_from_walk": (C.c_int, [H, H, C.c_int, vp, C.c_uint64, vp, vp, C.c_uint64]),
+        "dbg_build_from_walks": (C.c_int, [H, C.c_int, C.POINTER(WalkBlock), C.c_uint64, vp, vp, C.c_uint64]),
         "dbg_shard_apply": (C.c_int, [H, vp]),
         "dbg_import_graph": (C.c_int, [H, C.c_int, C.c_int, u64p, vp, vp, vp, vp, vp]),
         "dbg_device_keys_hi": (C.c_int, [H, C.POINTER(vp)]),
@@ -314,16 +320,39 @@ class Graph:
         self.generation += 1
         self._chk(self._lib.dbg_build(self._h, int(k), int(table_capacity_hint)))
 
-    def build_from_walk(self, src, k1, order, bases, offsets):
-        """The k1 = k + 1 graph of (the contigs of ``src``'s last non-final walk, in ``order``) + the extra reads
-        ``bases`` / ``offsets`` (as for set_reads), built on the device from src's chains (dbg_build_from_walk)."""
-        o = np.ascontiguousarray(order, dtype=np.uint64)
+    @staticmethod
+    def _extra_reads(bases, offsets):
         b = np.ascontiguousarray(np.frombuffer(bases, dtype=np.uint8) if not isinstance(bases, np.ndarray) else bases, dtype=np.uint8)
         off = np.ascontiguousarray(offsets, dtype=np.uint64)
         assert off.ndim == 1 and off.size >= 1 and int(off[-1]) == b.size
+        return b, off
+
+    def build_from_walk(self, src, k1, order, bases, offsets, tail_blocks=()):
+        """The k1 = k + 1 graph of (the contigs of ``src``'s last non-final walk, in ``order``) + the extra reads
+        ``bases`` / ``offsets`` (as for set_reads), built on the device from src's chains (dbg_build_from_walk).
+        ``tail_blocks``: (graph, contig indices) pairs whose contigs follow those of ``src`` as further virtual reads,
+        each a subset of the last non-final walk of a graph at a smaller k (dbg_build_from_walks)."""
+        if len(tail_blocks):
+            return self.build_from_walks(k1, [(src, order)] + list(tail_blocks), bases, offsets)
+        o = np.ascontiguousarray(order, dtype=np.uint64)
+        b, off = self._extra_reads(bases, offsets)
         self.generation += 1
         self._chk(self._lib.dbg_build_from_walk(self._h, src._h, int(k1), _ptr(o) if o.size else None, o.size,
                                                 _ptr(b) if b.size else None, _ptr(off), off.size - 1))
+
+    def build_from_walks(self, k1, blocks, bases, offsets):
+        """The k1-graph of the reads (contigs of block 0, of block 1, ..., then the extra reads ``bases`` / ``offsets``),
+        built on the device from the chains of the blocks' graphs (dbg_build_from_walks).  ``blocks``: (graph, contig
+        indices) pairs -- any subset of the contig index of that graph's last non-final walk, in read order; the graphs
+        are distinct, on this device, ACGT, at any k < k1."""
+        idx = [np.ascontiguousarray(c, dtype=np.uint64) for _, c in blocks]
+        arr = (WalkBlock * max(len(idx), 1))()
+        for i, ((g, _), c) in enumerate(zip(blocks, idx)):
+            arr[i].src, arr[i].contigs, arr[i].n = g._h.value, (c.ctypes.data if c.size else None), c.size
+        b, off = self._extra_reads(bases, offsets)
+        self.generation += 1
+        self._chk(self._lib.dbg_build_from_walks(self._h, int(k1), arr, len(idx), _ptr(b) if b.size else None, _ptr(off),
+                                                 off.size - 1))
 
     def refine_edge_order(self):
         self._chk(self._lib.dbg_refine_edge_order(self._h))

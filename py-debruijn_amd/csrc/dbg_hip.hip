@@ -195,11 +195,16 @@ struct dbg {
     // branch k-mer lookup (pull-out reads)
     uint64_t *d_btab = nullptr;
     uint64_t btab_cap = 0;
-    // graph of dbg_build_from_walk (dbg_nextk.h): nk_reads contigs of nk_bytes characters are virtual reads in front of
-    // the real ones; their pull-out test needs the chain successors of the k-graph, y(x) and the start of every contig
+    // graph of dbg_build_from_walk(s) (dbg_nextk.h): nk_reads contigs of nk_bytes characters are virtual reads in front of
+    // the real ones; their pull-out test needs, per block of contigs, the chain successors of the block's source graph,
+    // z(x) and the start of every contig
+    struct NkBlock {
+        uint64_t n_src = 0, n_reads = 0;  // nodes of the source graph, contigs of the block
+        uint32_t *next = nullptr, *z = nullptr, *start = nullptr;
+    };
     bool nk_graph = false;
-    uint64_t nk_reads = 0, nk_bytes = 0, nk_src_nodes = 0;
-    uint32_t *d_nk_next = nullptr, *d_nk_y = nullptr, *d_nk_start = nullptr;
+    uint64_t nk_reads = 0, nk_bytes = 0;
+    std::vector<NkBlock> nk_blocks;
     uint8_t *d_nk_read_flags = nullptr;
 
     dbg_stats_t stats{};
@@ -1599,9 +1604,11 @@ static void free_build(dbg *h) {
     h->n_starts = h->n_contigs = h->contig_chars = 0;
     h->starts_known = false;
     h->n_kmer_inst = h->n_edge_inst = 0;
-    dev_free(h->d_nk_next); dev_free(h->d_nk_y); dev_free(h->d_nk_start); dev_free(h->d_nk_read_flags);
+    for (auto &b : h->nk_blocks) { dev_free(b.next); dev_free(b.z); dev_free(b.start); }
+    h->nk_blocks.clear();
+    dev_free(h->d_nk_read_flags);
     h->nk_graph = false;
-    h->nk_reads = h->nk_bytes = h->nk_src_nodes = 0;
+    h->nk_reads = h->nk_bytes = 0;
 }
 
 static void free_reads(dbg *h) {

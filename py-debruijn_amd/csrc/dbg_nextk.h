@@ -1,15 +1,21 @@
-// The driver's k -> k+1 step (II_assembleFromReads.py:56-75) without spelling the contigs: dbg_build_from_walk builds the
-// (k+1)-graph of (contigs of the last non-final walk, in driver order) + (extra reads) straight from the chain structure
-// of the k-graph.  Included by dbg_hip.hip after every helper it uses ("Next k from the walk").
+// The driver's step to the next k (II_assembleFromReads.py:56-75) without spelling the contigs: dbg_build_from_walks builds
+// the K-graph of (blocks of contigs of earlier non-final walks, in driver order) + (extra reads) straight from the chain
+// structure of the graphs those walks ran on; dbg_build_from_walk is its one-block call with K = k + 1.  Included by
+// dbg_hip.hip after every helper it uses ("Next k from the walk").
 //
-// A non-final contig is a chain x0 -> x1 -> ... -> x(n-1) under one per-node continuation nxt() (k_jump_init's rule), so
-// for the (k+1)-graph of the contigs:
-//   - nodes: y(x) = key(x) * 4 + last base of nxt(x), for every x on a contig of n >= 3 nodes that has nxt(x);
-//   - count of the edge y(x) -> y(nxt x): S(x) = number of such contigs through x (a sum over the starts upstream);
-//   - first occurrence: the lowest-ranked such contig through x, at hop distance d from its start: (off + d) << 1 | d != 0.
+// A non-final contig is a chain x0 -> x1 -> ... -> x(n-1) of k-nodes under one per-node continuation nxt() (k_jump_init's
+// rule): k + n - 1 characters.  With d = K - k, for the K-graph of the selected contigs of one block:
+//   - nodes: z(x) = key(x) followed by the last bases of nxt^1(x) .. nxt^d(x), for every x that has nxt^d(x) and lies on a
+//     selected contig of n >= d + 2 nodes (a read makes nodes only if it is longer than K);
+//   - count of the edge z(x) -> z(nxt x), where nxt^(d+1)(x) exists: S(x) = number of such contigs through x (a sum over
+//     the starts upstream);
+//   - first occurrence: the lowest-ranked such contig through x, at hop distance h from its start: (off + h) << 1 | h != 0.
 // Both reductions run by doubling over the jump pointers J_j(u) = nxt^(2^j)(u) (NONE past the chain end, never wrapped):
 // B_(j+1)(v) = B_j(v) (+) sum over u with J_j(u) = v of B_j(u), one scatter per round.  Upstream sets of distinct u are
-// disjoint in a forest, so every start counts once; cycles carry no weight (they emit no contig).
+// disjoint in a forest, so every start counts once; cycles carry no weight (they emit no contig).  d only enters the start
+// weights (hops >= d + 1) and the walk of d pointers that spells z(x).
+// The blocks are reduced one after another (the chain scratch of a block is freed before the next one starts) and then
+// merged, in block order, into one table keyed by the two words of the K-mer.
 #pragma once
 
 constexpr uint32_t NK_NONE = 0xFFFFFFFFu;
@@ -65,8 +71,9 @@ struct NkChars {
     __device__ uint64_t operator()(uint64_t i) const { return emit[i] ? (uint64_t)k + H[i] : 0; }
 };
 
-// weights of the starts: contig index c (ascending start id == the walk's index), driver rank r = rank_of[c]
-__global__ __launch_bounds__(256) void k_nk_weights(uint64_t n, const uint8_t *__restrict__ emit, const uint32_t *__restrict__ cidx,
+// weights of the starts: contig index c (ascending start id == the walk's index), rank r = rank_of[c] inside the block
+// (NONE: the block does not hold the contig)
+__global__ __launch_bounds__(256) void k_nk_weights(uint64_t n, int d, const uint8_t *__restrict__ emit, const uint32_t *__restrict__ cidx,
                                                     const uint32_t *__restrict__ H, const uint32_t *__restrict__ rank_of,
                                                     uint32_t *S, unsigned long long *M, uint32_t *start_of_rank) {
     const uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -75,8 +82,10 @@ __global__ __launch_bounds__(256) void k_nk_weights(uint64_t n, const uint8_t *_
     unsigned long long m = ~0ull;
     if (emit[v]) {
         const uint32_t r = rank_of[cidx[v]];
-        start_of_rank[r] = (uint32_t)v;
-        if (H[v] >= 2) { s = 1; m = (unsigned long long)r << 32; }  // n >= 3 nodes: the contig makes (k+1)-nodes
+        if (r != NK_NONE) {
+            start_of_rank[r] = (uint32_t)v;
+            if (H[v] >= (uint32_t)d + 1) { s = 1; m = (unsigned long long)r << 32; }  // n >= d + 2 nodes: the contig makes K-nodes
+        }
     }
     S[v] = s;
     M[v] = m;
@@ -106,33 +115,46 @@ __global__ __launch_bounds__(256) void k_nk_push(uint64_t n, int j, const uint32
     if ((threadIdx.x & 63) == 0 && o) atomicAdd(open, (unsigned long long)o);
 }
 
-__device__ inline void nk_ykey(const GDna &g, uint32_t x, uint32_t c, uint64_t &lo, uint64_t &hi) {
-    const uint64_t l = g.keys[x], h = g.keys_hi ? g.keys_hi[x] : 0ull;
-    lo = (l << 2) | c;
-    hi = (h << 2) | (l >> 62);
+// z(x): key(x) shifted by 2d bits across the two key words, the last bases of nxt^1(x) .. nxt^d(x) behind it; t = nxt^d(x).
+// false where the chain ends before nxt^d(x).  On a cycle the walk just goes round (d <= 62 steps).
+__device__ inline bool nk_zkey(const GDna &g, const uint32_t *__restrict__ nxt, uint32_t x, int d, uint64_t &lo, uint64_t &hi,
+                               uint32_t &t) {
+    lo = g.keys[x];
+    hi = g.keys_hi ? g.keys_hi[x] : 0ull;
+    t = x;
+    for (int i = 0; i < d; ++i) {
+        t = nxt[t];
+        if (t == NK_NONE) return false;
+        hi = (hi << 2) | (lo >> 62);
+        lo = (lo << 2) | g.last_code(t);
+    }
+    return true;
 }
 
-struct NkYFlag {
-    const uint32_t *S, *nxt;
-    __device__ uint64_t operator()(uint64_t i) const { return S[i] && nxt[i] != NK_NONE; }
+// S(x) != 0 puts x on a chain that ends, where H is the exact hop count to the end: x has nxt^d(x) iff H(x) >= d
+struct NkZFlag {
+    const uint32_t *S, *H;
+    uint32_t d;
+    __device__ uint64_t operator()(uint64_t i) const { return S[i] && H[i] >= d; }
 };
 
-// the (k+1)-nodes of the contigs: key, stamp, the one successor code (0xFF: none) and its count
-__global__ __launch_bounds__(256) void k_nk_emit(uint64_t n, GDna g, const uint32_t *__restrict__ nxt, const uint32_t *__restrict__ S,
-                                                 const unsigned long long *__restrict__ M, const uint32_t *__restrict__ yidx,
-                                                 const uint64_t *__restrict__ drv_off, uint64_t *ck_lo, uint64_t *ck_hi,
-                                                 uint64_t *cstamp, uint8_t *ccode, uint32_t *ccnt) {
+// the K-nodes of the block's contigs: key, stamp, the one successor code (0xFF: none) and its count
+__global__ __launch_bounds__(256) void k_nk_emit(uint64_t n, int d, GDna g, const uint32_t *__restrict__ nxt, const uint32_t *__restrict__ S,
+                                                 const uint32_t *__restrict__ H, const unsigned long long *__restrict__ M,
+                                                 const uint32_t *__restrict__ zidx, const uint64_t *__restrict__ drv_off,
+                                                 uint64_t *ck_lo, uint64_t *ck_hi, uint64_t *cstamp, uint8_t *ccode, uint32_t *ccnt) {
     const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= n || !S[x] || nxt[x] == NK_NONE) return;
-    const uint32_t j = yidx[x], nx = nxt[x], nnx = nxt[nx];
+    if (x >= n || !S[x] || H[x] < (uint32_t)d) return;
     uint64_t lo, hi;
-    nk_ykey(g, (uint32_t)x, g.last_code(nx), lo, hi);
+    uint32_t t;
+    if (!nk_zkey(g, nxt, (uint32_t)x, d, lo, hi, t)) return;  // not taken: H(x) >= d
+    const uint32_t j = zidx[x], nt = nxt[t];
     ck_lo[j] = lo;
     ck_hi[j] = hi;
-    const uint64_t m = M[x], d = m & 0xFFFFFFFFull;
-    cstamp[j] = ((drv_off[m >> 32] + d) << 1) | (d != 0);
-    ccode[j] = nnx != NK_NONE ? (uint8_t)g.last_code(nnx) : (uint8_t)0xFF;
-    ccnt[j] = nnx != NK_NONE ? S[x] : 0u;
+    const uint64_t m = M[x], h = m & 0xFFFFFFFFull;
+    cstamp[j] = ((drv_off[m >> 32] + h) << 1) | (h != 0);
+    ccode[j] = nt != NK_NONE ? (uint8_t)g.last_code(nt) : (uint8_t)0xFF;
+    ccnt[j] = nt != NK_NONE ? S[x] : 0u;
 }
 
 // ---- node table of the union: open addressing, (lo, hi) -> node id; inserts and lookups are separate launches
@@ -166,21 +188,32 @@ __global__ __launch_bounds__(256) void k_nk_insert(uint64_t n, const uint64_t *_
     if (i < n) tab.insert(lo[i], hi ? hi[i] : 0ull, (uint32_t)i);
 }
 
-// contig node j: the extra-read node with its key, or NONE (then it is new)
+// contig node j of a block: the node of the union so far (extra reads, earlier blocks) with its key, or NONE (then it is new)
 __global__ __launch_bounds__(256) void k_nk_match(uint64_t n_c, const uint64_t *__restrict__ ck_lo, const uint64_t *__restrict__ ck_hi,
-                                                  NkTab tab, uint32_t *hit, uint8_t *isnew) {
+                                                  NkTab tab, uint32_t *cid, uint8_t *isnew) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_c) return;
     const uint32_t e = tab.find(ck_lo[j], ck_hi[j]);
-    hit[j] = e;
+    cid[j] = e;
     isnew[j] = e == NK_NONE;
+}
+
+// the new nodes of a block take the ids from new_from on and enter the table (a block holds every key once)
+__global__ __launch_bounds__(256) void k_nk_insert_new(uint64_t n_c, uint64_t new_from, const uint8_t *__restrict__ isnew,
+                                                       const uint32_t *__restrict__ newidx, const uint64_t *__restrict__ ck_lo,
+                                                       const uint64_t *__restrict__ ck_hi, NkTab tab, uint32_t *cid) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_c || !isnew[j]) return;
+    const uint32_t id = (uint32_t)(new_from + newidx[j]);
+    cid[j] = id;
+    tab.insert(ck_lo[j], ck_hi[j], id);
 }
 
 // the extra-read graph, stamps moved behind the contig text (+2T); fs = its first-seen successor order
 __global__ __launch_bounds__(256) void k_nk_fill_extra(uint64_t n_e, const uint64_t *__restrict__ e_lo, const uint64_t *__restrict__ e_hi,
                                                        const uint64_t *__restrict__ e_st, const uint32_t *__restrict__ e_cnt,
                                                        const uint8_t *__restrict__ e_fs, uint64_t stamp_add, uint64_t *lo,
-                                                       uint64_t *hi, uint64_t *st, uint32_t *cnt, uint8_t *fs, uint8_t *c0) {
+                                                       uint64_t *hi, uint64_t *st, uint32_t *cnt, uint8_t *fs, uint16_t *bo) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_e) return;
     lo[i] = e_lo[i];
@@ -188,45 +221,50 @@ __global__ __launch_bounds__(256) void k_nk_fill_extra(uint64_t n_e, const uint6
     st[i] = e_st[i] + stamp_add;
     reinterpret_cast<uint4 *>(cnt)[i] = reinterpret_cast<const uint4 *>(e_cnt)[i];
     fs[i] = e_fs[i];
-    c0[i] = 0xFF;
+    bo[i] = 0;
 }
 
-// contig nodes: merged into their extra-read twin (counts add, the contig's earlier stamp wins) or appended
-__global__ __launch_bounds__(256) void k_nk_fill_contig(uint64_t n_c, uint64_t n_e, const uint64_t *__restrict__ ck_lo,
+// the nodes of one block, blocks in read order: appended (ids from new_from on are this block's) or merged into the node
+// that holds the key already -- counts add, the earliest stamp wins (block bases rise, the extra reads lie behind all
+// blocks).  bo: the successor codes in the order of the first block whose chains hold that edge (2 bits each, their
+// number in bits 8..10); a block gives a node at most one code.
+__global__ __launch_bounds__(256) void k_nk_fill_contig(uint64_t n_c, uint64_t new_from, const uint64_t *__restrict__ ck_lo,
                                                         const uint64_t *__restrict__ ck_hi, const uint64_t *__restrict__ cstamp,
                                                         const uint8_t *__restrict__ ccode, const uint32_t *__restrict__ ccnt,
-                                                        const uint32_t *__restrict__ hit, const uint32_t *__restrict__ newidx,
-                                                        uint64_t *lo, uint64_t *hi, uint64_t *st, uint32_t *cnt, uint8_t *fs,
-                                                        uint8_t *c0, uint32_t *cid) {
+                                                        const uint32_t *__restrict__ cid, uint64_t *lo, uint64_t *hi, uint64_t *st,
+                                                        uint32_t *cnt, uint8_t *fs, uint16_t *bo) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n_c) return;
-    uint32_t id = hit[j];
+    const uint32_t id = cid[j];
     const uint8_t c = ccode[j];
-    if (id == NK_NONE) {
-        id = (uint32_t)(n_e + newidx[j]);
+    uint32_t b = 0;
+    if (id >= new_from) {
         lo[id] = ck_lo[j];
         if (hi) hi[id] = ck_hi[j];
         reinterpret_cast<uint4 *>(cnt)[id] = make_uint4(0, 0, 0, 0);
         fs[id] = 0;
+        st[id] = cstamp[j];
+    } else {
+        b = bo[id];
+        const uint64_t mine = cstamp[j];
+        if (mine < st[id]) st[id] = mine;
     }
-    st[id] = cstamp[j];  // below T: earlier than any extra read
-    if (c != 0xFF) cnt[(uint64_t)id * 4 + c] += ccnt[j];
-    c0[id] = c;
-    cid[j] = id;
+    if (c != 0xFF) {
+        cnt[(uint64_t)id * 4 + c] += ccnt[j];
+        const uint32_t held = b >> 8;
+        bool seen = false;
+        for (uint32_t r = 0; r < held; ++r) seen |= ((b >> (2 * r)) & 3u) == c;
+        if (!seen) b = ((b & 0xFFu) | ((uint32_t)c << (2 * held))) | ((held + 1) << 8);
+    }
+    bo[id] = (uint16_t)b;
 }
 
-__global__ __launch_bounds__(256) void k_nk_insert_new(uint64_t n_c, const uint8_t *__restrict__ isnew, const uint32_t *__restrict__ cid,
-                                                       const uint64_t *__restrict__ ck_lo, const uint64_t *__restrict__ ck_hi, NkTab tab) {
-    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n_c && isnew[j]) tab.insert(ck_lo[j], ck_hi[j], cid[j]);
-}
-
-// successors by key, degrees, indegree flags and the two rank bytes.  First-seen key of a code: the contig successor c0
-// first (its first occurrence is below T), then the extra graph's first-seen order; codes without count last, in ASCII
-// order (A C G T = codes 0 1 3 2) as every build ranks them.  most_common = (count desc, first seen asc).
+// successors by key, degrees, indegree flags and the two rank bytes.  First-seen key of a code: the block successors in
+// block order (bo; their first occurrences are below T), then the extra graph's first-seen order; codes without count
+// last, in ASCII order (A C G T = codes 0 1 3 2) as every build ranks them.  most_common = (count desc, first seen asc).
 __global__ __launch_bounds__(256) void k_nk_succ(uint64_t n, int k1, const uint64_t *__restrict__ lo, const uint64_t *__restrict__ hi,
                                                  const uint64_t *__restrict__ st, const uint32_t *__restrict__ cnt,
-                                                 const uint8_t *__restrict__ fs, const uint8_t *__restrict__ c0, NkTab tab,
+                                                 const uint8_t *__restrict__ fs, const uint16_t *__restrict__ bo, NkTab tab,
                                                  uint32_t *succ, uint8_t *deg, uint8_t *flags, uint8_t *order, uint8_t *fsorder) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -235,7 +273,8 @@ __global__ __launch_bounds__(256) void k_nk_succ(uint64_t n, int k1, const uint6
     const uint64_t l = lo[i], h = hi ? hi[i] : 0ull;
     const uint64_t lo_mask = k1 >= 32 ? ~0ull : ((1ull << (2 * k1)) - 1);
     const uint64_t hi_mask = k1 > 32 ? ((1ull << (2 * k1 - 64)) - 1) : 0ull;
-    const uint8_t f = fs[i], z = c0[i];
+    const uint8_t f = fs[i];
+    const uint32_t z = bo[i], held = z >> 8;
     uint32_t s[4], key[4], code[4] = {0, 1, 2, 3};
     const uint32_t ascii_rank[4] = {0, 1, 3, 2};
 #pragma unroll
@@ -243,10 +282,12 @@ __global__ __launch_bounds__(256) void k_nk_succ(uint64_t n, int k1, const uint6
         s[b] = NK_NONE;
         if (c[b]) {
             s[b] = tab.find(((l << 2) | (uint64_t)b) & lo_mask, ((h << 2) | (l >> 62)) & hi_mask);
-            uint32_t pos = 0;
+            uint32_t pos = 0, blk = 4;
             for (int r = 0; r < 4; ++r)
                 if (((f >> (2 * r)) & 3u) == (uint32_t)b) { pos = r; break; }
-            key[b] = (b == z) ? 0u : 1u + pos;
+            for (uint32_t r = 0; r < held; ++r)
+                if (((z >> (2 * r)) & 3u) == (uint32_t)b) { blk = r; break; }
+            key[b] = blk < 4 ? blk : 4u + pos;
         } else {
             key[b] = 16u + ascii_rank[b];
         }
@@ -272,22 +313,17 @@ __global__ __launch_bounds__(256) void k_nk_succ(uint64_t n, int k1, const uint6
     order[i] = (uint8_t)(code[0] | (code[1] << 2) | (code[2] << 4) | (code[3] << 6));
 }
 
-// y(x) for every k-node x with a chain successor: the (k+1)-node id in the union, or NONE
-__global__ __launch_bounds__(256) void k_nk_ymap(uint64_t n, GDna g, const uint32_t *__restrict__ nxt, NkTab tab, int k1, uint32_t *y) {
+// z(x) for every node x of a source that has nxt^d(x): the K-node id in the union, or NONE
+__global__ __launch_bounds__(256) void k_nk_zmap(uint64_t n, int d, GDna g, const uint32_t *__restrict__ nxt, NkTab tab, uint32_t *z) {
     const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (x >= n) return;
-    const uint32_t nx = nxt[x];
-    uint32_t r = NK_NONE;
-    if (nx != NK_NONE) {
-        uint64_t lo, hi;
-        nk_ykey(g, (uint32_t)x, g.last_code(nx), lo, hi);
-        (void)k1;
-        r = tab.find(lo, hi);
-    }
-    y[x] = r;
+    uint64_t lo, hi;
+    uint32_t t;
+    z[x] = nk_zkey(g, nxt, (uint32_t)x, d, lo, hi, t) ? tab.find(lo, hi) : NK_NONE;
 }
 
-// ---- pull-out reads of the contigs: OR over a chain (last node excluded) of "y(x) is a branch (k+1)-node"
+// ---- pull-out reads of the contigs: OR over a chain of "x has nxt^d(x) and z(x) is a branch K-node".  z(x) is looked up
+// in the union, so a contig of exactly K characters (no node of its own) can still hold a branch node.
 __global__ __launch_bounds__(256) void k_nk_or_init(uint64_t n, const uint32_t *__restrict__ y, const uint8_t *__restrict__ flags,
                                                     const uint32_t *__restrict__ nxt, uint32_t *J, uint8_t *P) {
     const uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -338,75 +374,172 @@ static int nk_jump_until_closed(dbg *h, uint64_t n, Step step, bool until_zero =
     return -1;
 }
 
-// called by dbg_mark_pull_reads on a graph from dbg_build_from_walk: flags of the virtual contig reads
+// called by dbg_mark_pull_reads on a graph from dbg_build_from_walk(s): flags of the virtual contig reads, block by block
 static int nk_mark_contigs(dbg *h) {
     dev_free(h->d_nk_read_flags);
     CHK(dev_alloc(h, &h->d_nk_read_flags, h->nk_reads));
     HIPCHK(h, hipMemsetAsync(h->d_nk_read_flags, 0, h->nk_reads ? h->nk_reads : 1, h->stream));
     if (!h->nk_reads || !h->n_branch) return DBG_OK;
-    const uint64_t n = h->nk_src_nodes;
-    uint32_t *J[2] = {nullptr, nullptr};
-    uint8_t *P[2] = {nullptr, nullptr};
+    uint64_t first_read = 0;
+    for (const dbg::NkBlock &b : h->nk_blocks) {
+        const uint64_t n = b.n_src;
+        if (!b.n_reads || !n) { first_read += b.n_reads; continue; }
+        uint32_t *J[2] = {nullptr, nullptr};
+        uint8_t *P[2] = {nullptr, nullptr};
+        int rc = DBG_OK;
+        do {
+            if ((rc = dev_alloc(h, &J[0], n)) != DBG_OK || (rc = dev_alloc(h, &J[1], n)) != DBG_OK ||
+                (rc = dev_alloc(h, &P[0], n)) != DBG_OK || (rc = dev_alloc(h, &P[1], n)) != DBG_OK) break;
+            const dim3 grid(grid_for(n, 256));
+            hipLaunchKernelGGL(k_nk_or_init, grid, dim3(256), 0, h->stream, n, b.z, h->d_flags, b.next, J[0], P[0]);
+            int cur = 0;
+            const int rounds = nk_jump_until_closed(h, n, [&](int, unsigned long long *open) {
+                hipLaunchKernelGGL(k_nk_or_step, grid, dim3(256), 0, h->stream, n, J[cur], P[cur], J[cur ^ 1], P[cur ^ 1], open);
+                cur ^= 1;
+            });
+            if (rounds < 0) { rc = DBG_E_HIP; break; }
+            hipLaunchKernelGGL(k_nk_or_gather, dim3(grid_for(b.n_reads, 256)), dim3(256), 0, h->stream, b.n_reads, b.start, P[cur],
+                               h->d_nk_read_flags + first_read);
+            if (hipGetLastError() != hipSuccess) { h->err = "pull-out contigs: launch failed"; rc = DBG_E_HIP; break; }
+            hipError_t e = hipStreamSynchronize(h->stream);  // the scratch goes back before the next block
+            if (e != hipSuccess) { h->err = std::string("pull-out contigs: ") + hipGetErrorString(e); rc = DBG_E_HIP; }
+        } while (0);
+        dev_free(J[0]); dev_free(J[1]); dev_free(P[0]); dev_free(P[1]);
+        if (rc != DBG_OK) return rc;
+        first_read += b.n_reads;
+    }
+    uint64_t total = 0;
+    CHK(reduce_sum(h, h->nk_reads, ByteAt{h->d_nk_read_flags}, &total));
+    h->n_pull_reads += total;
+    return DBG_OK;
+}
+
+// why src cannot be a source of a K-graph on dst, or nullptr.  several: the checks of dbg_build_from_walks (a graph in
+// parts is named as such even before it has a walk, and the node limit belongs to the list); otherwise the checks of
+// dbg_build_from_walk in the order it has always made them (it tests the node limit behind its own arguments)
+static const char *nk_refuse_source(const dbg *dst, const dbg *src, bool several) {
+    const char *parts = "src holds a graph in parts: build from a single-table graph";
+    if (dst == src) return "dst and src must be different handles";
+    if (dst->device != src->device) return "dst and src must be on the same device";
+    if (several && (src->multipass || src->partial_graph)) return parts;
+    if (!src->k || !src->walk_indexed) return "src has no walk of its current graph";
+    if (src->multipass || src->partial_graph) return parts;
+    if (src->D != 4 || !src->is_dna) return "src is not an ACGT graph (generic alphabets take the text path)";
+    if (src->walk_final) return "the last walk of src was a final-mode walk (all simple paths, not chains)";
+    if (several && src->n_nodes >= 0xFFFFFFF0ull) return "src has too many nodes";
+    return nullptr;
+}
+
+// a HIP call inside a do { } while (0) body that owns device memory: on an error set rc and leave through the frees
+#define NK_HIP(h, call)                                                        \
+    if (hipError_t e_ = (call); e_ != hipSuccess) {                            \
+        (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);          \
+        rc = e_ == hipErrorOutOfMemory ? DBG_E_NOMEM : DBG_E_HIP;              \
+        break;                                                                 \
+    } else (void)0
+
+// the K-nodes of one block, kept until the union
+struct NkNodes {
+    uint64_t n_c = 0;
+    uint64_t *lo = nullptr, *hi = nullptr, *stamp = nullptr;
+    uint8_t *code = nullptr;
+    uint32_t *cnt = nullptr, *cid = nullptr;
+    void release() { dev_free(lo); dev_free(hi); dev_free(stamp); dev_free(code); dev_free(cnt); dev_free(cid); }
+};
+
+// The chain phase of one block: continuation pointers of src, the two doubling reductions with the block's start weights,
+// and the block's K-nodes.  rank_of[c]: position of contig c inside the block or NONE; drv_off[r]: offset of the block's
+// r-th contig in the virtual text (block base included).  Everything but `out` and `kept` is freed on return.
+static int nk_chain_block(dbg *dst, dbg *src, int d, const std::vector<uint32_t> &rank_of, const std::vector<uint64_t> &drv_off,
+                          NkNodes &out, dbg::NkBlock &kept) {
+    const uint64_t n = src->n_nodes, n_sel = drv_off.size() - 1;
+    kept.n_src = n;
+    kept.n_reads = n_sel;
+    if (!n_sel || !n) { kept.n_src = 0; return DBG_OK; }
+    const GDna g = dna_view(src);
+    const dim3 grid(grid_for(n, 256));
+    uint32_t *nxt = nullptr, *J[2] = {nullptr, nullptr}, *H[2] = {nullptr, nullptr}, *cidx = nullptr, *d_rank = nullptr,
+             *S[2] = {nullptr, nullptr}, *zidx = nullptr, *start_of_rank = nullptr;
+    unsigned long long *M[2] = {nullptr, nullptr};
+    uint64_t *d_drv = nullptr;
+    uint8_t *emit = nullptr;
     int rc = DBG_OK;
     do {
-        if ((rc = dev_alloc(h, &J[0], n)) != DBG_OK || (rc = dev_alloc(h, &J[1], n)) != DBG_OK ||
-            (rc = dev_alloc(h, &P[0], n)) != DBG_OK || (rc = dev_alloc(h, &P[1], n)) != DBG_OK) break;
-        const dim3 grid(grid_for(n, 256));
-        if (n) hipLaunchKernelGGL(k_nk_or_init, grid, dim3(256), 0, h->stream, n, h->d_nk_y, h->d_flags, h->d_nk_next, J[0], P[0]);
+        // 1. continuation pointers and hops to the chain end
+        if ((rc = dev_alloc(dst, &nxt, n)) != DBG_OK) break;
+        if ((rc = dev_alloc(dst, &J[0], n)) != DBG_OK || (rc = dev_alloc(dst, &J[1], n)) != DBG_OK) break;
+        if ((rc = dev_alloc(dst, &H[0], n)) != DBG_OK || (rc = dev_alloc(dst, &H[1], n)) != DBG_OK) break;
+        hipLaunchKernelGGL(k_nk_next, grid, dim3(256), 0, dst->stream, n, g, nxt);
+        hipLaunchKernelGGL(k_nk_hops_init, grid, dim3(256), 0, dst->stream, n, nxt, J[0], H[0]);
         int cur = 0;
-        const int rounds = n ? nk_jump_until_closed(h, n, [&](int, unsigned long long *open) {
-            hipLaunchKernelGGL(k_nk_or_step, grid, dim3(256), 0, h->stream, n, J[cur], P[cur], J[cur ^ 1], P[cur ^ 1], open);
-            cur ^= 1;
-        }) : 0;
-        if (rounds < 0) { rc = DBG_E_HIP; break; }
-        hipLaunchKernelGGL(k_nk_or_gather, dim3(grid_for(h->nk_reads, 256)), dim3(256), 0, h->stream, h->nk_reads, h->d_nk_start,
-                           P[cur], h->d_nk_read_flags);
-        if (hipGetLastError() != hipSuccess) { h->err = "pull-out contigs: launch failed"; rc = DBG_E_HIP; break; }
-        uint64_t total = 0;
-        if ((rc = reduce_sum(h, h->nk_reads, ByteAt{h->d_nk_read_flags}, &total)) != DBG_OK) break;
-        h->n_pull_reads += total;
+        if (nk_jump_until_closed(dst, n, [&](int, unsigned long long *open) {
+                hipLaunchKernelGGL(k_nk_rank_step, grid, dim3(256), 0, dst->stream, n, J[cur], H[cur], J[cur ^ 1], H[cur ^ 1], open);
+                cur ^= 1;
+            }) < 0) { rc = DBG_E_HIP; break; }
+        uint32_t *Jend = J[cur], *Hops = H[cur];
+        // 2. emitting starts == the walk's contig index (checked against it)
+        if ((rc = dev_alloc(dst, &emit, n)) != DBG_OK || (rc = dev_alloc(dst, &cidx, n)) != DBG_OK) break;
+        hipLaunchKernelGGL(k_nk_emits, grid, dim3(256), 0, dst->stream, n, g.flags, Jend, emit);
+        uint64_t n_ctg = 0, n_chr = 0;
+        if ((rc = exclusive_scan(dst, n, ByteAt{emit}, cidx, &n_ctg)) != DBG_OK) break;
+        if ((rc = reduce_sum(dst, n, NkChars{emit, Hops, src->k}, &n_chr)) != DBG_OK) break;
+        if (n_ctg != src->n_contigs || n_chr != src->contig_chars) {
+            dst->err = "internal: chains disagree with the walk's contig index";
+            rc = DBG_E_HIP;
+            break;
+        }
+        // 3. start weights, then doubling of (sum, min) over the jump pointers
+        if ((rc = dev_alloc(dst, &d_rank, rank_of.size())) != DBG_OK || (rc = dev_alloc(dst, &start_of_rank, n_sel)) != DBG_OK) break;
+        if ((rc = dev_alloc(dst, &d_drv, n_sel + 1)) != DBG_OK) break;
+        NK_HIP(dst, hipMemcpyAsync(d_rank, rank_of.data(), rank_of.size() * 4, hipMemcpyHostToDevice, dst->stream));
+        NK_HIP(dst, hipMemcpyAsync(d_drv, drv_off.data(), (n_sel + 1) * 8, hipMemcpyHostToDevice, dst->stream));
+        if ((rc = dev_alloc(dst, &S[0], n)) != DBG_OK || (rc = dev_alloc(dst, &S[1], n)) != DBG_OK) break;
+        if ((rc = dev_alloc(dst, &M[0], n)) != DBG_OK || (rc = dev_alloc(dst, &M[1], n)) != DBG_OK) break;
+        dev_free(H[cur ^ 1]);
+        hipLaunchKernelGGL(k_nk_weights, grid, dim3(256), 0, dst->stream, n, d, emit, cidx, Hops, d_rank, S[0], M[0], start_of_rank);
+        NK_HIP(dst, hipMemcpyAsync(J[0], nxt, n * 4, hipMemcpyDeviceToDevice, dst->stream));
+        cur = 0;
+        if (nk_jump_until_closed(dst, n, [&](int round, unsigned long long *open) {
+                (void)hipMemcpyAsync(S[cur ^ 1], S[cur], n * 4, hipMemcpyDeviceToDevice, dst->stream);
+                (void)hipMemcpyAsync(M[cur ^ 1], M[cur], n * 8, hipMemcpyDeviceToDevice, dst->stream);
+                hipLaunchKernelGGL(k_nk_push, grid, dim3(256), 0, dst->stream, n, round, J[cur], S[cur], M[cur], J[cur ^ 1], S[cur ^ 1],
+                                   M[cur ^ 1], open);
+                cur ^= 1;
+            }, true) < 0) { rc = DBG_E_HIP; break; }
+        const uint32_t *Sum = S[cur];
+        const unsigned long long *Min = M[cur];
+        // 4. the K-nodes of the block's contigs
+        if ((rc = dev_alloc(dst, &zidx, n)) != DBG_OK) break;
+        if ((rc = exclusive_scan(dst, n, NkZFlag{Sum, Hops, (uint32_t)d}, zidx, &out.n_c)) != DBG_OK) break;
+        const uint64_t n_c = out.n_c;
+        if ((rc = dev_alloc(dst, &out.lo, n_c)) != DBG_OK || (rc = dev_alloc(dst, &out.hi, n_c)) != DBG_OK ||
+            (rc = dev_alloc(dst, &out.stamp, n_c)) != DBG_OK || (rc = dev_alloc(dst, &out.code, n_c)) != DBG_OK ||
+            (rc = dev_alloc(dst, &out.cnt, n_c)) != DBG_OK || (rc = dev_alloc(dst, &out.cid, n_c)) != DBG_OK) break;
+        hipLaunchKernelGGL(k_nk_emit, grid, dim3(256), 0, dst->stream, n, d, g, nxt, Sum, Hops, Min, zidx, d_drv, out.lo, out.hi,
+                           out.stamp, out.code, out.cnt);
+        if (hipGetLastError() != hipSuccess) { dst->err = "build_from_walks: launch failed"; rc = DBG_E_HIP; break; }
+        hipError_t e = hipStreamSynchronize(dst->stream);  // the scratch goes back before the next block starts
+        if (e != hipSuccess) { dst->err = std::string("build_from_walks: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
+        kept.next = nxt; nxt = nullptr;
+        kept.start = start_of_rank; start_of_rank = nullptr;
     } while (0);
-    dev_free(J[0]); dev_free(J[1]); dev_free(P[0]); dev_free(P[1]);
+    dev_free(nxt); dev_free(J[0]); dev_free(J[1]); dev_free(H[0]); dev_free(H[1]); dev_free(cidx); dev_free(d_rank);
+    dev_free(S[0]); dev_free(S[1]); dev_free(zidx); dev_free(start_of_rank); dev_free(M[0]); dev_free(M[1]); dev_free(d_drv);
+    dev_free(emit);
     return rc;
 }
 
-extern "C" int dbg_build_from_walk(dbg_t *dst, dbg_t *src, int k1, const uint64_t *order, uint64_t n_order,
-                                   const char *extra_bases, const uint64_t *extra_offsets, uint64_t n_extra) {
-    if (!dst || !src) return DBG_E_ARG;
-    if (dst == src) { dst->err = "dst and src must be different handles"; return DBG_E_ARG; }
-    if (dst->device != src->device) { dst->err = "dst and src must be on the same device"; return DBG_E_ARG; }
-    auto refuse = [&](const char *msg) { dst->err = msg; return DBG_E_ARG; };
-    if (!src->k || !src->walk_indexed) return refuse("src has no walk of its current graph");
-    if (src->multipass || src->partial_graph) return refuse("src holds a graph in parts: build from a single-table graph");
-    if (src->D != 4 || !src->is_dna) return refuse("src is not an ACGT graph (generic alphabets take the text path)");
-    if (src->walk_final) return refuse("the last walk of src was a final-mode walk (all simple paths, not chains)");
-    if (k1 > 63) return refuse("k1 must be at most 63");
-    if (k1 != src->k + 1) return refuse("k1 must be the k of src plus one");
-    if (n_order != src->n_contigs || (n_order && !order)) return refuse("order must be a permutation of the contig index");
-    if (src->n_nodes >= 0xFFFFFFF0ull) return refuse("src has too many nodes");
-    std::vector<uint32_t> rank_of(n_order, NK_NONE);
-    for (uint64_t r = 0; r < n_order; ++r) {
-        if (order[r] >= n_order || rank_of[order[r]] != NK_NONE) return refuse("order must be a permutation of the contig index");
-        rank_of[order[r]] = (uint32_t)r;
-    }
-    if (!extra_offsets || (n_extra && extra_offsets[n_extra] && !extra_bases)) return refuse("extra reads: offsets required");
-    HIPCHK(src, hipSetDevice(src->device));
-    CHK(ensure_dense(src));
-    // contig lengths in driver order -> offsets of the virtual reads
-    std::vector<uint64_t> off(n_order + 1, 0), drv_off(n_order + 1, 0);
-    if (n_order) {
-        HIPCHK(src, hipMemcpyAsync(off.data(), src->d_ctg_off, (n_order + 1) * 8, hipMemcpyDeviceToHost, src->stream));
-        HIPCHK(src, hipStreamSynchronize(src->stream));
-    }
-    uint64_t n_kmer_virtual = 0;
-    for (uint64_t r = 0; r < n_order; ++r) {
-        const uint64_t len = off[order[r] + 1] - off[order[r]];
-        drv_off[r + 1] = drv_off[r] + len;
-        if (len >= (uint64_t)k1) n_kmer_virtual += len - k1 + 1;  // KmerInstances: windows of reads with len >= k
-    }
-    const uint64_t T = drv_off[n_order];
-    if (T >= (1ull << 62)) return refuse("contig text too long for 64-bit stamps");
+// one block after its checks: its source, the level difference, the rank of every contig of the source inside the block
+// and the offsets of the block's contigs in the virtual text
+struct NkPlan {
+    dbg *src = nullptr;
+    int d = 0;
+    std::vector<uint32_t> rank_of;
+    std::vector<uint64_t> drv_off;
+};
 
+static int nk_build(dbg *dst, int k1, std::vector<NkPlan> &plan, uint64_t T, uint64_t n_kmer_virtual, const char *extra_bases,
+                    const uint64_t *extra_offsets, uint64_t n_extra) {
     // the extra reads become dst's reads (dbg_set_reads frees dst's graph); their k1-graph is built on a helper handle
     CHK(dbg_set_reads(dst, extra_bases, extra_offsets, n_extra));
     CHK(compute_alphabet(dst));
@@ -423,101 +556,58 @@ extern "C" int dbg_build_from_walk(dbg_t *dst, dbg_t *src, int k1, const uint64_
         if (rc != DBG_OK) { dst->err = std::string("extra reads: ") + ex->err; dbg_destroy(ex); return rc; }
         n_e = ex->n_nodes;
     }
-    const GDna g = dna_view(src);
-    const uint64_t n = src->n_nodes;
-    const dim3 grid(grid_for(n, 256));
     const bool wide = k1 > 31;
-    // scratch of the chain phase (freed at the end) and the arrays dst keeps for its pull-out test
-    uint32_t *nxt = nullptr, *J[2] = {nullptr, nullptr}, *H[2] = {nullptr, nullptr}, *cidx = nullptr, *d_rank = nullptr,
-             *S[2] = {nullptr, nullptr}, *yidx = nullptr, *start_of_rank = nullptr, *ccnt = nullptr, *hit = nullptr,
-             *newidx = nullptr, *cid = nullptr, *ynode = nullptr, *tab_id = nullptr;
-    unsigned long long *M[2] = {nullptr, nullptr};
-    uint64_t *d_drv = nullptr, *ck_lo = nullptr, *ck_hi = nullptr, *cstamp = nullptr, *tab_lo = nullptr, *tab_hi = nullptr;
-    uint8_t *emit = nullptr, *ccode = nullptr, *isnew = nullptr, *fs = nullptr, *c0 = nullptr;
+    const uint64_t n_blocks = plan.size();
+    std::vector<NkNodes> nodes(n_blocks);
+    std::vector<dbg::NkBlock> kept(n_blocks);
+    uint32_t *newidx = nullptr, *tab_id = nullptr;
+    uint64_t *tab_lo = nullptr, *tab_hi = nullptr;
+    uint8_t *isnew = nullptr, *fs = nullptr;
+    uint16_t *bo = nullptr;
     auto cleanup = [&]() {
-        dev_free(nxt); dev_free(J[0]); dev_free(J[1]); dev_free(H[0]); dev_free(H[1]); dev_free(cidx); dev_free(d_rank);
-        dev_free(S[0]); dev_free(S[1]); dev_free(yidx); dev_free(start_of_rank); dev_free(ccnt); dev_free(hit); dev_free(newidx);
-        dev_free(cid); dev_free(ynode); dev_free(tab_id); dev_free(M[0]); dev_free(M[1]); dev_free(d_drv); dev_free(ck_lo);
-        dev_free(ck_hi); dev_free(cstamp); dev_free(tab_lo); dev_free(tab_hi); dev_free(emit); dev_free(ccode); dev_free(isnew);
-        dev_free(fs); dev_free(c0);
+        for (auto &b : nodes) b.release();
+        for (auto &b : kept) { dev_free(b.next); dev_free(b.z); dev_free(b.start); }
+        dev_free(newidx); dev_free(tab_id); dev_free(tab_lo); dev_free(tab_hi); dev_free(isnew); dev_free(fs); dev_free(bo);
         if (ex) { dbg_destroy(ex); ex = nullptr; }
     };
     int rc = DBG_OK;
     do {
-        // 1. continuation pointers and hops to the chain end
-        if ((rc = dev_alloc(dst, &nxt, n)) != DBG_OK) break;
-        if ((rc = dev_alloc(dst, &J[0], n)) != DBG_OK || (rc = dev_alloc(dst, &J[1], n)) != DBG_OK) break;
-        if ((rc = dev_alloc(dst, &H[0], n)) != DBG_OK || (rc = dev_alloc(dst, &H[1], n)) != DBG_OK) break;
-        if (n) {
-            hipLaunchKernelGGL(k_nk_next, grid, dim3(256), 0, dst->stream, n, g, nxt);
-            hipLaunchKernelGGL(k_nk_hops_init, grid, dim3(256), 0, dst->stream, n, nxt, J[0], H[0]);
+        // 1.-4. block by block: the chain reductions and the block's K-nodes
+        uint64_t n_c_all = 0;
+        for (uint64_t b = 0; b < n_blocks && rc == DBG_OK; ++b) {
+            rc = nk_chain_block(dst, plan[b].src, plan[b].d, plan[b].rank_of, plan[b].drv_off, nodes[b], kept[b]);
+            std::vector<uint32_t>().swap(plan[b].rank_of);
+            std::vector<uint64_t>().swap(plan[b].drv_off);
+            n_c_all += nodes[b].n_c;
         }
-        int cur = 0;
-        if (n && nk_jump_until_closed(dst, n, [&](int, unsigned long long *open) {
-                hipLaunchKernelGGL(k_nk_rank_step, grid, dim3(256), 0, dst->stream, n, J[cur], H[cur], J[cur ^ 1], H[cur ^ 1], open);
-                cur ^= 1;
-            }) < 0) { rc = DBG_E_HIP; break; }
-        uint32_t *Jend = J[cur], *Hops = H[cur];
-        // 2. emitting starts == the walk's contig index (checked against it)
-        if ((rc = dev_alloc(dst, &emit, n)) != DBG_OK || (rc = dev_alloc(dst, &cidx, n)) != DBG_OK) break;
-        if (n) hipLaunchKernelGGL(k_nk_emits, grid, dim3(256), 0, dst->stream, n, g.flags, Jend, emit);
-        uint64_t n_ctg = 0, n_chr = 0;
-        if ((rc = exclusive_scan(dst, n, ByteAt{emit}, cidx, &n_ctg)) != DBG_OK) break;
-        if ((rc = reduce_sum(dst, n, NkChars{emit, Hops, src->k}, &n_chr)) != DBG_OK) break;
-        if (n_ctg != src->n_contigs || n_chr != src->contig_chars) {
-            dst->err = "internal: chains disagree with the walk's contig index";
-            rc = DBG_E_HIP;
-            break;
-        }
-        // 3. start weights, then doubling of (sum, min) over the jump pointers
-        if ((rc = dev_alloc(dst, &d_rank, n_order)) != DBG_OK || (rc = dev_alloc(dst, &start_of_rank, n_order)) != DBG_OK) break;
-        if ((rc = dev_alloc(dst, &d_drv, n_order + 1)) != DBG_OK) break;
-        if (n_order) {
-            HIPCHK(dst, hipMemcpyAsync(d_rank, rank_of.data(), n_order * 4, hipMemcpyHostToDevice, dst->stream));
-            HIPCHK(dst, hipMemcpyAsync(d_drv, drv_off.data(), (n_order + 1) * 8, hipMemcpyHostToDevice, dst->stream));
-        }
-        if ((rc = dev_alloc(dst, &S[0], n)) != DBG_OK || (rc = dev_alloc(dst, &S[1], n)) != DBG_OK) break;
-        if ((rc = dev_alloc(dst, &M[0], n)) != DBG_OK || (rc = dev_alloc(dst, &M[1], n)) != DBG_OK) break;
-        dev_free(H[cur ^ 1]);
-        if (n) {
-            hipLaunchKernelGGL(k_nk_weights, grid, dim3(256), 0, dst->stream, n, emit, cidx, Hops, d_rank, S[0], M[0], start_of_rank);
-            HIPCHK(dst, hipMemcpyAsync(J[0], nxt, n * 4, hipMemcpyDeviceToDevice, dst->stream));
-        }
-        cur = 0;
-        if (n && nk_jump_until_closed(dst, n, [&](int round, unsigned long long *open) {
-                (void)hipMemcpyAsync(S[cur ^ 1], S[cur], n * 4, hipMemcpyDeviceToDevice, dst->stream);
-                (void)hipMemcpyAsync(M[cur ^ 1], M[cur], n * 8, hipMemcpyDeviceToDevice, dst->stream);
-                hipLaunchKernelGGL(k_nk_push, grid, dim3(256), 0, dst->stream, n, round, J[cur], S[cur], M[cur], J[cur ^ 1], S[cur ^ 1],
-                                   M[cur ^ 1], open);
-                cur ^= 1;
-            }, true) < 0) { rc = DBG_E_HIP; break; }
-        const uint32_t *Sum = S[cur];
-        const unsigned long long *Min = M[cur];
-        // 4. the (k+1)-nodes of the contigs
-        uint64_t n_c = 0;
-        if ((rc = dev_alloc(dst, &yidx, n)) != DBG_OK) break;
-        if ((rc = exclusive_scan(dst, n, NkYFlag{Sum, nxt}, yidx, &n_c)) != DBG_OK) break;
-        if (n_e + n_c >= 0xFFFFFFF0ull) { dst->err = "more than 2^32-16 nodes"; rc = DBG_E_CAPACITY; break; }
-        if ((rc = dev_alloc(dst, &ck_lo, n_c)) != DBG_OK || (rc = dev_alloc(dst, &ck_hi, n_c)) != DBG_OK ||
-            (rc = dev_alloc(dst, &cstamp, n_c)) != DBG_OK || (rc = dev_alloc(dst, &ccode, n_c)) != DBG_OK ||
-            (rc = dev_alloc(dst, &ccnt, n_c)) != DBG_OK) break;
-        if (n) hipLaunchKernelGGL(k_nk_emit, grid, dim3(256), 0, dst->stream, n, g, nxt, Sum, Min, yidx, d_drv, ck_lo, ck_hi, cstamp,
-                                  ccode, ccnt);
-        // 5. union with the extra reads' graph by key
+        if (rc != DBG_OK) break;
+        if (n_e + n_c_all >= 0xFFFFFFF0ull) { dst->err = "more than 2^32-16 nodes"; rc = DBG_E_CAPACITY; break; }
+        // 5. union by key: the extra reads' graph first (ids 0 .. n_e-1), then the new nodes of every block in block order
         uint64_t cap = 1024;
-        while (cap < 2 * (n_e + n_c)) cap <<= 1;
+        while (cap < 2 * (n_e + n_c_all)) cap <<= 1;
         if ((rc = dev_alloc(dst, &tab_id, cap)) != DBG_OK || (rc = dev_alloc(dst, &tab_lo, cap)) != DBG_OK ||
             (rc = dev_alloc(dst, &tab_hi, cap)) != DBG_OK) break;
-        HIPCHK(dst, hipMemsetAsync(tab_id, 0xFF, cap * 4, dst->stream));
+        NK_HIP(dst, hipMemsetAsync(tab_id, 0xFF, cap * 4, dst->stream));
         const NkTab tab{tab_id, tab_lo, tab_hi, cap - 1};
         if (n_e) hipLaunchKernelGGL(k_nk_insert, dim3(grid_for(n_e, 256)), dim3(256), 0, dst->stream, n_e, ex->d_keys, ex->d_keys_hi, tab);
-        if ((rc = dev_alloc(dst, &hit, n_c)) != DBG_OK || (rc = dev_alloc(dst, &isnew, n_c)) != DBG_OK ||
-            (rc = dev_alloc(dst, &newidx, n_c)) != DBG_OK || (rc = dev_alloc(dst, &cid, n_c)) != DBG_OK) break;
-        const dim3 cgrid(grid_for(n_c, 256));
-        if (n_c) hipLaunchKernelGGL(k_nk_match, cgrid, dim3(256), 0, dst->stream, n_c, ck_lo, ck_hi, tab, hit, isnew);
-        uint64_t n_new = 0;
-        if ((rc = exclusive_scan(dst, n_c, ByteAt{isnew}, newidx, &n_new)) != DBG_OK) break;
-        const uint64_t nn = n_e + n_new;
+        std::vector<uint64_t> new_from(n_blocks + 1, n_e);
+        for (uint64_t b = 0; b < n_blocks && rc == DBG_OK; ++b) {
+            const NkNodes &nb = nodes[b];
+            uint64_t n_new = 0;
+            if (nb.n_c) {
+                const dim3 cgrid(grid_for(nb.n_c, 256));
+                if ((rc = dev_alloc(dst, &isnew, nb.n_c)) != DBG_OK || (rc = dev_alloc(dst, &newidx, nb.n_c)) != DBG_OK) break;
+                hipLaunchKernelGGL(k_nk_match, cgrid, dim3(256), 0, dst->stream, nb.n_c, nb.lo, nb.hi, tab, nb.cid, isnew);
+                if ((rc = exclusive_scan(dst, nb.n_c, ByteAt{isnew}, newidx, &n_new)) != DBG_OK) break;
+                hipLaunchKernelGGL(k_nk_insert_new, cgrid, dim3(256), 0, dst->stream, nb.n_c, new_from[b], isnew, newidx, nb.lo, nb.hi,
+                                   tab, nb.cid);
+                NK_HIP(dst, hipStreamSynchronize(dst->stream));
+                dev_free(isnew); dev_free(newidx);
+            }
+            new_from[b + 1] = new_from[b] + n_new;
+        }
+        if (rc != DBG_OK) break;
+        const uint64_t nn = new_from[n_blocks];
         // dst's node arrays (owned: free_build releases them)
         dst->k = k1;
         if ((rc = dev_alloc(dst, &dst->d_keys, nn)) != DBG_OK || (rc = dev_alloc(dst, &dst->d_stamps, nn)) != DBG_OK ||
@@ -525,25 +615,33 @@ extern "C" int dbg_build_from_walk(dbg_t *dst, dbg_t *src, int k1, const uint64_
             (rc = dev_alloc(dst, &dst->d_flags, nn)) != DBG_OK || (rc = dev_alloc(dst, &dst->d_order, nn)) != DBG_OK ||
             (rc = dev_alloc(dst, &dst->d_fsorder, nn)) != DBG_OK || (rc = dev_alloc(dst, &dst->d_deg, nn)) != DBG_OK) break;
         if (wide && (rc = dev_alloc(dst, &dst->d_keys_hi, nn)) != DBG_OK) break;
-        if ((rc = dev_alloc(dst, &fs, nn)) != DBG_OK || (rc = dev_alloc(dst, &c0, nn)) != DBG_OK) break;
+        if ((rc = dev_alloc(dst, &fs, nn)) != DBG_OK || (rc = dev_alloc(dst, &bo, nn)) != DBG_OK) break;
         dst->n_nodes = nn;
         if (n_e)
             hipLaunchKernelGGL(k_nk_fill_extra, dim3(grid_for(n_e, 256)), dim3(256), 0, dst->stream, n_e, ex->d_keys, ex->d_keys_hi,
                                ex->d_stamps, ex->d_cnt, ex->d_fsorder, 2 * T, dst->d_keys, dst->d_keys_hi, dst->d_stamps, dst->d_cnt,
-                               fs, c0);
-        if (n_c) {
-            hipLaunchKernelGGL(k_nk_fill_contig, cgrid, dim3(256), 0, dst->stream, n_c, n_e, ck_lo, ck_hi, cstamp, ccode, ccnt, hit,
-                               newidx, dst->d_keys, dst->d_keys_hi, dst->d_stamps, dst->d_cnt, fs, c0, cid);
-            hipLaunchKernelGGL(k_nk_insert_new, cgrid, dim3(256), 0, dst->stream, n_c, isnew, cid, ck_lo, ck_hi, tab);
+                               fs, bo);
+        for (uint64_t b = 0; b < n_blocks; ++b) {
+            const NkNodes &nb = nodes[b];
+            if (nb.n_c)
+                hipLaunchKernelGGL(k_nk_fill_contig, dim3(grid_for(nb.n_c, 256)), dim3(256), 0, dst->stream, nb.n_c, new_from[b], nb.lo,
+                                   nb.hi, nb.stamp, nb.code, nb.cnt, nb.cid, dst->d_keys, dst->d_keys_hi, dst->d_stamps, dst->d_cnt,
+                                   fs, bo);
         }
         if (nn)
             hipLaunchKernelGGL(k_nk_succ, dim3(grid_for(nn, 256)), dim3(256), 0, dst->stream, nn, k1, dst->d_keys, dst->d_keys_hi,
-                               dst->d_stamps, dst->d_cnt, fs, c0, tab, dst->d_succ, dst->d_deg, dst->d_flags, dst->d_order,
+                               dst->d_stamps, dst->d_cnt, fs, bo, tab, dst->d_succ, dst->d_deg, dst->d_flags, dst->d_order,
                                dst->d_fsorder);
-        // 6. what dbg_mark_pull_reads needs later: chain successors, y(x), the start of every virtual read
-        if ((rc = dev_alloc(dst, &ynode, n)) != DBG_OK) break;
-        if (n) hipLaunchKernelGGL(k_nk_ymap, grid, dim3(256), 0, dst->stream, n, g, nxt, tab, k1, ynode);
-        if (hipGetLastError() != hipSuccess) { dst->err = "build_from_walk: launch failed"; rc = DBG_E_HIP; break; }
+        // 6. what dbg_mark_pull_reads needs later, per block: chain successors, z(x), the start of every virtual read
+        for (uint64_t b = 0; b < n_blocks; ++b) {
+            const uint64_t n = kept[b].n_src;
+            if (!n) continue;
+            if ((rc = dev_alloc(dst, &kept[b].z, n)) != DBG_OK) break;
+            hipLaunchKernelGGL(k_nk_zmap, dim3(grid_for(n, 256)), dim3(256), 0, dst->stream, n, plan[b].d, dna_view(plan[b].src),
+                               kept[b].next, tab, kept[b].z);
+        }
+        if (rc != DBG_OK) break;
+        if (hipGetLastError() != hipSuccess) { dst->err = "build_from_walks: launch failed"; rc = DBG_E_HIP; break; }
         uint64_t edges = 0;
         if ((rc = reduce_sum(dst, nn * 4, CountSum{dst->d_cnt}, &edges)) != DBG_OK) break;
         dst->n_edge_inst = edges;
@@ -551,18 +649,86 @@ extern "C" int dbg_build_from_walk(dbg_t *dst, dbg_t *src, int k1, const uint64_
         if ((rc = finish_graph(dst)) != DBG_OK) break;
         dst->order_exact = true;
         dst->nk_graph = true;
-        dst->nk_reads = n_order;
         dst->nk_bytes = T;
-        dst->nk_src_nodes = n;
-        dst->d_nk_next = nxt; nxt = nullptr;
-        dst->d_nk_y = ynode; ynode = nullptr;
-        dst->d_nk_start = start_of_rank; start_of_rank = nullptr;
+        dst->nk_reads = 0;
+        for (const auto &b : kept) dst->nk_reads += b.n_reads;
+        dst->nk_blocks.swap(kept);
+        kept.clear();
         hipError_t e = hipStreamSynchronize(dst->stream);
-        if (e != hipSuccess) { dst->err = std::string("build_from_walk: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
+        if (e != hipSuccess) { dst->err = std::string("build_from_walks: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
     } while (0);
     cleanup();
     if (rc != DBG_OK) { const std::string keep = dst->err; free_build(dst); dst->err = keep; return rc; }
     dst->stats = dbg_stats_t{};
     dst->stats.ms_build_total = t_all.stop();
     return DBG_OK;
+}
+
+// contig lengths of src's walk -> the block's offsets in the virtual text, from `base` on; adds the block's K-mer windows
+static int nk_plan_block(dbg *dst, dbg *src, int k1, const uint64_t *contigs, uint64_t n_sel, uint64_t base, NkPlan &p,
+                         uint64_t &n_kmer_virtual) {
+    const uint64_t n_ctg = src->n_contigs;
+    p.src = src;
+    p.d = k1 - src->k;
+    p.rank_of.assign(n_ctg, NK_NONE);
+    for (uint64_t r = 0; r < n_sel; ++r) {
+        if (contigs[r] >= n_ctg) { dst->err = "a block names a contig index out of range"; return DBG_E_ARG; }
+        if (p.rank_of[contigs[r]] != NK_NONE) { dst->err = "a block names a contig twice"; return DBG_E_ARG; }
+        p.rank_of[contigs[r]] = (uint32_t)r;
+    }
+    HIPCHK(dst, hipSetDevice(src->device));
+    CHK(ensure_dense(src));
+    std::vector<uint64_t> off(n_ctg + 1, 0);
+    if (n_ctg) HIPCHK(dst, hipMemcpyAsync(off.data(), src->d_ctg_off, (n_ctg + 1) * 8, hipMemcpyDeviceToHost, src->stream));
+    HIPCHK(dst, hipStreamSynchronize(src->stream));
+    p.drv_off.assign(n_sel + 1, base);
+    for (uint64_t r = 0; r < n_sel; ++r) {
+        const uint64_t len = off[contigs[r] + 1] - off[contigs[r]];
+        p.drv_off[r + 1] = p.drv_off[r] + len;
+        if (len > (uint64_t)k1) n_kmer_virtual += len - k1 + 1;  // n_kmer_instances: windows of reads with len > k, as dbg_build counts
+    }
+    return DBG_OK;
+}
+
+extern "C" int dbg_build_from_walks(dbg_t *dst, int k1, const dbg_walk_block_t *blocks, uint64_t n_blocks,
+                                    const char *extra_bases, const uint64_t *extra_offsets, uint64_t n_extra) {
+    if (!dst || (n_blocks && !blocks)) return DBG_E_ARG;
+    auto refuse = [&](const char *msg) { dst->err = msg; return DBG_E_ARG; };
+    if (k1 > 63) return refuse("k1 must be at most 63");
+    for (uint64_t b = 0; b < n_blocks; ++b) {
+        const dbg *src = blocks[b].src;
+        if (!src) return refuse("a block has no source");
+        if (const char *why = nk_refuse_source(dst, src, true)) return refuse(why);
+        if (src->k >= k1) return refuse("k1 must be larger than the k of every source");
+        if (blocks[b].n && !blocks[b].contigs) return refuse("a block has no contig indices");
+        for (uint64_t a = 0; a < b; ++a)
+            if (blocks[a].src == src) return refuse("the same src is named by two blocks");
+    }
+    if (!extra_offsets || (n_extra && extra_offsets[n_extra] && !extra_bases)) return refuse("extra reads: offsets required");
+    std::vector<NkPlan> plan(n_blocks);
+    uint64_t T = 0, n_kmer_virtual = 0;
+    for (uint64_t b = 0; b < n_blocks; ++b) {
+        CHK(nk_plan_block(dst, blocks[b].src, k1, blocks[b].contigs, blocks[b].n, T, plan[b], n_kmer_virtual));
+        T = plan[b].drv_off.back();
+        if (T >= (1ull << 62)) return refuse("contig text too long for 64-bit stamps");
+    }
+    return nk_build(dst, k1, plan, T, n_kmer_virtual, extra_bases, extra_offsets, n_extra);
+}
+
+extern "C" int dbg_build_from_walk(dbg_t *dst, dbg_t *src, int k1, const uint64_t *order, uint64_t n_order,
+                                   const char *extra_bases, const uint64_t *extra_offsets, uint64_t n_extra) {
+    if (!dst || !src) return DBG_E_ARG;
+    auto refuse = [&](const char *msg) { dst->err = msg; return DBG_E_ARG; };
+    if (const char *why = nk_refuse_source(dst, src, false)) return refuse(why);
+    if (k1 > 63) return refuse("k1 must be at most 63");
+    if (k1 != src->k + 1) return refuse("k1 must be the k of src plus one");
+    if (n_order != src->n_contigs || (n_order && !order)) return refuse("order must be a permutation of the contig index");
+    if (src->n_nodes >= 0xFFFFFFF0ull) return refuse("src has too many nodes");
+    std::vector<uint8_t> seen(n_order, 0);
+    for (uint64_t r = 0; r < n_order; ++r) {
+        if (order[r] >= n_order || seen[order[r]]) return refuse("order must be a permutation of the contig index");
+        seen[order[r]] = 1;
+    }
+    const dbg_walk_block_t block{src, order, n_order};
+    return dbg_build_from_walks(dst, k1, &block, 1, extra_bases, extra_offsets, n_extra);
 }

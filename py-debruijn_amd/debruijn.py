@@ -20,6 +20,7 @@ the append order of ``already_pull_out``, contig order) -- equals the reference.
 """
 from __future__ import annotations
 
+import bisect
 import os
 from collections.abc import ItemsView, Mapping, Sequence
 
@@ -377,6 +378,34 @@ class ContigList(list):
 MAX_CONTIG_CHARS = 0  # dbg_walk's max_chars; 0 = the library default (1 GiB of contig text kept on the device)
 
 
+class _ContigBlock(Sequence):
+    """Contigs of one walk by reference: the graph handle, contig indices into its index and their lengths.  A text is
+    fetched from that graph when it is indexed (dbg_export_contig_text); ``len`` and ``take`` move none."""
+
+    def __init__(self, graph, idx, lengths, final, generation, walk):
+        self._graph = graph
+        self._idx = np.asarray(idx, dtype=np.int64)
+        self.lengths = np.asarray(lengths, dtype=np.int64)
+        self._final, self._generation, self._walk = final, generation, walk
+
+    def __len__(self):
+        return len(self._idx)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        return self._graph.export_contig_text(int(self._idx[i]), int(self.lengths[i])).decode("latin-1")
+
+    def take(self, positions):
+        p = np.asarray(positions, dtype=np.int64)
+        return _ContigBlock(self._graph, self._idx[p], self.lengths[p], self._final, self._generation, self._walk)
+
+    def current(self):
+        """The graph still holds the non-final walk these indices point into."""
+        g = self._graph
+        return self._final is False and g.generation == self._generation and g.walks == self._walk
+
+
 class LazyContigs(Sequence):
     """Contigs of a walk whose text was larger than MAX_CONTIG_CHARS: same order, ``.scores`` and ``.lengths`` as
     ContigList, every text fetched from the device when it is indexed (dbg_export_contig_text).
@@ -386,7 +415,8 @@ class LazyContigs(Sequence):
     ``sequences.extend(pull_out_read)``) runs unchanged on this object.  Both only permute / append: no text moves.
     ``sort`` orders by the device-computed getScore of every contig -- the one key the pipeline sorts by; evaluating an
     arbitrary ``key`` would mean fetching every text (10^12 characters at the BASELINE size).  A ``key`` that is not
-    that score is detected on a sample of the shortest contigs and refused."""
+    that score is detected on a sample of the shortest contigs and refused.  ``extend`` with the pull_out_read of a graph
+    built from walks (_PulledReads) appends its pulled contigs as blocks of references into the graphs that hold them."""
 
     _final = None       # set by output_contigs: the walk's mode and the handle state it read (construct_graph at k + 1
     _generation = None  # builds from the chains of a current non-final walk, dbg_build_from_walk)
@@ -397,12 +427,15 @@ class LazyContigs(Sequence):
         self._order = np.asarray(order)
         self._off = off
         self._score = np.asarray(score)
-        self._tail = []   # plain strings appended by extend()
+        self._tail = []   # appended by extend(): plain strings, and _ContigBlock's of contigs that stay on the device
+        self._tail_first = []  # position (behind the main part) of the first element of every tail item
+        self._tail_blocks = []  # which tail items are _ContigBlock's
+        self._tail_len = 0
         self.scores = self._score[self._order].tolist()
         self.lengths = (off[1:] - off[:-1])[self._order].tolist()
 
     def __len__(self):
-        return len(self._order) + len(self._tail)
+        return len(self._order) + self._tail_len
 
     def __getitem__(self, i):
         if isinstance(i, slice):
@@ -412,7 +445,10 @@ class LazyContigs(Sequence):
         if not 0 <= i < len(self):
             raise IndexError(i)
         if i >= len(self._order):
-            return self._tail[i - len(self._order)]
+            i -= len(self._order)
+            t = bisect.bisect_right(self._tail_first, i) - 1
+            item = self._tail[t]
+            return item[i - self._tail_first[t]] if type(item) is _ContigBlock else item
         c = int(self._order[i])
         return self._graph.export_contig_text(c, int(self._off[c + 1] - self._off[c])).decode("latin-1")
 
@@ -435,16 +471,61 @@ class LazyContigs(Sequence):
         self.lengths = [self.lengths[i] for i in perm.tolist()]
 
     def extend(self, more):
-        self._tail.extend(more)
+        parts = more._parts if type(more) is _PulledReads else [more]
+        for part in parts:
+            if type(part) is _ContigBlock:
+                if len(part):
+                    self._tail_blocks.append(len(self._tail))
+                    self._tail.append(part)
+                    self._tail_first.append(self._tail_len)
+                    self._tail_len += len(part)
+            else:
+                n = len(self._tail)
+                self._tail.extend(part)
+                n = len(self._tail) - n
+                self._tail_first.extend(range(self._tail_len, self._tail_len + n))
+                self._tail_len += n
+
+    def _main_block(self):
+        return _ContigBlock(self._graph, self._order, np.asarray(self.lengths, dtype=np.int64), self._final, self._generation,
+                            self._walk)
+
+    def _segments(self):
+        """The whole sequence in order as (first position, _ContigBlock) and (first position, list of the strings of a run)."""
+        yield 0, self._main_block()
+        n, at = len(self._order), 0
+        for b in self._tail_blocks + [len(self._tail)]:
+            if b > at:
+                yield n + self._tail_first[at], self._tail[at:b]
+            if b < len(self._tail):
+                yield n + self._tail_first[b], self._tail[b]
+            at = b + 1
 
 
 class _PulledReads(Sequence):
-    """pull_out_read of a graph built from a walk: the pulled contigs fetch their text from the k-graph when indexed
-    (like LazyContigs.__getitem__), the pulled original reads are strings."""
+    """pull_out_read of a graph built from walks: the pulled contigs stay references (graph, contig indices, lengths),
+    grouped by the graph that holds them -- the pulled contigs of the main part as one block, then the still pulled
+    subset of every block of the tail -- and fetch their text when indexed; the pulled original reads are strings."""
 
     def __init__(self, reads, idx):
-        self._reads = reads
-        self._idx = [int(i) for i in idx]
+        self._idx = idx = np.asarray(idx, dtype=np.int64)
+        self._parts = []  # _ContigBlock's and lists of strings, in read order
+        self._first = []
+        n = 0
+        for first, item in reads._segments():
+            lo, hi = np.searchsorted(idx, [first, first + len(item)])
+            if type(item) is _ContigBlock:
+                part = item.take(idx[lo:hi] - first)
+            else:
+                part = [item[i] for i in (idx[lo:hi] - first).tolist()]
+                if part and self._parts and type(self._parts[-1]) is list:
+                    self._parts[-1].extend(part)
+                    n += len(part)
+                    continue
+            if len(part):
+                self._parts.append(part)
+                self._first.append(n)
+                n += len(part)
 
     def __len__(self):
         return len(self._idx)
@@ -452,23 +533,40 @@ class _PulledReads(Sequence):
     def __getitem__(self, i):
         if isinstance(i, slice):
             return [self[j] for j in range(*i.indices(len(self)))]
-        return self._reads[self._idx[i]]
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        t = bisect.bisect_right(self._first, i) - 1
+        return self._parts[t][i - self._first[t]]
 
     def __eq__(self, other):
         return isinstance(other, (list, Sequence)) and list(self) == list(other)
 
 
 def _walk_source(reads, k):
-    """The k-graph whose chains build the (k = its k + 1)-graph of ``reads`` (dbg_build_from_walk), or None: a
-    LazyContigs of a current non-final walk over ACGT whose appended tail holds plain strings."""
+    """What builds the k-graph of ``reads`` from chains on the device (dbg_build_from_walk(s)), or None: a LazyContigs
+    of a current non-final walk over ACGT at k - 1 whose appended tail holds zero or more blocks of contigs of current
+    non-final ACGT walks on distinct graphs at smaller k, followed by plain strings.
+    -> (graph of the main part, [(graph, contig indices) of the tail blocks], the strings)."""
     if type(reads) is not LazyContigs or reads._final is not False:
         return None
     g = reads._graph
     if g.generation != reads._generation or g.walks != reads._walk or g.alphabet()[1] != 2 or g.sizes()["k"] + 1 != k:
         return None
-    if not all(type(r) is str for r in reads._tail):
+    nb = len(reads._tail_blocks)
+    if reads._tail_blocks != list(range(nb)):  # a string in front of a block
         return None
-    return g
+    blocks, strings, seen = [], reads._tail[nb:], {id(g)}
+    for item in reads._tail[:nb]:
+        bg = item._graph
+        if id(bg) in seen or not item.current() or bg.alphabet()[1] != 2 or bg.sizes()["k"] >= k:
+            return None
+        seen.add(id(bg))
+        blocks.append((bg, item._idx))
+    if not all(type(r) is str for r in strings):
+        return None
+    return g, blocks, strings
 
 
 def _pack_reads(reads):
@@ -493,13 +591,15 @@ def construct_graph(reads, k, threshold=3, final=False):
     k = int(k)
     src = _walk_source(reads, k)
     if src is not None:
-        bases, offsets = _pack_reads(reads._tail)
+        src, tail_blocks, strings = src
+        bases, offsets = _pack_reads(strings)
         if not np.isin(bases, np.frombuffer(b"ACGT", dtype=np.uint8)).all():
             src = None
     if src is not None:
-        # the contigs of the k-graph's walk + the appended reads, built from the chains: no contig text is spelled
+        # the contigs of the (k-1)-graph's walk + the pulled contigs of earlier walks + the appended reads, built from
+        # the chains of the graphs that hold them: no contig text is spelled
         g = _dbg.Graph()
-        g.build_from_walk(src, k, reads._order, bases, offsets)
+        g.build_from_walk(src, k, reads._order, bases, offsets, tail_blocks)
     else:
         if isinstance(reads, DeviceReads):
             g = reads._graph  # reads are resident (alphabet is checked by the kernels: AlphabetError is a ValueError)
