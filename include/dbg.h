@@ -27,7 +27,7 @@
  *     alphabet (the reference is alphabet-agnostic; its real inputs are peptides) takes the
  *     generic path: up to 32 distinct bytes, codes in byte order (dbg_get_alphabet), 32 successor
  *     slots per node, k <= 63 (5 bits per character in one word up to k = 11, tables keyed by
- *     reference into the reads above); DBG_E_ALPHABET for more symbols or k >= 64.
+ *     reference into the reads above); DBG_E_ALPHABET for more symbols.  k >= 64 is DBG_E_ARG, as on every path.
  */
 #ifndef DBG_H
 #define DBG_H
