@@ -136,7 +136,13 @@ int dbg_abi_version(void);
  * of 2 GiB and more): 3 = k_sk_count3 (default), 1, 2; "wcount_kernel" k > 31, 32-bit stamps: 2 = k_wsk_count2 (default),
  * 1 = k_wsk_count; "stamp64" 1: dbg_build / dbg_build_multipass keep 64-bit stamps below 2 GiB of reads too (what larger
  * inputs get by themselves); "resolve_sorted" 1 (2: at any size): cross-bucket successor queries grouped by their target
- * before the resolver (measured slower: off); "wide_engine" 0: k > 31 on the global-table engine of round 1;
+ * before the resolver (measured slower: off); "resolve_direct" 1 (default): the resolver of a single-GPU build takes a
+ * cross-bucket successor's node from the directory entry of its home slot alone where that entry names it (the run of
+ * occupied slots from the home slot is one slot long and ends inside the 64-slot block) and reads no key for it -- such an
+ * answer is not compared, so a single wrong directory entry no longer fails the build by itself; 0: every query reads and
+ * compares its key run (the full check); sharded builds and dbg_shard_answer always compare;
+ * "resolve_count" 1 (tests): the resolvers run a counting instantiation that fills the resolve_* counters of
+ * dbg_get_counter; "wide_engine" 0: k > 31 on the global-table engine of round 1;
  * "extract_generic" 1: the window-minimum-through-LDS extraction kernels; "extract_presplit" f0 in 0..6: dbg_build's
  * extraction (13 <= k <= 31 over ACGT) writes its records pre-split by the top f0 bits of the bucket hash so that level 1 of
  * the multisplit has 2^f0 times fewer children per group (0: one segment per workgroup); "shard_stamp64" 1: dbg_shard_extract hands out
@@ -314,6 +320,8 @@ int dbg_get_stats(dbg_t *h, dbg_stats_t *out);
  * "extract_presplit_fallbacks": builds whose pre-split extraction overflowed a sub-segment and ran again without the split.
  * "extract_presplit_rehists": builds whose level 1 took another width than the pre-split extraction had counted its
  *   records for, so that the level ran its histogram pass after all.
+ * "resolve_direct_hits" / "resolve_keyed": cross-bucket successor queries (dbg_shard_answer's included) answered from the
+ *   directory entry alone / after reading keys; counted only while option "resolve_count" is 1.
  * DBG_E_ARG for an unknown name. */
 int dbg_get_counter(dbg_t *h, const char *name, uint64_t *out);
 

@@ -75,7 +75,9 @@ class WalkBlock(C.Structure):
     _fields_ = [("src", C.c_void_p), ("contigs", C.c_void_p), ("n", C.c_uint64)]
 
 
-COUNTERS = ("extract_presplit_fallbacks", "extract_presplit_rehists")  # dbg_get_counter names that Graph.stats() reports
+# dbg_get_counter names that Graph.stats() reports.  resolve_*: queries the resolver answered from the directory entry alone /
+# after reading keys -- filled only under option "resolve_count" 1 (tests), by a counting instantiation of the resolver
+COUNTERS = ("extract_presplit_fallbacks", "extract_presplit_rehists", "resolve_direct_hits", "resolve_keyed")
 
 
 class DbgError(RuntimeError):

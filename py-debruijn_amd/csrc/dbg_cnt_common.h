@@ -98,7 +98,7 @@ __device__ inline void cnt_write_directory(const LDS &s, const OUT &ow, uint64_t
         SkDirEnt de;
         de.mask = s.dir_mask[td];
         de.base = (uint32_t)(gbase + s.dir_base[td]);
-        de.pad = s.ri < ow.n_buckets ? 1u : 0u;
+        de.pad = s.ri < ow.n_buckets ? DIR_WHOLE_BUCKET : 0u;
         const uint64_t di = s.ri < ow.n_buckets ? s.ri - ow.own_lo : ow.own_cnt + (s.ri - ow.n_buckets);
         ow.dirs[di * (CAP / 64) + td] = de;
     }

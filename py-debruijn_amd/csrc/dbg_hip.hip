@@ -161,6 +161,9 @@ struct dbg {
     int count_kernel_u64 = 3; // option "count_kernel_u64": the count kernel of 64-bit stamps (shards, reads of 2 GiB and more): 3 = k_sk_count3 (one hint per slot; 12.2 ms on a 10 M-read shard), 1 = k_sk_count (13.4), 2 = k_sk_count2 (15.5: 320 staged records)
     int stamp64 = 0;         // option "stamp64" 1: dbg_build keeps 64-bit stamps even for reads below 2 GiB (what reads of 2 GiB and more get by themselves; tests)
     int resolve_sorted = 0;  // option "resolve_sorted" 1: cross-bucket queries grouped by the 512 level-1 groups of their target before k_succ_resolve.  Measured (tools/resolve_ab.py, 10 M reads): 3.09 ms with the grouping against 2.05 ms in the askers' order -- off
+    int resolve_direct = 1;  // option "resolve_direct" 1: the resolver of a single-GPU build takes a successor's node from the directory entry alone where dir_decide (dbg_dir.h) can name it, and reads no key for it; 0: every query reads and compares its key run.  Measured: DESIGN.md 3
+    int resolve_count = 0;   // option "resolve_count" 1 (tests): the resolvers' counting instantiation fills resolve_direct_hits / resolve_keyed
+    uint64_t resolve_direct_hits = 0, resolve_keyed = 0;  // queries answered without / with a key read, summed over the handle's resolver launches under "resolve_count" (dbg_get_counter)
     int wcount_kernel = 2;   // 32 <= k <= 63, 32-bit stamps: 2 = k_wsk_count2 (one successor hint per slot, deferred lookups), 1 = k_wsk_count
     int count_kernel = 2;    // k <= 31, 4096 slots: 2 = k_sk_count2 (successor hints, 16-bit counters; falls back to 1 on counter overflow), 1 = k_sk_count
 
@@ -2459,6 +2462,8 @@ extern "C" int dbg_set_option(dbg_t *h, const char *name, int64_t value) {
     if (n == "count_kernel" && value >= 1 && value <= 3) { h->count_kernel = (int)value; return DBG_OK; }
     if (n == "stamp64" && (value == 0 || value == 1)) { h->stamp64 = (int)value; return DBG_OK; }
     if (n == "resolve_sorted" && value >= 0 && value <= 2) { h->resolve_sorted = (int)value; return DBG_OK; }
+    if (n == "resolve_direct" && (value == 0 || value == 1)) { h->resolve_direct = (int)value; return DBG_OK; }
+    if (n == "resolve_count" && (value == 0 || value == 1)) { h->resolve_count = (int)value; return DBG_OK; }
     if (n == "wcount_kernel" && (value == 1 || value == 2)) { h->wcount_kernel = (int)value; return DBG_OK; }
     if (n == "count_kernel_u64" && value >= 1 && value <= 3) { h->count_kernel_u64 = (int)value; return DBG_OK; }
     if (n == "shard_node_limit" && value >= 0 && value < (1ll << 29)) { h->shard_node_limit = (uint64_t)value; return DBG_OK; }
@@ -3366,6 +3371,8 @@ extern "C" int dbg_get_counter(dbg_t *h, const char *name, uint64_t *out) {
     const std::string n(name);
     if (n == "extract_presplit_rehists") { *out = h->presplit_rehists; return DBG_OK; }
     if (n == "extract_presplit_fallbacks") { *out = h->presplit_fallbacks; return DBG_OK; }
+    if (n == "resolve_direct_hits") { *out = h->resolve_direct_hits; return DBG_OK; }
+    if (n == "resolve_keyed") { *out = h->resolve_keyed; return DBG_OK; }
     h->err = "unknown counter: " + n;
     return DBG_E_ARG;
 }
@@ -4021,6 +4028,17 @@ static int sk_partition(dbg *h, const SkPartitionParams<Est> &pp, const uint64_t
     return DBG_OK;
 }
 
+// option "resolve_count": the pair that a resolver's counting instantiation left in the scalar block joins the handle's counters
+static int resolve_counts_in(dbg *h) {
+    if (!h->resolve_count) return DBG_OK;
+    uint64_t c[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(c, h->d_scalars + SC_RESOLVE_COUNTS, 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->resolve_direct_hits += c[0];
+    h->resolve_keyed += c[1];
+    return DBG_OK;
+}
+
 // ---- stages 2..: records given as segments of (in_w0, in_w1, in_st) -> node arrays + successors.
 // The ping-pong sets w0/w1/st (arena) must hold n_rec records; n_inst bounds the distinct k-mers.
 // shard_bits > 0: only buckets whose top shard_bits equal my_shard hold records (the caller made
@@ -4253,11 +4271,19 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
             q_meta = qm[1];
         }
         if (n_q) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_succ_resolve<CAP>), dim3(grid_for(n_q, 256)), dim3(256), 0, h->stream,
+            // the shortcut is for the queries of a single-GPU build: every one of them is the successor of a counted edge
+            const bool direct = !shard_bits && h->resolve_direct;
+            auto resolver = direct ? k_succ_resolve<CAP, true, false> : k_succ_resolve<CAP, false, false>;
+            if (h->resolve_count) {
+                resolver = direct ? k_succ_resolve<CAP, true, true> : k_succ_resolve<CAP, false, true>;
+                HIPCHK(h, hipMemsetAsync(sc_dev + SC_RESOLVE_COUNTS, 0, 16, h->stream));
+            }
+            hipLaunchKernelGGL(resolver, dim3(grid_for(n_q, 256)), dim3(256), 0, h->stream,
                                qk[qset] + root[0], qc[qset] + root[0], n_q, geom, ranges, n_buckets, n_ranges, dirs, h->d_keys,
-                               h->n_nodes, h->d_col, id_tag, sc_dev, q_meta);
+                               h->n_nodes, h->d_col, id_tag, sc_dev, q_meta, sc_dev + SC_RESOLVE_COUNTS);
             HIPCHK(h, hipGetLastError());
             HIPCHK(h, hipMemcpyAsync(sc, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream));
+            CHK(resolve_counts_in(h));
             HIPCHK(h, hipStreamSynchronize(h->stream));
             if (sc[0] & STATUS_SUCC_MISSING) { h->err = "internal: a successor k-mer was not found in its bucket"; return DBG_E_HIP; }
         }
@@ -4566,10 +4592,18 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
             n_q = mine_n;
         }
         if (n_q) {
-            hipLaunchKernelGGL(k_wsucc_resolve, dim3(grid_for(n_q, 256)), dim3(256), 0, h->stream, r_lo, r_hi, stride, r_col, n_q, geom,
-                               ranges, n_buckets, n_ranges, dirs, h->d_keys, h->d_keys_hi, h->n_nodes, h->d_col, id_tag, sc_dev);
+            const bool direct = !shard_bits && h->resolve_direct;  // as in sk_count_from_segments
+            auto resolver = direct ? k_wsucc_resolve<true, false> : k_wsucc_resolve<false, false>;
+            if (h->resolve_count) {
+                resolver = direct ? k_wsucc_resolve<true, true> : k_wsucc_resolve<false, true>;
+                HIPCHK(h, hipMemsetAsync(sc_dev + SC_RESOLVE_COUNTS, 0, 16, h->stream));
+            }
+            hipLaunchKernelGGL(resolver, dim3(grid_for(n_q, 256)), dim3(256), 0, h->stream, r_lo, r_hi, stride, r_col, n_q, geom,
+                               ranges, n_buckets, n_ranges, dirs, h->d_keys, h->d_keys_hi, h->n_nodes, h->d_col, id_tag, sc_dev,
+                               sc_dev + SC_RESOLVE_COUNTS);
             HIPCHK(h, hipGetLastError());
             HIPCHK(h, hipMemcpyAsync(sc, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream));
+            CHK(resolve_counts_in(h));
             HIPCHK(h, hipStreamSynchronize(h->stream));
             if (sc[0] & STATUS_SUCC_MISSING) { h->err = "internal: a successor k-mer was not found in its bucket"; return DBG_E_HIP; }
         }
@@ -5152,19 +5186,26 @@ extern "C" int dbg_shard_answer(dbg_t *h, const void *d_q_keys, uint64_t n, void
     unsigned long long *sc_dev = (unsigned long long *)h->d_scalars;
     HIPCHK(h, hipMemsetAsync(d_answers, 0xFF, n * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_scalars, 0, 8, h->stream));
+    if (h->resolve_count) HIPCHK(h, hipMemsetAsync(h->d_scalars + SC_RESOLVE_COUNTS, 0, 16, h->stream));
     const SkRange *ranges = (const SkRange *)h->ar_misc[MISC_RANGES].p;
     const SkDirEnt *dirs = (const SkDirEnt *)h->ar_dir.p;
     if (!ranges || !dirs || h->sk_cap != 4096) { h->err = "dbg_shard_build must run first"; return DBG_E_ARG; }
     if (h->k > 31) {  // two-word k-mers: the keys come as (lo, hi) pairs
         if (!h->d_keys_hi) { h->err = "dbg_shard_build (LDS engine) must run first"; return DBG_E_ARG; }
-        hipLaunchKernelGGL(k_wsucc_resolve, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const uint64_t *)d_q_keys,
+        auto resolver = h->resolve_count ? k_wsucc_resolve<false, true> : k_wsucc_resolve<false, false>;
+        hipLaunchKernelGGL(resolver, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const uint64_t *)d_q_keys,
                            (const uint64_t *)d_q_keys + 1, 2, (const uint32_t *)nullptr, n, h->sk_geom, ranges, h->sk_n_buckets,
-                           h->sk_n_ranges, dirs, h->d_keys, h->d_keys_hi, h->n_nodes, (uint32_t *)d_answers, 0u, sc_dev);
-    } else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_succ_resolve<4096>), dim3(grid_for(n, 256)), dim3(256), 0, h->stream,
-                       (const uint64_t *)d_q_keys, (const uint32_t *)nullptr, n, h->sk_geom, ranges, h->sk_n_buckets,
-                       h->sk_n_ranges, dirs, h->d_keys, h->n_nodes, (uint32_t *)d_answers, 0u, sc_dev, (const uint64_t *)nullptr);
+                           h->sk_n_ranges, dirs, h->d_keys, h->d_keys_hi, h->n_nodes, (uint32_t *)d_answers, 0u, sc_dev,
+                           sc_dev + SC_RESOLVE_COUNTS);
+    } else {
+        auto resolver = h->resolve_count ? k_succ_resolve<4096, false, true> : k_succ_resolve<4096, false, false>;
+        hipLaunchKernelGGL(resolver, dim3(grid_for(n, 256)), dim3(256), 0, h->stream,
+                           (const uint64_t *)d_q_keys, (const uint32_t *)nullptr, n, h->sk_geom, ranges, h->sk_n_buckets,
+                           h->sk_n_ranges, dirs, h->d_keys, h->n_nodes, (uint32_t *)d_answers, 0u, sc_dev, (const uint64_t *)nullptr,
+                           sc_dev + SC_RESOLVE_COUNTS);
+    }
     HIPCHK(h, hipGetLastError());
+    CHK(resolve_counts_in(h));
     uint64_t sc0 = 0;
     HIPCHK(h, hipMemcpyAsync(&sc0, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -5490,6 +5531,8 @@ static int multipass_parts(dbg *h, int k, int n_virtual, int v_first, int n_pass
         sub->count_kernel_u64 = h->count_kernel_u64;
         sub->wcount_kernel = h->wcount_kernel;
         sub->resolve_sorted = h->resolve_sorted;
+        sub->resolve_direct = h->resolve_direct;
+        sub->resolve_count = h->resolve_count;
         sub->target_distinct = h->target_distinct;
         sub->est_scale_pct = h->est_scale_pct;
         if (!sub->d_scalars) HIPCHK(h, hipMalloc((void **)&sub->d_scalars, 128 * sizeof(uint64_t)));

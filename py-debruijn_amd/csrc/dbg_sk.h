@@ -13,6 +13,7 @@
 #pragma once
 #include <cstddef>
 #include "dbg_device.h"
+#include "dbg_dir.h"
 
 namespace dbgk {
 
@@ -783,16 +784,7 @@ __device__ inline int lds_find(const unsigned long long *keys, uint64_t key) {
     return -1;
 }
 
-// Directory of one counted range: per 64-slot block of its LDS table the occupancy mask and the node id of the
-// block's first node.  The nodes of a block are written in slot order, so (mask, base) turn a slot into a node id and
-// k_succ_resolve can repeat the table's linear probing against the node keys in HBM -- a successor that lives in
-// another bucket costs the asker two dependent reads instead of a trip through a multisplit of all such queries.
-struct SkDirEnt {
-    unsigned long long mask;
-    uint32_t base;
-    uint32_t pad;
-};
-static_assert(sizeof(SkDirEnt) == 16, "directory entry");
+// (the directory of a counted range, SkDirEnt: dbg_dir.h)
 
 // What the count kernel writes: the graph in ONE representation -- node keys, first-occurrence stamps, one byte per
 // node (indegree flag | bases that occur << 1) and the CSR rows (rowptr, successor id, count).  The dense per-base views
@@ -1240,7 +1232,7 @@ __global__ __launch_bounds__((CntCfg<ST, CAP>::NT)) void k_sk_count(const uint64
                 SkDirEnt de;
                 de.mask = s.dir_mask[threadIdx.x];
                 de.base = (uint32_t)(gbase + s.dir_base[threadIdx.x]);
-                de.pad = s.ri < ow.n_buckets ? 1u : 0u;  // 1: the whole bucket is this one range (k_succ_resolve need not ask)
+                de.pad = s.ri < ow.n_buckets ? DIR_WHOLE_BUCKET : 0u;  // the whole bucket is this one range (k_succ_resolve need not ask)
                 const uint64_t di = s.ri < ow.n_buckets ? s.ri - ow.own_lo : ow.own_cnt + (s.ri - ow.n_buckets);
                 ow.dirs[di * (CAP / 64) + threadIdx.x] = de;
             }
@@ -1364,15 +1356,21 @@ __global__ __launch_bounds__(256) void k_q_bucket(const uint64_t *__restrict__ q
 // in slot order from dir.base on -- so the probe is one directory entry (16 bytes) and a run of consecutive keys.
 // `whole` (may be null): set to false when the first entry read is not marked as the directory of an unsplit bucket
 // (the bucket was counted in hash sub-ranges, or is empty): the caller then goes through the ranges.
-template <int CAP>
+// DIRECT (with `whole`, first block only): where dir_decide (dbg_dir.h) names the node from the entry alone, the key run
+// is not read and *direct is set -- for queries that exist as a node by construction; such an answer is not compared.
+template <int CAP, bool DIRECT = false>
 __device__ inline uint32_t dir_find(const SkDirEnt *__restrict__ dirs, uint64_t ri, const uint64_t *__restrict__ keys,
-                                    uint64_t n_nodes, uint64_t key, bool *whole = nullptr) {
+                                    uint64_t n_nodes, uint64_t key, bool *whole = nullptr, bool *direct = nullptr) {
     constexpr int NBLK = CAP / 64;
     uint32_t slot = slot_of<CAP>(key);
     for (int blocks = 0; blocks <= NBLK; ++blocks) {
         const SkDirEnt de = dirs[ri * NBLK + (slot >> 6)];
-        if (whole && blocks == 0 && de.pad != 1u) { *whole = false; return NO_NODE; }
+        if (whole && blocks == 0 && !(de.pad & DIR_WHOLE_BUCKET)) { *whole = false; return NO_NODE; }
         const int bit = (int)(slot & 63);
+        if (DIRECT && whole && blocks == 0) {
+            uint64_t node;
+            if (dir_decide(de, bit, &node) && node < n_nodes) { *direct = true; return (uint32_t)node; }
+        }
         const unsigned long long run_bits = de.mask >> bit;
         if (!(run_bits & 1ull)) return NO_NODE;
         const int avail = 64 - bit;
@@ -1387,41 +1385,59 @@ __device__ inline uint32_t dir_find(const SkDirEnt *__restrict__ dirs, uint64_t 
     return NO_NODE;
 }
 
+// The resolvers' counting instantiation (tests only): every query adds one to a workgroup's LDS pair, one global add per
+// workgroup and counter.  counts[0] += queries dir_decide answered, counts[1] += queries that read keys.  All threads of
+// the workgroup come here (barriers); `valid`: this thread had a query.
+__device__ inline void resolve_count(bool valid, bool direct, unsigned long long *counts) {
+    __shared__ uint32_t s_cnt[2];
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    if (valid) atomicAdd(&s_cnt[direct ? 0 : 1], 1u);
+    __syncthreads();
+    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)s_cnt[threadIdx.x]);
+}
+
 // out[q_col ? q_col[i] : i] = node id of q_key[i] (| id_tag).  One thread per query.
-template <int CAP>
+// DIRECT: option "resolve_direct" of a single-GPU build (every query is the successor of a counted edge, so it exists);
+// COUNT: resolve_count.  The default instantiation carries no counting and no atomics but the status word's.
+template <int CAP, bool DIRECT, bool COUNT>
 __global__ __launch_bounds__(256) void k_succ_resolve(const uint64_t *__restrict__ q_key, const uint32_t *__restrict__ q_col,
                                                       uint64_t n, SkGeom g, const SkRange *__restrict__ ranges,
                                                       uint64_t n_buckets, uint64_t n_ranges,
                                                       const SkDirEnt *__restrict__ dirs, const uint64_t *__restrict__ keys,
                                                       uint64_t n_nodes, uint32_t *out, uint32_t id_tag,
                                                       unsigned long long *scalars,
-                                                      const uint64_t *__restrict__ q_meta /* NULL, or k_q_bucket's words: the bucket hash in bits 40.. */) {
+                                                      const uint64_t *__restrict__ q_meta /* NULL, or k_q_bucket's words: the bucket hash in bits 40.. */,
+                                                      unsigned long long *counts /* COUNT */) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t key = q_key[i];
-    const uint64_t bucket = sk_bucket_of(q_meta ? (uint32_t)(q_meta[i] >> 40) : kmer_bucket22(key, g.k, g.m), g);
-    uint32_t id = NO_NODE;
-    if (bucket >= g.own_lo && bucket < g.own_lo + g.own_cnt) {
-        // common case: the bucket is one range and its directory says so -- two dependent reads (directory entry, key
-        // run), each a 128-byte line of HBM; the ranges array is not touched (the resolver moves ~370 bytes per query
-        // and runs at the HBM rate, so a line less per query is a quarter of its time)
-        bool whole = true;
-        id = dir_find<CAP>(dirs, bucket - g.own_lo, keys, n_nodes, key, &whole);
-        uint64_t ri = bucket;
-        bool have = false;
-        if (!whole) {  // the bucket was counted in hash sub-ranges: walk its chain of ranges to the one of this key
-            const uint32_t sh = sub_hash(key);
-            uint32_t r = ranges[bucket].next;
-            for (int guard = 0; r && r < n_ranges && !have && guard < (1 << 20); ++guard) {
-                const SkRange rg = ranges[r];
-                if (rg.node_cnt && (sh & rg.mask) == rg.val) { ri = r; have = true; }
-                r = rg.next;
+    bool direct = false;
+    if (i < n) {
+        const uint64_t key = q_key[i];
+        const uint64_t bucket = sk_bucket_of(q_meta ? (uint32_t)(q_meta[i] >> 40) : kmer_bucket22(key, g.k, g.m), g);
+        uint32_t id = NO_NODE;
+        if (bucket >= g.own_lo && bucket < g.own_lo + g.own_cnt) {
+            // common case: the bucket is one range and its directory says so -- the directory entry and, where the entry
+            // alone does not name the node, the key run: dependent reads, each a 128-byte line of HBM; the ranges array is
+            // not touched (the resolver runs at the HBM rate for whole-line gathers, so a line less per query is time)
+            bool whole = true;
+            id = dir_find<CAP, DIRECT>(dirs, bucket - g.own_lo, keys, n_nodes, key, &whole, &direct);
+            uint64_t ri = bucket;
+            bool have = false;
+            if (!whole) {  // the bucket was counted in hash sub-ranges: walk its chain of ranges to the one of this key
+                const uint32_t sh = sub_hash(key);
+                uint32_t r = ranges[bucket].next;
+                for (int guard = 0; r && r < n_ranges && !have && guard < (1 << 20); ++guard) {
+                    const SkRange rg = ranges[r];
+                    if (rg.node_cnt && (sh & rg.mask) == rg.val) { ri = r; have = true; }
+                    r = rg.next;
+                }
             }
+            if (have) id = dir_find<CAP>(dirs, g.own_cnt + (ri - n_buckets), keys, n_nodes, key);
         }
-        if (have) id = dir_find<CAP>(dirs, g.own_cnt + (ri - n_buckets), keys, n_nodes, key);
+        if (id == NO_NODE) atomicOr(&scalars[0], STATUS_SUCC_MISSING);  // every successor k-mer exists as a node
+        else out[q_col ? q_col[i] : i] = id | id_tag;
     }
-    if (id == NO_NODE) { atomicOr(&scalars[0], STATUS_SUCC_MISSING); return; }  // every successor k-mer exists as a node
-    out[q_col ? q_col[i] : i] = id | id_tag;
+    if (COUNT) resolve_count(i < n, direct, counts);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -73,6 +73,7 @@ struct Cnt2Cfg {
 // Words of the handle's scalar block that the host addresses by number during a build (word 0 holds the Status bits,
 // dbg_device.h).  Outside a build the words are free: dbg_build_from_walk keeps a cursor in word 40, the walk one in word 64.
 constexpr int SC_ESTIMATE = 40;    // (instances, distinct k-mers) of the estimate kernel
+constexpr int SC_RESOLVE_COUNTS = 48;  // (direct hits, keyed queries) of a resolver's counting instantiation (option "resolve_count")
 constexpr int SC_L2_SUMS = 56;     // (k-mer, edge) instances summed by a level-2 histogram pass or k_stamp_globalize
 constexpr int SC_DESCRIPTOR = 64;  // words 64..: the count kernels' descriptor (fresh_args)
 // the query cursor of this kernel: far from the node / edge cursor (word 4) -- atomics on one cache line queue up behind each other
@@ -629,7 +630,7 @@ __global__ __launch_bounds__(1024) void k_sk_count2(const SkCount2Args *__restri
                     SkDirEnt de;
                     de.mask = s.dir_mask[threadIdx.x];
                     de.base = (uint32_t)(gbase + s.dir_base[threadIdx.x]);
-                    de.pad = s.ri < ow.n_buckets ? 1u : 0u;
+                    de.pad = s.ri < ow.n_buckets ? DIR_WHOLE_BUCKET : 0u;
                     const uint64_t di = s.ri < ow.n_buckets ? s.ri - ow.own_lo : ow.own_cnt + (s.ri - ow.n_buckets);
                     ow.dirs[di * (CAP / 64) + threadIdx.x] = de;
                 }

@@ -964,7 +964,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count(const uint64_t *__restric
                 SkDirEnt de;
                 de.mask = s.dir_mask[threadIdx.x];
                 de.base = (uint32_t)(gbase + s.dir_base[threadIdx.x]);
-                de.pad = s.ri < ow.n_buckets ? 1u : 0u;
+                de.pad = s.ri < ow.n_buckets ? DIR_WHOLE_BUCKET : 0u;
                 const uint64_t di = s.ri < ow.n_buckets ? s.ri - ow.own_lo : ow.own_cnt + (s.ri - ow.n_buckets);
                 ow.dirs[di * (WCAP / 64) + threadIdx.x] = de;
             }
@@ -1053,14 +1053,21 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count(const uint64_t *__restric
 // ------------------------------------------------------------------------------------------------
 // successors that live in another bucket, through the directory (k_succ_resolve with two-word keys)
 // ------------------------------------------------------------------------------------------------
+// (dir_find of dbg_sk.h, DIRECT included; the key run is a line of keys[] and one of keys_hi[])
+template <bool DIRECT = false>
 __device__ inline uint32_t wdir_find(const SkDirEnt *__restrict__ dirs, uint64_t ri, const uint64_t *__restrict__ keys,
-                                     const uint64_t *__restrict__ keys_hi, uint64_t n_nodes, K128 key, bool *whole = nullptr) {
+                                     const uint64_t *__restrict__ keys_hi, uint64_t n_nodes, K128 key, bool *whole = nullptr,
+                                     bool *direct = nullptr) {
     constexpr int NBLK = WCAP / 64;
     uint32_t slot = wslot_of(key);
     for (int blocks = 0; blocks <= NBLK; ++blocks) {
         const SkDirEnt de = dirs[ri * NBLK + (slot >> 6)];
-        if (whole && blocks == 0 && de.pad != 1u) { *whole = false; return NO_NODE; }
+        if (whole && blocks == 0 && !(de.pad & DIR_WHOLE_BUCKET)) { *whole = false; return NO_NODE; }
         const int bit = (int)(slot & 63);
+        if (DIRECT && whole && blocks == 0) {
+            uint64_t node;
+            if (dir_decide(de, bit, &node) && node < n_nodes) { *direct = true; return (uint32_t)node; }
+        }
         const unsigned long long run_bits = de.mask >> bit;
         if (!(run_bits & 1ull)) return NO_NODE;
         const int avail = 64 - bit;
@@ -1093,35 +1100,40 @@ __global__ __launch_bounds__(256) void k_wq_park(uint64_t n, const uint64_t *__r
 }
 
 // q_lo / q_hi: query i at [i * stride] (1: two arrays; 2: (lo, hi) pairs, q_hi = q_lo + 1).  id_tag is OR-ed into the ids.
+// DIRECT / COUNT: as k_succ_resolve.
+template <bool DIRECT, bool COUNT>
 __global__ __launch_bounds__(256) void k_wsucc_resolve(const uint64_t *__restrict__ q_lo, const uint64_t *__restrict__ q_hi,
                                                        int stride, const uint32_t *__restrict__ q_col, uint64_t n, SkGeom g,
                                                        const SkRange *__restrict__ ranges, uint64_t n_buckets, uint64_t n_ranges,
                                                        const SkDirEnt *__restrict__ dirs, const uint64_t *__restrict__ keys,
                                                        const uint64_t *__restrict__ keys_hi, uint64_t n_nodes, uint32_t *out,
-                                                       uint32_t id_tag, unsigned long long *scalars) {
+                                                       uint32_t id_tag, unsigned long long *scalars, unsigned long long *counts /* COUNT */) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const K128 key{q_hi[i * stride], q_lo[i * stride]};
-    const uint64_t bucket = sk_bucket_of(wkmer_bucket22(key, g.k, g.m), g);
-    uint32_t id = NO_NODE;
-    if (bucket >= g.own_lo && bucket < g.own_lo + g.own_cnt) {
-        bool whole = true;
-        id = wdir_find(dirs, bucket - g.own_lo, keys, keys_hi, n_nodes, key, &whole);
-        if (!whole) {
-            const uint32_t sh = wsub_hash(key);
-            uint32_t r = ranges[bucket].next;
-            uint64_t ri = 0;
-            bool have = false;
-            for (int guard = 0; r && r < n_ranges && !have && guard < (1 << 20); ++guard) {
-                const SkRange rg = ranges[r];
-                if (rg.node_cnt && (sh & rg.mask) == rg.val) { ri = r; have = true; }
-                r = rg.next;
+    bool direct = false;
+    if (i < n) {
+        const K128 key{q_hi[i * stride], q_lo[i * stride]};
+        const uint64_t bucket = sk_bucket_of(wkmer_bucket22(key, g.k, g.m), g);
+        uint32_t id = NO_NODE;
+        if (bucket >= g.own_lo && bucket < g.own_lo + g.own_cnt) {
+            bool whole = true;
+            id = wdir_find<DIRECT>(dirs, bucket - g.own_lo, keys, keys_hi, n_nodes, key, &whole, &direct);
+            if (!whole) {
+                const uint32_t sh = wsub_hash(key);
+                uint32_t r = ranges[bucket].next;
+                uint64_t ri = 0;
+                bool have = false;
+                for (int guard = 0; r && r < n_ranges && !have && guard < (1 << 20); ++guard) {
+                    const SkRange rg = ranges[r];
+                    if (rg.node_cnt && (sh & rg.mask) == rg.val) { ri = r; have = true; }
+                    r = rg.next;
+                }
+                if (have) id = wdir_find(dirs, g.own_cnt + (ri - n_buckets), keys, keys_hi, n_nodes, key);
             }
-            if (have) id = wdir_find(dirs, g.own_cnt + (ri - n_buckets), keys, keys_hi, n_nodes, key);
         }
+        if (id == NO_NODE) atomicOr(&scalars[0], STATUS_SUCC_MISSING);  // every successor k-mer exists as a node of its owner
+        else out[q_col ? q_col[i] : i] = id | id_tag;
     }
-    if (id == NO_NODE) { atomicOr(&scalars[0], STATUS_SUCC_MISSING); return; }  // every successor k-mer exists as a node of its owner
-    out[q_col ? q_col[i] : i] = id | id_tag;
+    if (COUNT) resolve_count(i < n, direct, counts);
 }
 
 static_assert(sizeof(WCntLds<uint64_t>) <= 160 * 1024 && sizeof(WCntLds<uint32_t>) <= 160 * 1024, "LDS of the two-word count kernel");
