@@ -106,6 +106,11 @@ __device__ inline uint64_t wave_sum_u64(uint64_t v) {
     return v;  // valid in lane 0
 }
 
+// lane i receives the value of lane i + 1 of its wave; lane 63 receives `last` (DPP wave shift: one VALU move, no LDS)
+__device__ inline uint32_t from_next_lane(uint32_t v, uint32_t last) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)last, (int)v, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
+}
+
 // ------------------------------------------------------------------------------------------
 // tile loader shared by k_count and k_pull_reads: TILE positions + 64 halo, as a big-endian
 // 2-bit stream in LDS (16 bases per dword) plus the matching slice of the read-start bitmap
@@ -128,32 +133,67 @@ struct TileLdsT {
 using TileLds = TileLdsT<HALO>;
 static_assert(TileLds::PK == PK_WORDS && TileLds::SB == SB_WORDS, "tile layout");
 
+// the 16 bytes of word v of a tile's 2-bit stream, from tile0 + 16 v on, 'A' where the reads (or the SPAN) end;
+// *in_reads: some of them are bytes < n_bytes
+template <class T>
+__device__ inline uint4 load_tile_bytes(const char *bases, uint64_t n_bytes, uint64_t tile0, int v, bool *in_reads) {
+    const uint64_t off = tile0 + (uint64_t)v * 16;
+    uint4 q = make_uint4(0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u);  // 'A' padding
+    *in_reads = v < T::SPAN / 16 && off < n_bytes;
+    if (*in_reads) {
+        if (off + 16 <= n_bytes) {
+            q = *reinterpret_cast<const uint4 *>(bases + off);
+        } else {
+            uint32_t w[4] = {0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u};
+            for (int b = 0; b < 16 && off + b < n_bytes; ++b) {
+                w[b >> 2] &= ~(0xFFu << (8 * (b & 3)));
+                w[b >> 2] |= (uint32_t)(uint8_t)bases[off + b] << (8 * (b & 3));
+            }
+            q = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+    }
+    return q;
+}
+// ... as 16 2-bit codes; *bad is set if a byte outside ACGT is among them (asked for bytes of the reads only)
+__device__ inline uint32_t pack_tile_word(uint4 q, bool in_reads, uint32_t *bad) {
+    const uint32_t ok = acgt_bytes(q.x) & acgt_bytes(q.y) & acgt_bytes(q.z) & acgt_bytes(q.w);
+    *bad |= (in_reads && ok != 0x80808080u);
+    return (pack4(q.x) << 24) | (pack4(q.y) << 16) | (pack4(q.z) << 8) | pack4(q.w);
+}
+
 // returns nonzero if a byte outside ACGT was seen among the bytes < n_bytes
+// Every lane issues all its loads before it converts the first: two words of the 2-bit stream per round, its word of the
+// few that PK has beyond a multiple of the block (the halo; they used to be a pass of their own that the rest of the block
+// spent at the barrier) and its start-bit words -- one trip to memory per tile instead of one after the other.
 template <class T>
 __device__ inline uint32_t load_tile(T &t, const char *bases, uint64_t n_bytes, const uint32_t *startbits,
                                      uint64_t tile0) {
     uint32_t bad = 0;
-    for (int v = threadIdx.x; v < T::PK; v += blockDim.x) {
-        const uint64_t off = tile0 + (uint64_t)v * 16;
-        uint4 q = make_uint4(0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u);  // 'A' padding
-        if (v < T::SPAN / 16 && off < n_bytes) {
-            if (off + 16 <= n_bytes) {
-                q = *reinterpret_cast<const uint4 *>(bases + off);
-            } else {
-                uint32_t w[4] = {0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u};
-                for (int b = 0; b < 16 && off + b < n_bytes; ++b) {
-                    w[b >> 2] &= ~(0xFFu << (8 * (b & 3)));
-                    w[b >> 2] |= (uint32_t)(uint8_t)bases[off + b] << (8 * (b & 3));
-                }
-                q = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-            const uint32_t ok = acgt_bytes(q.x) & acgt_bytes(q.y) & acgt_bytes(q.z) & acgt_bytes(q.w);
-            bad |= (ok != 0x80808080u);
-        }
-        t.pk[v] = (pack4(q.x) << 24) | (pack4(q.y) << 16) | (pack4(q.z) << 8) | pack4(q.w);
-    }
+    const int tid = threadIdx.x, bd = blockDim.x;
+    const int whole = T::PK >= bd ? T::PK / bd * bd : T::PK;  // words taken in rounds of the whole block
+    const int vt = whole + tid;
+    const bool tail = vt < T::PK;
     const uint64_t w0 = tile0 >> 5;
-    for (int v = threadIdx.x; v < T::SB; v += blockDim.x) t.sb[v] = startbits[w0 + v];
+    uint32_t s0 = 0, s1 = 0;
+    if (tid < T::SB) s0 = startbits[w0 + tid];
+    if (tid + bd < T::SB) s1 = startbits[w0 + tid + bd];
+    const uint4 pad = make_uint4(0x41414141u, 0x41414141u, 0x41414141u, 0x41414141u);
+    bool ct = false;
+    uint4 qt = pad;
+    if (tail) qt = load_tile_bytes<T>(bases, n_bytes, tile0, vt, &ct);
+    for (int v = tid; v < whole; v += 2 * bd) {
+        const int v1 = v + bd;
+        bool c0, c1 = false;
+        const uint4 q0 = load_tile_bytes<T>(bases, n_bytes, tile0, v, &c0);
+        uint4 q1 = pad;
+        if (v1 < whole) q1 = load_tile_bytes<T>(bases, n_bytes, tile0, v1, &c1);
+        t.pk[v] = pack_tile_word(q0, c0, &bad);
+        if (v1 < whole) t.pk[v1] = pack_tile_word(q1, c1, &bad);
+    }
+    if (tail) t.pk[vt] = pack_tile_word(qt, ct, &bad);
+    if (tid < T::SB) t.sb[tid] = s0;
+    if (tid + bd < T::SB) t.sb[tid + bd] = s1;
+    for (int v = tid + 2 * bd; v < T::SB; v += bd) t.sb[v] = startbits[w0 + v];
     return bad;
 }
 

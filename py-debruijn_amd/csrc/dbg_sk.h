@@ -14,6 +14,7 @@
 #include <cstddef>
 #include "dbg_device.h"
 #include "dbg_dir.h"
+#include "dbg_minwin.h"
 
 namespace dbgk {
 
@@ -33,9 +34,7 @@ __host__ __device__ inline uint32_t fmix32(uint32_t x) {
     x ^= x >> 16;
     return x;
 }
-// m <= 13: an m-mer is at most 26 bits.  Minimizer order = 16-bit hash, ties to the leftmost.
-// one multiply: the minimizer order only has to look random, and this hash runs ~1.6x per base
-__device__ inline uint32_t mmer_hash16(uint32_t mmer) { return ((mmer ^ (mmer >> 9) ^ 0x3C6EF372u) * 0x9E3779B1u) >> 16; }
+// (mmer_hash16, the minimizer order: dbg_minwin.h)
 __device__ inline uint32_t bucket_hash22(uint32_t mmer) { return fmix32(mmer * 0x9E3779B1u + 0x7F4A7C15u) >> (32 - SK_BUCKET_BITS); }
 
 // minimizer-hash bucket of a single packed k-mer (pure function of the k-mer)
@@ -201,18 +200,21 @@ __global__ __launch_bounds__(256) void k_sk_extract(const char *__restrict__ bas
 }
 
 // Fast extraction for m = 13 and a compile-time window W = k - 12 (k = 31 -> W = 19).
-// Every lane owns 32 consecutive positions: it reads 64 bases and 64 read-start bits once, rolls
-// the 32 + W - 1 m-mer hashes it needs in registers and takes the sliding-window minimum with
-// the van Herk / Gil-Werman block scheme (about 4 min ops per position instead of W LDS reads).
-// Hash and leftmost tie-break are the same as in the generic kernel: packed = hash16 << 8 | offset.
+// Every lane owns 32 consecutive positions: it reads 64 bases and 64 read-start bits once, hashes the 32 m-mers that
+// start at its own positions, takes the W - 1 hashes its windows reach beyond them from the next lane (a DPP shift; the
+// W - 1 m-mers behind a wave's last position are hashed by W - 1 lanes of the wave and handed to lane 63 through LDS) and
+// takes the sliding-window minimum with the van Herk / Gil-Werman block scheme (about 3 min ops per position instead of
+// W LDS reads).  Hash and leftmost tie-break are the same as in the generic kernel; the per-lane arithmetic is
+// dbg_minwin.h, which a host test runs too.
 struct SkLdsW {
     TileLds t;
-    uint8_t minp[TILE];
+    uint8_t minp[TILE];             // index byte of every position, 32 per lane in the order of index_byte_at()
     unsigned long long sbits[TILE / 64 + 1];
     unsigned long long vbits[TILE / 64 + 1];
     uint32_t wpre[TILE / 64 + 1];
     uint16_t list[TILE];            // record index -> start position (dense work list)
     uint8_t edge[256];
+    alignas(16) uint32_t nx[4][20]; // per wave: packed values 32 .. NV - 1 of its lane 63
     uint32_t nrec;
 };
 
@@ -254,7 +256,6 @@ __global__ __launch_bounds__(256, DBG_EXW_WAVES) void k_sk_extract_w(const char 
     const uint64_t t_beg = tile_first + n_tiles * blockIdx.x / gridDim.x, t_end = tile_first + n_tiles * (blockIdx.x + 1) / gridDim.x;
     const uint64_t seg0 = (uint64_t)blockIdx.x * seg_cap;  // !PS: this workgroup's one segment and the records in it so far
     uint64_t cursor = 0;
-    constexpr uint32_t mid_mask = (1u << (K - 1)) - 1u;
     uint64_t n_k = 0, n_e = 0;
     bool overflow = false;
     const int j0 = threadIdx.x * 32;
@@ -269,12 +270,17 @@ __global__ __launch_bounds__(256, DBG_EXW_WAVES) void k_sk_extract_w(const char 
         __syncthreads();
         // ---- register phase
         const uint64_t wa = window32(s.t, j0), wb = window32(s.t, j0 + 32);
-        uint32_t pv[NV], P[NV];
+        uint32_t pv[NV];
 #pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const uint64_t win = (i == 0) ? wa : (i < 32) ? ((wa << (2 * i)) | (wb >> (64 - 2 * i))) : (i == 32) ? wb : (wb << (2 * (i - 32)));
-            pv[i] = (mmer_hash16((uint32_t)(win >> (64 - 2 * M))) << 8) | (uint32_t)i;
-            P[i] = (i % W == 0) ? pv[i] : min(P[i - 1], pv[i]);
+        for (int i = 0; i < 32; ++i) {
+            const uint64_t win = (i == 0) ? wa : ((wa << (2 * i)) | (wb >> (64 - 2 * i)));
+            pv[i] = mmer_packed((uint32_t)(win >> (64 - 2 * M)), (uint32_t)i);
+        }
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if constexpr (W > 1) {  // the m-mers behind this wave's 2048 positions (wave 3: in the tile's halo), one per lane
+            if (lane < W - 1)
+                s.nx[wave][lane] = mmer_packed((uint32_t)(window32(s.t, (wave + 1) * 2048 + lane) >> (64 - 2 * M)), 32u + (uint32_t)lane);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // read back by this wave alone: LDS serves a wave in order
         }
         const uint64_t sb64 = ((uint64_t)s.t.sb[(j0 >> 5) + 1] << 32) | s.t.sb[j0 >> 5];
         // a k-mer at position q is valid iff no read starts at q + 1 .. q + K - 1, not both at q and q + K (a read of
@@ -284,39 +290,28 @@ __global__ __launch_bounds__(256, DBG_EXW_WAVES) void k_sk_extract_w(const char 
         const uint64_t left = n_bytes > tile0 + (uint64_t)j0 ? n_bytes - (tile0 + (uint64_t)j0) : 0;
         const uint32_t inside = left >= 32 ? 0xFFFFFFFFu : ((1u << (uint32_t)left) - 1u);
         const uint32_t vmask = ~(uint32_t)window_or64<K - 1>(sb64 >> 1) & ~(skmask & (uint32_t)sb64) & inside;
-        (void)mid_mask;
         n_k += __popc(vmask);
         n_e += __popc(vmask & ~skmask);
-        uint32_t off[32];
-        {
-            uint32_t S = 0xFFFFFFFFu;
+        if constexpr (W > 1) {
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-            for (int i = NV - 1; i >= 0; --i) {
-                S = (i % W == W - 1 || i == NV - 1) ? pv[i] : min(S, pv[i]);
-                if (i < 32) {
-                    const uint32_t mn = (i % W == 0) ? P[i + W - 1] : min(S, P[i + W - 1]);
-                    off[i] = ((vmask >> i) & 1u) ? ((mn & 0xFFu) - (uint32_t)i) : 0xFFu;
-                }
-            }
+            for (int i = 0; i < W - 1; ++i) pv[32 + i] = from_next_lane(pv[i] + 32u, s.nx[wave][i]);
+        }
+        uint32_t D[8];
+        {
+            uint32_t mn[32];
+            window_min32<W>(pv, mn);
+            pack_index_bytes(mn, vmask, D);
         }
 #pragma unroll
-        for (int q = 0; q < 32; q += 4)
-            reinterpret_cast<uint32_t *>(s.minp)[(j0 + q) >> 2] = off[q] | (off[q + 1] << 8) | (off[q + 2] << 16) | (off[q + 3] << 24);
-        s.edge[threadIdx.x] = (uint8_t)off[31];
+        for (int g = 0; g < 8; ++g) reinterpret_cast<uint32_t *>(s.minp)[threadIdx.x * 8 + g] = D[g];
+        s.edge[threadIdx.x] = (uint8_t)edge_index_byte(D);
         reinterpret_cast<uint32_t *>(s.vbits)[threadIdx.x] = vmask;
         __syncthreads();
-        uint32_t smask = 0;
-        {
-            uint32_t prev = threadIdx.x ? (uint32_t)s.edge[threadIdx.x - 1] : 0xFFu;
-#pragma unroll
-            for (int q = 0; q < 32; ++q) {
-                // new record unless the previous position holds a k-mer with the same minimizer occurrence
-                const bool st = (off[q] != 0xFFu) && (prev == 0xFFu || prev != off[q] + 1);
-                smask |= (uint32_t)st << q;
-                prev = off[q];
-            }
-            reinterpret_cast<uint32_t *>(s.sbits)[threadIdx.x] = smask;
-        }
+        // new record unless the previous position holds a k-mer with the same minimizer occurrence
+        const uint32_t smask = record_starts(D, threadIdx.x ? (uint32_t)s.edge[threadIdx.x - 1] : MW_NONE, vmask);
+        reinterpret_cast<uint32_t *>(s.sbits)[threadIdx.x] = smask;
         __syncthreads();
         if (threadIdx.x < 64) {
             uint32_t a = __popcll(s.sbits[threadIdx.x]), b = __popcll(s.sbits[threadIdx.x + 64]);
@@ -375,7 +370,7 @@ __global__ __launch_bounds__(256, DBG_EXW_WAVES) void k_sk_extract_w(const char 
             if (nb < 32) { w0 &= ~0ull << (64 - 2 * nb); hi = 0; }
             else if (nb == 32) hi = 0;
             else hi &= ~0ull << (64 - 2 * (nb - 32));
-            const uint32_t mp = j + s.minp[j];
+            const uint32_t mp = (j & ~31) + s.minp[(j & ~31) + index_byte_at(j & 31)];
             const uint32_t bh = bucket_hash22((uint32_t)(window32(s.t, mp) >> (64 - 2 * M)));
             const uint64_t w1 = (hi & (~0ull << SK_META_BITS)) | ((uint64_t)bh << 6) | ((uint64_t)(len - 1) << 1) | has_succ;
             uint64_t o = gbase + r;  // PS: replaced below

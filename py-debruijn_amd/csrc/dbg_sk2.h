@@ -109,11 +109,6 @@ struct Cnt2Lds {
 #endif
 };
 
-// lane i receives the value of lane i + 1 of its wave; lane 63 receives `last` (DPP wave shift: one VALU move, no LDS)
-__device__ inline uint32_t from_next_lane(uint32_t v, uint32_t last) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)last, (int)v, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
-}
-
 // sum over the wave, valid in lane 63: four shifts inside the rows of 16 lanes, then the row totals are handed on
 // (row_bcast:15 -> rows 1 and 3, row_bcast:31 -> rows 2 and 3); VALU only
 __device__ inline uint32_t wave_sum_dpp(uint32_t v) {
