@@ -320,6 +320,8 @@ int dbg_get_stats(dbg_t *h, dbg_stats_t *out);
  * "extract_presplit_fallbacks": builds whose pre-split extraction overflowed a sub-segment and ran again without the split.
  * "extract_presplit_rehists": builds whose level 1 took another width than the pre-split extraction had counted its
  *   records for, so that the level ran its histogram pass after all.
+ * "refine_crowded" / "pull_crowded": dbg_refine_edge_order / dbg_mark_pull_reads calls (k <= 31) whose per-range kernel met a
+ *   range with more multi-successor / branch nodes than it has slots for, so that the pass over the reads ran instead.
  * "resolve_direct_hits" / "resolve_keyed": cross-bucket successor queries (dbg_shard_answer's included) answered from the
  *   directory entry alone / after reading keys; counted only while option "resolve_count" is 1.
  * DBG_E_ARG for an unknown name. */

@@ -77,7 +77,8 @@ class WalkBlock(C.Structure):
 
 # dbg_get_counter names that Graph.stats() reports.  resolve_*: queries the resolver answered from the directory entry alone /
 # after reading keys -- filled only under option "resolve_count" 1 (tests), by a counting instantiation of the resolver
-COUNTERS = ("extract_presplit_fallbacks", "extract_presplit_rehists", "resolve_direct_hits", "resolve_keyed")
+COUNTERS = ("extract_presplit_fallbacks", "extract_presplit_rehists", "resolve_direct_hits", "resolve_keyed",
+            "refine_crowded", "pull_crowded")
 
 
 class DbgError(RuntimeError):

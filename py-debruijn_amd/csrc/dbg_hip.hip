@@ -182,6 +182,7 @@ struct dbg {
     int extract_presplit = DBG_EXTRACT_PRESPLIT;  // option: dbg_build's extraction pre-splits its records by this many top bits of the bucket hash (0: off)
     uint64_t presplit_rehists = 0;  // builds whose level 1 took another width than the pre-split extraction counted for, so it ran its histogram pass (dbg_get_counter)
     uint64_t presplit_fallbacks = 0;  // builds whose pre-split extraction overflowed a sub-segment and ran again without the split (dbg_get_counter)
+    uint64_t refine_crowded = 0, pull_crowded = 0;  // dbg_refine_edge_order / dbg_mark_pull_reads calls whose per-range kernel met a crowded range and fell back to the pass over the reads (dbg_get_counter)
     uint64_t sk_n_ranges = 0, sk_n_buckets = 0;
     SkGeom sk_geom{};            // hash -> bucket mapping of the last partitioned build (k_succ_resolve)
     void *shard_state = nullptr;  // ShardState (multi-GPU builds)
@@ -2764,6 +2765,7 @@ extern "C" int dbg_refine_edge_order(dbg_t *h) {
         HIPCHK(h, hipMemcpyAsync(&crowded, flag, 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         if (!crowded) { h->order_exact = true; return DBG_OK; }
+        ++h->refine_crowded;
         // a range with hundreds of multi-successor nodes: the streaming pass below recomputes every node
     }
     uint64_t n_multi = 0;
@@ -3136,6 +3138,7 @@ extern "C" int dbg_mark_pull_reads(dbg_t *h) {
             HIPCHK(h, hipMemcpyAsync(&crowded, flag, 8, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
             by_range = !crowded;  // else: the pass over the reads below marks every read again (flags only ever go to 1)
+            if (crowded) ++h->pull_crowded;
         }
         if (by_range) {
         } else if (h->D == GEN_D)
@@ -3371,6 +3374,8 @@ extern "C" int dbg_get_counter(dbg_t *h, const char *name, uint64_t *out) {
     const std::string n(name);
     if (n == "extract_presplit_rehists") { *out = h->presplit_rehists; return DBG_OK; }
     if (n == "extract_presplit_fallbacks") { *out = h->presplit_fallbacks; return DBG_OK; }
+    if (n == "refine_crowded") { *out = h->refine_crowded; return DBG_OK; }
+    if (n == "pull_crowded") { *out = h->pull_crowded; return DBG_OK; }
     if (n == "resolve_direct_hits") { *out = h->resolve_direct_hits; return DBG_OK; }
     if (n == "resolve_keyed") { *out = h->resolve_keyed; return DBG_OK; }
     h->err = "unknown counter: " + n;

@@ -35,22 +35,26 @@ def test_lane_arithmetic_on_the_host(tmp_path):
 
 
 # ---- inputs -------------------------------------------------------------------------------------------------------------
-def random_reads(seed, total, starts_at=()):
-    """Uniform ACGT reads of 31 .. 300 bases, `total` bytes in all; a read starts at each position of starts_at."""
+def random_reads(seed, total, starts_at=(), min_len=31):
+    """Uniform ACGT reads of min_len .. 300 bases, `total` bytes in all; a read starts at each position of starts_at.  An entry
+    (start, length) of starts_at asks for a read of exactly that length there (any length; its bases are uniform too)."""
     rng = np.random.default_rng(seed)
-    goals = sorted(starts_at) + [total]
+    fixed = sorted((g, 0) if np.isscalar(g) else (int(g[0]), int(g[1])) for g in starts_at)
     offsets = [0]
-    for goal in goals:
+    for goal, length in fixed + [(total, 0)]:
         while offsets[-1] < goal:
             gap = goal - offsets[-1]
             if gap <= 300:
                 n = gap
             else:
-                n = int(rng.integers(31, 301))
-                if gap - n < 31:
-                    n = gap - 31
-            assert 31 <= n <= 300
+                n = int(rng.integers(min_len, 301))
+                if gap - n < min_len:
+                    n = gap - min_len
+            assert min_len <= n <= 300
             offsets.append(offsets[-1] + n)
+        assert offsets[-1] == goal
+        if length:
+            offsets.append(goal + length)
     bases = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=total)]
     return np.ascontiguousarray(bases), np.array(offsets, dtype=np.uint64)
 
@@ -164,7 +168,8 @@ def test_inputs_exercise_the_borders(name, k):
 
 # ---- builds -------------------------------------------------------------------------------------------------------------
 def build(bases, offsets, k, **opts):
-    """Nodes in stamp order (keys, stamps, counts, successors as stamps), sizes() and three stats() of a fresh handle's build."""
+    """Nodes in stamp order (keys, keys_hi, stamps, counts, successors as stamps and as rows of that order), sizes() and three
+    stats() of a fresh handle's build."""
     g = _dbg.Graph()
     try:
         for name, v in opts.items():
@@ -172,12 +177,17 @@ def build(bases, offsets, k, **opts):
         g.set_reads(bases, offsets)
         g.build(k)
         keys, stamps, counts, _ = g.export_nodes()
+        hi = g.export_keys_hi()
         succ = g.export_succ()
         present = succ != NO_NODE
         succ_stamps = np.where(present, stamps[np.where(present, succ, 0)].astype(np.int64), np.int64(-1))
         o = np.argsort(stamps, kind="stable")
+        row = np.empty(o.size, dtype=np.int64)
+        row[o] = np.arange(o.size)
+        succ_rows = np.where(present, row[np.where(present, succ, 0)], np.int64(-1))
         st = g.stats()
-        return {"keys": keys[o], "stamps": stamps[o].astype(np.uint64), "counts": counts[o], "succ_stamps": succ_stamps[o],
+        return {"keys": keys[o], "keys_hi": hi[o], "stamps": stamps[o].astype(np.uint64), "counts": counts[o],
+                "succ_stamps": succ_stamps[o], "succ": succ_rows[o],
                 "sizes": g.sizes(), "stats": {f: st[f] for f in ("n_records", "n_buckets", "n_queries")}}
     finally:
         g.close()
