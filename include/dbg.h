@@ -47,8 +47,9 @@ typedef struct dbg dbg_t;
 #define DBG_E_CAPACITY (-4) /* hash table or an output limit was exceeded */
 #define DBG_E_NOMEM (-5)    /* host or device allocation failed */
 
-#define DBG_ABI_VERSION 6 /* not raised for dbg_build_from_walks: it only adds a symbol, every earlier call and struct is
-                            * unchanged, and tests/test_fasta_stream.py pins this number; a binding that needs the new
+#define DBG_ABI_VERSION 6 /* not raised for dbg_build_from_walks, nor for the query calls (dbg_lookup_nodes[_device],
+                            * dbg_gather_nodes, dbg_score_sequences): they only add symbols, every earlier call and struct is
+                            * unchanged, and tests/test_fasta_stream.py pins this number; a binding that needs a new
                             * call fails at symbol lookup on an older library */
 
 /* node flag bits (dbg_export_nodes: flags[]) */
@@ -146,7 +147,9 @@ int dbg_abi_version(void);
  * "extract_generic" 1: the window-minimum-through-LDS extraction kernels; "extract_presplit" f0 in 0..6: dbg_build's
  * extraction (13 <= k <= 31 over ACGT) writes its records pre-split by the top f0 bits of the bucket hash so that level 1 of
  * the multisplit has 2^f0 times fewer children per group (0: one segment per workgroup); "shard_stamp64" 1: dbg_shard_extract hands out
- * 64-bit rank-local stamps; "target_distinct": mean distinct k-mers per bucket the geometry aims at (0 = default). */
+ * 64-bit rank-local stamps; "target_distinct": mean distinct k-mers per bucket the geometry aims at (0 = default);
+ * "lookup_index" 1: the query calls (dbg_lookup_nodes, dbg_score_sequences) find nodes through the sorted index even where
+ * the build's directory would answer (test hook: both ways must agree). */
 int dbg_set_option(dbg_t *h, const char *name, int64_t value);
 
 /* ---- reads (replaces the `reads` list argument, debruijn.py:206; FASTA
@@ -324,6 +327,8 @@ int dbg_get_stats(dbg_t *h, dbg_stats_t *out);
  *   range with more multi-successor / branch nodes than it has slots for, so that the pass over the reads ran instead.
  * "resolve_direct_hits" / "resolve_keyed": cross-bucket successor queries (dbg_shard_answer's included) answered from the
  *   directory entry alone / after reading keys; counted only while option "resolve_count" is 1.
+ * "lookup_dir_calls" / "lookup_index_calls": dbg_lookup_nodes[_device] / dbg_score_sequences calls answered through the
+ *   build's directory / through the sorted index; "lookup_index_builds": sorts that built such an index (one per graph).
  * DBG_E_ARG for an unknown name. */
 int dbg_get_counter(dbg_t *h, const char *name, uint64_t *out);
 
@@ -368,6 +373,36 @@ int dbg_export_contig_text(dbg_t *h, uint64_t index, char *buf, uint64_t buf_len
 /* device-side views for callers that stay on the GPU (valid until the next build/destroy) */
 int dbg_device_views(dbg_t *h, const void **d_keys, const void **d_counts, const void **d_stamps,
                      const void **d_flags, const void **d_succ);
+
+/* ---- point queries on the current graph (the reference asks its dicts: `kmer in vertices`, `edges[kmer]`,
+ *      `edge_count_table[edge]`, getScore): answered on the device, nothing of size n_nodes moves.
+ *      They work on the graph of dbg_build (both engines, ACGT at k = 1..63; any other alphabet at k <= 11),
+ *      dbg_build_from_walk(s) and dbg_import_graph, before and after prune, tips and walk.  DBG_E_ARG (text in
+ *      dbg_last_error) without a graph, for a graph in parts (dbg_build_multipass), for one shard of several, and for the
+ *      generic alphabet at k >= 12, whose nodes have no packed key.  n = 0 returns DBG_OK and touches nothing.
+ *      Two ways to a node, same answers: where the handle still holds the directory of the build that made the graph (a
+ *      single-GPU dbg_build on the partitioned engines, k <= 31 and k > 31) a query costs its bucket hash, one directory
+ *      entry and one run of keys, and no memory.  Every other graph (engine 1, "wide_engine" 0, generic, from walks,
+ *      imported) gets a sorted index on the first lookup: one device radix sort of (keys_hi, keys, id), 12 B per node
+ *      (20 B for two-word keys) kept until the next build, import, change of reads or dbg_destroy, plus the same again as
+ *      scratch while it is sorted; a query is then a binary search. */
+/* node id (row in table order, as in dbg_export_nodes) of n k-mers, DBG_NO_NODE where the k-mer is no node.
+ * keys_hi NULL = all zero; for k <= 31 a non-zero keys_hi[i], or key bits above 2k (5k), mean "absent". */
+int dbg_lookup_nodes(dbg_t *h, const uint64_t *keys, const uint64_t *keys_hi, uint64_t n, uint32_t *ids);
+int dbg_lookup_nodes_device(dbg_t *h, const void *d_keys, const void *d_keys_hi, uint64_t n, void *d_ids);
+/* rows of n nodes, any output may be NULL: keys, keys_hi, stamps u64[n]; counts u32[n][D]; flags u8[n];
+ * keepmask u32[n]; order / fsorder u8[n] (D == 4) or u8[n][32] (D == 32) -- the same values the whole-graph
+ * exports give at those rows (and their preconditions: keepmask after dbg_prune, fsorder of ACGT graphs after
+ * dbg_refine_edge_order).  DBG_E_ARG for an id >= n_nodes. */
+int dbg_gather_nodes(dbg_t *h, const uint32_t *ids, uint64_t n, uint64_t *keys, uint64_t *keys_hi, uint64_t *stamps,
+                     uint32_t *counts, uint8_t *flags, uint32_t *keepmask, uint8_t *order, uint8_t *fsorder);
+/* getScore (II_assembleFromReads.py:14-18) of n_seq sequences (chars + offsets[n_seq + 1], host): scores[s] = sum over
+ * i in [0, len - k) of count(seq[i : i + k + 1]); first_missing[s] = smallest i whose (k+1)-mer is no edge of the graph
+ * (the reference raises KeyError there), UINT64_MAX if none -- then scores[s] is the reference's value.  A sequence of
+ * len <= k scores 0.  A character outside the graph's alphabet makes every window that holds it missing.
+ * The text goes to the device once; the work is split over the windows of the concatenated text, not over sequences. */
+int dbg_score_sequences(dbg_t *h, const char *chars, const uint64_t *offsets, uint64_t n_seq, uint64_t *scores,
+                        uint64_t *first_missing);
 
 /* ---- multi-GPU: hash-prefix sharding (no reference counterpart: the reference is one process).
  *      One handle per rank; the caller moves the buffers between ranks (RCCL all-to-all).  Owner

@@ -21,7 +21,10 @@ from debruijn import read_reads, read_reads_device
 
 def getScore(edge_count_table, contig, k):
     """II_assembleFromReads.py:14-18: the counts of all (k+1)-mers of a contig, added up.  Host version of the score the
-    walk kernels attach to every contig (``ContigList.scores`` / ``get_score_device``); kept for callers that import it."""
+    walk kernels attach to every contig (``ContigList.scores`` / ``get_score_device``); kept for callers that import it.
+    A lazy table of a large graph (debruijn.LAZY_MIN_NODES) is asked on the device: no array of the graph is exported."""
+    if type(edge_count_table) is db._LazyEdgeCounts:
+        return db.score_sequences(edge_count_table, [contig], k)[0]
     return sum(edge_count_table[contig[i:i + k + 1]] for i in range(len(contig) - k))
 
 

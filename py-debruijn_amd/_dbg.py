@@ -37,6 +37,7 @@ SYMBOLS = (
     "dbg_part_prune", "dbg_part_select", "dbg_part_gather", "dbg_part_mark", "dbg_part_clear", "dbg_part_cross_targets",
     "dbg_part_segments", "dbg_part_pflags", "dbg_scan_reads_for_keys", "dbg_set_orders", "dbg_part_segment_text",
     "dbg_build_from_walk", "dbg_build_from_walks",
+    "dbg_lookup_nodes", "dbg_lookup_nodes_device", "dbg_gather_nodes", "dbg_score_sequences",
 )
 
 
@@ -77,8 +78,10 @@ class WalkBlock(C.Structure):
 
 # dbg_get_counter names that Graph.stats() reports.  resolve_*: queries the resolver answered from the directory entry alone /
 # after reading keys -- filled only under option "resolve_count" 1 (tests), by a counting instantiation of the resolver
+# lookup_*: which way the query calls found their nodes (the build's directory / the sorted index) and how often such an
+# index was built
 COUNTERS = ("extract_presplit_fallbacks", "extract_presplit_rehists", "resolve_direct_hits", "resolve_keyed",
-            "refine_crowded", "pull_crowded")
+            "refine_crowded", "pull_crowded", "lookup_index_builds", "lookup_dir_calls", "lookup_index_calls")
 
 
 class DbgError(RuntimeError):
@@ -189,6 +192,10 @@ def load_library():
         "dbg_import_graph": (C.c_int, [H, C.c_int, C.c_int, u64p, vp, vp, vp, vp, vp]),
         "dbg_device_keys_hi": (C.c_int, [H, C.POINTER(vp)]),
         "dbg_reads_device": (C.c_int, [H, C.POINTER(vp), u64p, C.POINTER(vp), u64p]),
+        "dbg_lookup_nodes": (C.c_int, [H, vp, vp, C.c_uint64, vp]),
+        "dbg_lookup_nodes_device": (C.c_int, [H, vp, vp, C.c_uint64, vp]),
+        "dbg_gather_nodes": (C.c_int, [H, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "dbg_score_sequences": (C.c_int, [H, vp, vp, C.c_uint64, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -512,6 +519,68 @@ class Graph:
         self._chk(self._lib.dbg_export_sorted_fasta(self._h, _ptr(order) if order.size else None, _ptr(buf) if buf.size else None,
                                                     buf.size, C.byref(n)))
         return buf.tobytes(), order
+
+    # ---- point queries on the current graph (nothing of size n_nodes leaves the device)
+    def lookup_nodes(self, keys, keys_hi=None):
+        """Node ids (rows in table order, uint32) of packed k-mers; NO_NODE where the k-mer is no node.  keys / keys_hi:
+        numpy uint64 arrays (keys_hi None: all zero), or int64 torch tensors on this handle's device -- then the ids
+        come back as an int32 device tensor (dbg_lookup_nodes_device)."""
+        if not isinstance(keys, np.ndarray) and hasattr(keys, "data_ptr"):
+            import torch
+            ids = torch.empty(keys.numel(), dtype=torch.int32, device=keys.device)
+            self._chk(self._lib.dbg_lookup_nodes_device(self._h, C.c_void_p(keys.data_ptr()) if keys.numel() else None,
+                                                        C.c_void_p(keys_hi.data_ptr()) if keys_hi is not None and keys_hi.numel() else None,
+                                                        keys.numel(), C.c_void_p(ids.data_ptr()) if keys.numel() else None))
+            return ids
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        hi = None if keys_hi is None else np.ascontiguousarray(keys_hi, dtype=np.uint64).reshape(-1)
+        if hi is not None and hi.size != k.size:
+            raise ValueError("keys and keys_hi differ in length")
+        ids = np.empty(k.size, dtype=np.uint32)
+        self._chk(self._lib.dbg_lookup_nodes(self._h, _ptr(k) if k.size else None, _ptr(hi) if hi is not None and hi.size else None,
+                                             k.size, _ptr(ids) if k.size else None))
+        return ids
+
+    GATHER_COLUMNS = ("keys", "keys_hi", "stamps", "counts", "flags", "keepmask", "order", "fsorder")
+
+    def gather_nodes(self, ids, what=GATHER_COLUMNS):
+        """Rows of the nodes ``ids`` -> dict of numpy arrays for the names in ``what``: the values the whole-graph
+        exports hold at those rows.  counts (n, max_degree); order / fsorder as export_orders returns them,
+        (n, max_degree) successor codes by rank."""
+        unknown = [w for w in what if w not in self.GATHER_COLUMNS]
+        if unknown:
+            raise ValueError(f"gather_nodes: unknown columns {unknown}")
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        n = ids.size
+        d = self.sizes()["max_degree"] if any(w in what for w in ("counts", "order", "fsorder")) else 4
+        shapes = {"keys": ((n,), np.uint64), "keys_hi": ((n,), np.uint64), "stamps": ((n,), np.uint64),
+                  "counts": ((n, d), np.uint32), "flags": ((n,), np.uint8), "keepmask": ((n,), np.uint32),
+                  "order": ((n,) if d == 4 else (n, d), np.uint8), "fsorder": ((n,) if d == 4 else (n, d), np.uint8)}
+        out = {w: np.empty(*shapes[w]) for w in what}
+        p = lambda w: _ptr(out[w]) if w in out and n else None  # noqa: E731
+        self._chk(self._lib.dbg_gather_nodes(self._h, _ptr(ids) if n else None, n, p("keys"), p("keys_hi"), p("stamps"),
+                                             p("counts"), p("flags"), p("keepmask"), p("order"), p("fsorder")))
+        if d == 4:  # packed: 2 bits per rank
+            sh = np.array([0, 2, 4, 6], dtype=np.uint8)[None, :]
+            for w in ("order", "fsorder"):
+                if w in out:
+                    out[w] = (out[w][:, None] >> sh) & 3
+        return out
+
+    def score_sequences(self, chars, offsets):
+        """getScore of the sequences chars[offsets[s]:offsets[s + 1]] against the current graph -> (scores uint64[n],
+        first_missing uint64[n]: index of the first (k+1)-mer that is no edge, 2**64 - 1 if none)."""
+        c = np.frombuffer(chars, dtype=np.uint8) if not isinstance(chars, np.ndarray) else chars
+        c = np.ascontiguousarray(c, dtype=np.uint8).reshape(-1)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if o.size < 1 or int(o[-1]) != c.size:
+            raise ValueError("offsets must hold n + 1 entries and end at len(chars)")
+        n = o.size - 1
+        scores = np.zeros(n, dtype=np.uint64)
+        miss = np.full(n, np.iinfo(np.uint64).max, dtype=np.uint64)
+        self._chk(self._lib.dbg_score_sequences(self._h, _ptr(c) if c.size else None, _ptr(o), n, _ptr(scores) if n else None,
+                                                _ptr(miss) if n else None))
+        return scores, miss
 
     # ---- read-support scores (IV_sortOutputs.py:10-15)
     def support_read_scores(self, read_chars, read_off, scores, is_float, contig_chars, contig_off):

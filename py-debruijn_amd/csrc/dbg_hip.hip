@@ -38,6 +38,7 @@
 #include "dbg_support.h"
 #include "dbg_wsk.h"
 #include "dbg_fasta.h"
+#include "dbg_lookup.h"
 
 using namespace dbgk;
 
@@ -210,6 +211,15 @@ struct dbg {
     uint64_t nk_reads = 0, nk_bytes = 0;
     std::vector<NkBlock> nk_blocks;
     uint8_t *d_nk_read_flags = nullptr;
+
+    // query side (dbg_lookup.h).  dir_valid: ar_dir, the SkRange array, sk_geom and sk_cap are those of the build that made
+    // the CURRENT graph (a single-GPU dbg_build on one of the LDS engines) -- set there, cleared by everything that replaces
+    // or reshapes the graph or reuses ar_dir; never inferred from ar_dir.p
+    bool dir_valid = false;
+    int lookup_index = 0;     // option "lookup_index" 1 (tests): the sorted index even where the directory is valid
+    Buf ar_lookup[3];         // sorted index of the current graph: keys, ids, keys_hi (two-word keys) -- 12 or 20 B per node
+    bool lookup_built = false;
+    uint64_t lookup_index_builds = 0, lookup_dir_calls = 0, lookup_index_calls = 0;  // dbg_get_counter
 
     dbg_stats_t stats{};
     dbg_ingest_stats_t ingest{};  // the last FASTA ingest
@@ -1576,6 +1586,9 @@ static const char *const kPartialGraph =
 static int nk_mark_contigs(dbg *h);
 static void free_build(dbg *h) {
     multipass_free(h);
+    h->dir_valid = false;
+    for (auto &b : h->ar_lookup) buf_free(h, b);  // the sorted index of dbg_lookup_nodes belongs to the graph that goes
+    h->lookup_built = false;
     dev_free(h->d_tab); dev_free(h->d_occ);
     if (h->nodes_in_arena) {
         h->d_keys = nullptr; h->d_stamps = nullptr; h->d_cnt = nullptr; h->d_flags = nullptr;
@@ -2467,6 +2480,7 @@ extern "C" int dbg_set_option(dbg_t *h, const char *name, int64_t value) {
     if (n == "resolve_count" && (value == 0 || value == 1)) { h->resolve_count = (int)value; return DBG_OK; }
     if (n == "wcount_kernel" && (value == 1 || value == 2)) { h->wcount_kernel = (int)value; return DBG_OK; }
     if (n == "count_kernel_u64" && value >= 1 && value <= 3) { h->count_kernel_u64 = (int)value; return DBG_OK; }
+    if (n == "lookup_index" && (value == 0 || value == 1)) { h->lookup_index = (int)value; return DBG_OK; }
     if (n == "shard_node_limit" && value >= 0 && value < (1ll << 29)) { h->shard_node_limit = (uint64_t)value; return DBG_OK; }
     h->err = "unknown option or value out of range: " + n;
     return DBG_E_ARG;
@@ -2597,10 +2611,12 @@ extern "C" int dbg_build(dbg_t *h, int k, uint64_t table_capacity_hint) {
     if (tentative) {
         Timer t_total(h->stream);
         int rc;
+        bool lds_engine = true;  // the build that succeeds below is one of the LDS engines: its directory stays
         if (k > 31) {
             bool fallback = true;
             rc = h->wide_engine == 1 ? build_wsk(h, k, &fallback) : DBG_E_CAPACITY;
             if (fallback && rc != DBG_E_ALPHABET) {
+                lds_engine = false;
                 free_build(h);
                 h->k = k;
                 h->stats = dbg_stats_t{};
@@ -2615,6 +2631,7 @@ extern "C" int dbg_build(dbg_t *h, int k, uint64_t table_capacity_hint) {
             if (rc != DBG_OK) { const std::string keep = h->err; free_build(h); h->err = keep; return rc; }
             h->alpha_known = true;  // ACGT, confirmed byte by byte
             h->is_dna = true;
+            h->dir_valid = lds_engine;
             h->stats.ms_build_total = t_total.stop();
             if (k <= 31) pool_trim(h);
             return DBG_OK;
@@ -2648,6 +2665,7 @@ extern "C" int dbg_build(dbg_t *h, int k, uint64_t table_capacity_hint) {
         }
         if (rc == DBG_OK) rc = finish_graph(h);
         if (rc != DBG_OK) { const std::string keep = h->err; free_build(h); h->err = keep; return rc; }
+        h->dir_valid = !fallback;
         h->stats.ms_build_total = t_total.stop();
         return DBG_OK;
     }
@@ -2656,6 +2674,7 @@ extern "C" int dbg_build(dbg_t *h, int k, uint64_t table_capacity_hint) {
         int rc = build_sk(h, k, table_capacity_hint);
         if (rc == DBG_OK) rc = finish_graph(h);
         if (rc != DBG_OK) { const std::string keep = h->err; free_build(h); h->err = keep; return rc; }
+        h->dir_valid = true;
         h->stats.ms_build_total = t_total.stop();
         pool_trim(h);  // no-op in the steady state: the arenas only grow
         return DBG_OK;
@@ -3378,6 +3397,9 @@ extern "C" int dbg_get_counter(dbg_t *h, const char *name, uint64_t *out) {
     if (n == "pull_crowded") { *out = h->pull_crowded; return DBG_OK; }
     if (n == "resolve_direct_hits") { *out = h->resolve_direct_hits; return DBG_OK; }
     if (n == "resolve_keyed") { *out = h->resolve_keyed; return DBG_OK; }
+    if (n == "lookup_index_builds") { *out = h->lookup_index_builds; return DBG_OK; }
+    if (n == "lookup_dir_calls") { *out = h->lookup_dir_calls; return DBG_OK; }
+    if (n == "lookup_index_calls") { *out = h->lookup_index_calls; return DBG_OK; }
     h->err = "unknown counter: " + n;
     return DBG_E_ARG;
 }
@@ -3583,6 +3605,228 @@ extern "C" int dbg_device_views(dbg_t *h, const void **d_keys, const void **d_co
     if (d_flags) *d_flags = h->d_flags;
     if (d_succ) *d_succ = h->d_succ;
     return DBG_OK;
+}
+
+// ==========================================================================================
+// query side (dbg_lookup.h): dbg_lookup_nodes, dbg_gather_nodes, dbg_score_sequences
+// ==========================================================================================
+// The current graph answers point queries: whole (not in parts, not one shard of several) and with packed keys.
+static int lookup_ready(dbg *h) {
+    if (!h->k) { h->err = "no graph: dbg_build must run first"; return DBG_E_ARG; }
+    if (h->multipass) { h->err = kMultipassGraph; return DBG_E_ARG; }
+    if (h->partial_graph) { h->err = kPartialGraph; return DBG_E_ARG; }
+    if (!h->d_keys) { h->err = "the nodes of this graph have no packed key (generic alphabet, k >= 12): no lookup by key"; return DBG_E_ARG; }
+    return DBG_OK;
+}
+
+// (keys_hi, keys, id) of the current graph sorted by k-mer, built on the first lookup that needs it
+static int lookup_index_ensure(dbg *h) {
+    if (h->lookup_built) return DBG_OK;
+    const uint64_t n = h->n_nodes;
+    if (n > 0x7FFFFFFFull) { h->err = "too many nodes for one sort"; return DBG_E_CAPACITY; }
+    const bool two = h->d_keys_hi != nullptr;
+    CHK(buf_ensure(h, h->ar_lookup[0], n * 8));
+    CHK(buf_ensure(h, h->ar_lookup[1], n * 4));
+    if (two) CHK(buf_ensure(h, h->ar_lookup[2], n * 8));
+    if (n) {
+        uint64_t *lo_s = (uint64_t *)h->ar_lookup[0].p, *hi_s = (uint64_t *)h->ar_lookup[2].p, *hi_g = nullptr;
+        uint32_t *id_s = (uint32_t *)h->ar_lookup[1].p, *ids = nullptr, *ids1 = nullptr;
+        void *tmp = nullptr;
+        int rc = DBG_OK;
+        do {
+            if ((rc = dev_alloc(h, &ids, n)) != DBG_OK) break;
+            hipLaunchKernelGGL(k_iota32, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, n, ids);
+            const unsigned lo_bits = (unsigned)std::min(64, h->sym_bits * h->k);
+            size_t tmp_bytes = 0, tmp2 = 0;
+            // radix sorts are stable: by the low word first, then (two-word keys) by the high word of the nodes in that order
+            uint32_t *first_out = two ? nullptr : id_s;
+            if (two && (rc = dev_alloc(h, &ids1, n)) != DBG_OK) break;
+            if (two) first_out = ids1;
+            hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, h->d_keys, lo_s, ids, first_out, (size_t)n, 0u, lo_bits, h->stream);
+            if (e == hipSuccess && two) {
+                e = rocprim::radix_sort_pairs(nullptr, tmp2, hi_s, hi_s, ids1, id_s, (size_t)n, 0u, 64u, h->stream);
+                tmp_bytes = std::max(tmp_bytes, tmp2);
+            }
+            if (e == hipSuccess) e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1);
+            if (e == hipSuccess)
+                e = rocprim::radix_sort_pairs(tmp, tmp_bytes, h->d_keys, lo_s, ids, first_out, (size_t)n, 0u, lo_bits, h->stream);
+            if (e == hipSuccess && two) {
+                if ((rc = dev_alloc(h, &hi_g, n)) != DBG_OK) break;
+                const unsigned hi_bits = (unsigned)std::max(1, 2 * h->k - 64);
+                hipLaunchKernelGGL(k_gather_u64, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, ids1, n, h->d_keys_hi, hi_g);
+                e = rocprim::radix_sort_pairs(tmp, tmp_bytes, hi_g, hi_s, ids1, id_s, (size_t)n, 0u, hi_bits, h->stream);
+                hipLaunchKernelGGL(k_gather_u64, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, id_s, n, h->d_keys, lo_s);
+            }
+            if (e == hipSuccess) e = hipGetLastError();
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            if (e != hipSuccess) { h->err = std::string("lookup index: ") + hipGetErrorString(e); rc = DBG_E_HIP; }
+        } while (0);
+        if (tmp) (void)hipFree(tmp);
+        dev_free(ids); dev_free(ids1); dev_free(hi_g);
+        if (rc != DBG_OK) return rc;
+    }
+    h->lookup_built = true;
+    ++h->lookup_index_builds;
+    return DBG_OK;
+}
+
+// Runs fn(finder) with the finder of the current graph: the directory where the handle still holds the one of the build
+// that made this graph, else (or under option "lookup_index") the sorted index.
+template <class FN>
+static int with_finder(dbg *h, FN &&fn) {
+    const bool dir = h->dir_valid && !h->lookup_index && h->ar_dir.p && h->ar_misc[MISC_RANGES].p &&
+                     (h->sk_cap == 2048 || h->sk_cap == 4096) && (h->k <= 31 || h->d_keys_hi);
+    if (dir) {
+        ++h->lookup_dir_calls;
+        const SkRange *ranges = (const SkRange *)h->ar_misc[MISC_RANGES].p;
+        const SkDirEnt *dirs = (const SkDirEnt *)h->ar_dir.p;
+        if (h->k > 31) return fn(LkWDirFinder{h->sk_geom, ranges, h->sk_n_buckets, h->sk_n_ranges, dirs, h->d_keys, h->d_keys_hi, h->n_nodes});
+        if (h->sk_cap == 2048) return fn(LkDirFinder<2048>{h->sk_geom, ranges, h->sk_n_buckets, h->sk_n_ranges, dirs, h->d_keys, h->n_nodes});
+        return fn(LkDirFinder<4096>{h->sk_geom, ranges, h->sk_n_buckets, h->sk_n_ranges, dirs, h->d_keys, h->n_nodes});
+    }
+    CHK(lookup_index_ensure(h));
+    ++h->lookup_index_calls;
+    return fn(LkIndexFinder{h->d_keys_hi ? (const uint64_t *)h->ar_lookup[2].p : nullptr, (const uint64_t *)h->ar_lookup[0].p,
+                            (const uint32_t *)h->ar_lookup[1].p, h->n_nodes});
+}
+
+extern "C" int dbg_lookup_nodes_device(dbg_t *h, const void *d_keys, const void *d_keys_hi, uint64_t n, void *d_ids) {
+    if (!h) return DBG_E_ARG;
+    if (!n) return DBG_OK;
+    if (!d_keys || !d_ids) { h->err = "dbg_lookup_nodes: null keys or ids"; return DBG_E_ARG; }
+    CHK(lookup_ready(h));
+    HIPCHK(h, hipSetDevice(h->device));
+    const LkMask m = lk_mask(h->sym_bits, h->k);
+    CHK(with_finder(h, [&](auto f) -> int {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lookup_nodes<decltype(f)>), dim3(grid_for(n, 256)), dim3(256), 0, h->stream, f,
+                           (const uint64_t *)d_keys, (const uint64_t *)d_keys_hi, n, m, (uint32_t *)d_ids);
+        HIPCHK(h, hipGetLastError());
+        return DBG_OK;
+    }));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DBG_OK;
+}
+
+extern "C" int dbg_lookup_nodes(dbg_t *h, const uint64_t *keys, const uint64_t *keys_hi, uint64_t n, uint32_t *ids) {
+    if (!h) return DBG_E_ARG;
+    if (!n) return DBG_OK;
+    if (!keys || !ids) { h->err = "dbg_lookup_nodes: null keys or ids"; return DBG_E_ARG; }
+    CHK(lookup_ready(h));
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t *d_k = nullptr, *d_hi = nullptr;
+    uint32_t *d_ids = nullptr;
+    int rc = DBG_OK;
+    do {
+        if ((rc = dev_alloc(h, &d_k, n)) != DBG_OK || (rc = dev_alloc(h, &d_ids, n)) != DBG_OK) break;
+        if (keys_hi && (rc = dev_alloc(h, &d_hi, n)) != DBG_OK) break;
+        hipError_t e = hipMemcpyAsync(d_k, keys, n * 8, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess && keys_hi) e = hipMemcpyAsync(d_hi, keys_hi, n * 8, hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) { h->err = std::string("dbg_lookup_nodes: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
+        if ((rc = dbg_lookup_nodes_device(h, d_k, d_hi, n, d_ids)) != DBG_OK) break;
+        e = hipMemcpy(ids, d_ids, n * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { h->err = std::string("dbg_lookup_nodes: ") + hipGetErrorString(e); rc = DBG_E_HIP; }
+    } while (0);
+    dev_free(d_k); dev_free(d_hi); dev_free(d_ids);
+    return rc;
+}
+
+extern "C" int dbg_gather_nodes(dbg_t *h, const uint32_t *ids, uint64_t n, uint64_t *keys, uint64_t *keys_hi, uint64_t *stamps,
+                                uint32_t *counts, uint8_t *flags, uint32_t *keepmask, uint8_t *order, uint8_t *fsorder) {
+    if (!h) return DBG_E_ARG;
+    if (!n) return DBG_OK;
+    if (!ids) { h->err = "dbg_gather_nodes: null ids"; return DBG_E_ARG; }
+    if (!h->k) { h->err = "no graph: dbg_build must run first"; return DBG_E_ARG; }
+    if (h->partial_graph) { h->err = kPartialGraph; return DBG_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(ensure_dense(h));  // refuses a graph in parts
+    if (keys && !h->d_keys) { h->err = "the nodes of this graph have no packed key (generic alphabet, k >= 12)"; return DBG_E_ARG; }
+    if (keepmask && !h->pruned) { h->err = "dbg_prune must run first"; return DBG_E_ARG; }      // dbg_export_keepmask
+    const bool gen = h->D == GEN_D;
+    if (fsorder && !gen && !h->d_fsorder) { h->err = "dbg_refine_edge_order must run first"; return DBG_E_ARG; }  // dbg_export_orders
+    const uint64_t ob = gen ? (uint64_t)GEN_D : 1;
+    // one device block for the ids, the status word and every output that was asked for
+    struct Out { void *host; uint64_t bytes, at; } outs[8] = {
+        {keys, n * 8, 0}, {keys_hi, n * 8, 0}, {stamps, n * 8, 0}, {counts, n * 4 * (uint64_t)h->D, 0}, {keepmask, n * 4, 0},
+        {flags, n, 0}, {order, n * ob, 0}, {fsorder, n * ob, 0}};
+    uint64_t total = 16 + ((n * 4 + 15) & ~15ull);
+    for (auto &o : outs) { o.at = total; if (o.host) total += (o.bytes + 15) & ~15ull; }
+    uint8_t *blk = nullptr;
+    CHK(dev_alloc(h, &blk, total));
+    int rc = DBG_OK;
+    do {
+        hipError_t e = hipMemsetAsync(blk, 0, 16, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(blk + 16, ids, n * 4, hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) { h->err = std::string("dbg_gather_nodes: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
+        auto dev = [&](int i) -> void * { return outs[i].host ? (void *)(blk + outs[i].at) : nullptr; };
+        LkGatherArgs a{h->d_keys, h->d_keys_hi, h->d_stamps, h->d_cnt, h->d_flags, gen ? h->d_keepmask : nullptr,
+                       gen ? h->d_rank_mc : h->d_order, gen ? h->d_rank_fs : h->d_fsorder,
+                       (uint64_t *)dev(0), (uint64_t *)dev(1), (uint64_t *)dev(2), (uint32_t *)dev(3), (uint8_t *)dev(5),
+                       (uint32_t *)dev(4), (uint8_t *)dev(6), (uint8_t *)dev(7), h->n_nodes, h->D};
+        hipLaunchKernelGGL(k_gather_nodes, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, a, (const uint32_t *)(blk + 16), n,
+                           (unsigned long long *)blk);
+        unsigned long long bad = 0;
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, blk, 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) { h->err = std::string("dbg_gather_nodes: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
+        if (bad) { h->err = "dbg_gather_nodes: a node id is not below n_nodes"; rc = DBG_E_ARG; break; }
+        for (auto &o : outs)
+            if (o.host && e == hipSuccess) e = hipMemcpyAsync(o.host, blk + o.at, o.bytes, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) { h->err = std::string("dbg_gather_nodes: ") + hipGetErrorString(e); rc = DBG_E_HIP; }
+    } while (0);
+    dev_free(blk);
+    return rc;
+}
+
+extern "C" int dbg_score_sequences(dbg_t *h, const char *chars, const uint64_t *offsets, uint64_t n_seq, uint64_t *scores,
+                                   uint64_t *first_missing) {
+    if (!h) return DBG_E_ARG;
+    if (!n_seq) return DBG_OK;
+    if (!offsets || !scores || !first_missing) { h->err = "dbg_score_sequences: null offsets, scores or first_missing"; return DBG_E_ARG; }
+    if (offsets[0] != 0) { h->err = "offsets[0] must be 0"; return DBG_E_ARG; }
+    for (uint64_t i = 0; i < n_seq; ++i)
+        if (offsets[i + 1] < offsets[i]) { h->err = "offsets must be non-decreasing"; return DBG_E_ARG; }
+    const uint64_t n_chars = offsets[n_seq];
+    if (n_chars && !chars) { h->err = "dbg_score_sequences: null chars"; return DBG_E_ARG; }
+    CHK(lookup_ready(h));
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(ensure_dense(h));
+    for (uint64_t i = 0; i < n_seq; ++i) { scores[i] = 0; first_missing[i] = ~0ull; }
+    if (n_chars <= (uint64_t)h->k) return DBG_OK;  // no sequence holds a (k+1)-mer
+    uint8_t lut[256];
+    memset(lut, LK_BAD_CODE, sizeof(lut));
+    if (h->D == GEN_D) for (int c = 0; c < h->n_sym && c < 32; ++c) lut[h->alphabet[c]] = (uint8_t)c;
+    else { lut['A'] = 0; lut['C'] = 1; lut['T'] = 2; lut['G'] = 3; }  // code = (ascii >> 1) & 3
+    // one device block: scores, first_missing, offsets, lut, text
+    const uint64_t at_miss = n_seq * 8, at_off = at_miss + n_seq * 8, at_lut = at_off + (n_seq + 1) * 8, at_txt = at_lut + 256;
+    uint8_t *blk = nullptr;
+    CHK(dev_alloc(h, &blk, at_txt + n_chars));
+    int rc = DBG_OK;
+    do {
+        hipError_t e = hipMemsetAsync(blk, 0, n_seq * 8, h->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(blk + at_miss, 0xFF, n_seq * 8, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(blk + at_off, offsets, (n_seq + 1) * 8, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(blk + at_lut, lut, 256, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(blk + at_txt, chars, n_chars, hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) { h->err = std::string("dbg_score_sequences: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
+        const unsigned grid = grid_for(n_chars - (uint64_t)h->k, LK_TILE);
+        rc = with_finder(h, [&](auto f) -> int {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_score_sequences<decltype(f)>), dim3(grid), dim3(LK_NT), 0, h->stream, f,
+                               (const char *)(blk + at_txt), n_chars, (const uint64_t *)(blk + at_off), n_seq,
+                               (const uint8_t *)(blk + at_lut), h->k, h->sym_bits, h->D, (const uint32_t *)h->d_cnt,
+                               (unsigned long long *)blk, (unsigned long long *)(blk + at_miss));
+            HIPCHK(h, hipGetLastError());
+            return DBG_OK;
+        });
+        if (rc != DBG_OK) break;
+        e = hipMemcpyAsync(scores, blk, n_seq * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(first_missing, blk + at_miss, n_seq * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) { h->err = std::string("dbg_score_sequences: ") + hipGetErrorString(e); rc = DBG_E_HIP; }
+    } while (0);
+    dev_free(blk);
+    return rc;
 }
 
 // ==========================================================================================
@@ -4114,6 +4358,7 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
     SkRange *ranges = (SkRange *)h->ar_misc[MISC_RANGES].p;
     // buckets this build owns (a shard or a pass owns 1 / 2^shard_bits of the level-1 groups): only they get a directory
     const uint64_t own_cnt = n_buckets >> shard_bits, own_lo = (uint64_t)my_shard * own_cnt;
+    h->dir_valid = false;  // the directory is rewritten: dbg_build says so when it is that of the finished graph
     CHK(buf_ensure(h, h->ar_dir, (own_cnt + (range_cap - n_buckets)) * (CAP / 64) * sizeof(SkDirEnt)));
     SkDirEnt *dirs = (SkDirEnt *)h->ar_dir.p;
     // k_sk_count2 for 32-bit stamps; with 64-bit stamps (sharded builds, reads of 2 GiB and more) its LDS leaves room for
@@ -4470,6 +4715,7 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
     const uint64_t range_cap = n_buckets + 4096 + n_inst / (WCAP / 4);
     CHK(buf_ensure(h, h->ar_misc[MISC_RANGES], range_cap * sizeof(SkRange)));
     SkRange *ranges = (SkRange *)h->ar_misc[MISC_RANGES].p;
+    h->dir_valid = false;  // as in sk_count_from_segments
     CHK(buf_ensure(h, h->ar_dir, (own_cnt + (range_cap - n_buckets)) * (WCAP / 64) * sizeof(SkDirEnt)));
     SkDirEnt *dirs = (SkDirEnt *)h->ar_dir.p;
     uint64_t *q_lo = nullptr, *q_hi = nullptr;
@@ -5424,6 +5670,7 @@ static int part_compact(dbg *sub, uint64_t n_dir_entries) {
     CHK(buf_shrink(sub, sub->ar_csr[3], (n + 1) * 4));
     CHK(buf_shrink(sub, sub->ar_csr[1], ne * 4));
     CHK(buf_shrink(sub, sub->ar_csr[2], ne * 4));
+    sub->dir_valid = false;  // a part's directory serves dbg_part_answer only
     CHK(buf_shrink(sub, sub->ar_dir, n_dir_entries * sizeof(SkDirEnt)));
     CHK(buf_shrink(sub, sub->ar_misc[MISC_RANGES], sub->sk_n_ranges * sizeof(SkRange)));
     sub->d_keys = (uint64_t *)sub->ar_node[0].p;

@@ -14,7 +14,9 @@ Differences a caller can observe, all documented in DESIGN.md:
   * ``output_contigs`` needs the objects returned by this module's ``construct_graph``;
   * graphs of ``LAZY_MIN_NODES`` (2e6, env ``DBG_LAZY_MIN_NODES``) or more nodes come back as read-only
     ``Mapping`` views over the exported arrays (label lookup, ``len``, ordered iteration; equal to the
-    reference's dicts when materialised) instead of Python dicts.
+    reference's dicts when materialised) instead of Python dicts.  A lookup of one label (``in``, ``[]``) is
+    answered on the device (dbg_lookup_nodes + dbg_gather_nodes) and exports nothing; iteration, ``len`` of
+    ``edges`` / ``edge_count_table`` and ``items()`` export the arrays, after which lookups are served from them.
 Everything else -- values AND orders (dict insertion order, ``Counter.most_common`` tie order,
 the append order of ``already_pull_out``, contig order) -- equals the reference.
 """
@@ -29,7 +31,7 @@ import numpy as np
 import _dbg
 
 __all__ = ["Node", "read_reads", "read_reads_device", "DeviceReads", "construct_graph", "output_contigs",
-           "get_score_device", "get_kmers", "get_graph_from_kmers"]
+           "get_score_device", "score_sequences", "get_kmers", "get_graph_from_kmers"]
 
 
 
@@ -139,12 +141,22 @@ class _Vertices(dict):
 LAZY_MIN_NODES = int(os.environ.get("DBG_LAZY_MIN_NODES", "2000000"))
 
 
+_STALE_VIEWS = ("these views belong to a graph that a later build on the same reads replaced: read them "
+                "(or dict() them) before the next construct_graph")
+_HOST = object()  # _NodeStore.device_row: this lookup is the host arrays' to answer
+
+
 class _NodeStore:
     """Host arrays of one graph (in the library's table order) + the dict-order permutation + label <-> index
     conversion.  Indices of this class's methods are positions in dict (first-occurrence) order; ``order[i]`` is the
-    row of node i in the arrays, so nothing of size n_nodes is gathered or sorted on the host up front."""
+    row of node i in the arrays, so nothing of size n_nodes is gathered or sorted on the host up front.
 
-    def __init__(self, k, alphabet, bits, n, loader):
+    While the arrays have not been loaded, one label is looked up on the device instead (``device_row``): the graph
+    handle finds the node and hands back its row, and nothing of size n_nodes moves."""
+
+    def __init__(self, k, alphabet, bits, n, loader, graph=None):
+        self._graph = graph
+        self._generation = None if graph is None else graph.generation
         self.k, self.alphabet, self.bits = k, alphabet, bits
         self.chars = alphabet.decode("latin-1")
         self.code_of = {ch: i for i, ch in enumerate(self.chars)}  # alphabet[code] = character
@@ -171,6 +183,29 @@ class _NodeStore:
     rank_fs = property(lambda self: self._get("rank_fs"))
     flags = property(lambda self: self._get("flags"))
     keep = property(lambda self: self._get("keep"))
+
+    def device_row(self, lab, what):
+        """The row of node ``lab`` (dict of the columns ``what``, one node each) from the device; None if ``lab`` is no
+        node; _HOST if the host arrays answer: they are loaded already, or the library does not look up this kind of
+        graph.  RuntimeError if a later build replaced the graph these views were made for."""
+        g = self._graph
+        if self._arrays is not None or g is None:
+            return _HOST
+        if g.generation != self._generation:
+            raise RuntimeError(_STALE_VIEWS)
+        e = self.encode(lab)
+        if e is None:
+            return None
+        try:
+            row = int(g.lookup_nodes(np.array([e[1]], dtype=np.uint64), np.array([e[0]], dtype=np.uint64))[0])
+            if row == _dbg.NO_NODE:
+                return None
+            return g.gather_nodes([row], what) if what else {}
+        except _dbg.DbgError as err:
+            if err.code != _dbg.DBG_E_ARG:
+                raise
+            self._graph = None  # refused (a graph the query calls do not cover): the host path from now on
+            return _HOST
 
     def rows(self, idx):
         return self.order[np.asarray(idx, dtype=np.int64)]
@@ -235,11 +270,12 @@ class _NodeStore:
     def successors(self, i, pruned):
         """Successor labels of node i: Counter.most_common order; only the kept ones when `pruned`."""
         r = self.order[i]
-        lab = self.row_labels([r])[0]
-        c = self.counts[r]
+        return self.ranked_successors(self.row_labels([r])[0], self.counts[r], self.rank_mc[r], int(self.keep[r]), pruned)
+
+    def ranked_successors(self, lab, c, rank_mc, kp, pruned):
+        """Successor labels of the node ``lab`` from its row: counts, most_common ranks and keep mask."""
         nd = int(np.count_nonzero(c))
-        ranked = [int(code) for code in np.atleast_1d(self.rank_mc[r]) if code != 0xFF and c[code]][:nd]
-        kp = int(self.keep[r])
+        ranked = [int(code) for code in np.atleast_1d(rank_mc) if code != 0xFF and c[code]][:nd]
         return [lab[1:] + self.chars[code] for code in ranked if not pruned or (kp >> code) & 1]
 
     def edge_names(self, i):
@@ -268,9 +304,17 @@ class _LazyVertices(Mapping):
             yield from self._s.labels(np.arange(lo, min(lo + (1 << 16), self._s.n)))
 
     def __contains__(self, lab):
+        r = self._s.device_row(lab, ())
+        if r is not _HOST:
+            return r is not None
         return self._s.find(lab) >= 0
 
     def __getitem__(self, lab):
+        r = self._s.device_row(lab, ("flags", "counts"))
+        if r is not _HOST:
+            if r is None:
+                raise KeyError(lab)
+            return Node(lab, int(r["flags"][0] & _dbg.F_INDEG), int(np.count_nonzero(r["counts"][0])))
         i = self._s.find(lab)
         if i < 0:
             raise KeyError(lab)
@@ -298,10 +342,18 @@ class _LazyEdges(Mapping):
             yield from self._s.labels(self._alive[lo:lo + (1 << 16)])
 
     def __contains__(self, lab):
+        r = self._s.device_row(lab, ("flags",))
+        if r is not _HOST:
+            return r is not None and not (r["flags"][0] & _dbg.F_PULLED)
         i = self._s.find(lab)
         return i >= 0 and not self._s.pulled(i)
 
     def __getitem__(self, lab):
+        r = self._s.device_row(lab, ("flags", "counts", "order", "keepmask"))
+        if r is not _HOST:
+            if r is None or r["flags"][0] & _dbg.F_PULLED:
+                raise KeyError(lab)
+            return self._s.ranked_successors(lab, r["counts"][0], r["order"][0], int(r["keepmask"][0]), True)
         i = self._s.find(lab)
         if i < 0 or self._s.pulled(i):
             raise KeyError(lab)
@@ -338,8 +390,14 @@ class _LazyEdgeCounts(Mapping):
     def __getitem__(self, name):
         if not isinstance(name, str) or len(name) != self._s.k + 1:
             raise KeyError(name)
-        i = self._s.find(name[:-1])
         code = self._s.code_of.get(name[-1])
+        r = self._s.device_row(name[:-1], ("counts",)) if code is not None else None
+        if r is not _HOST:
+            n = int(r["counts"][0][code]) if r is not None and code < r["counts"].shape[1] else 0
+            if not n:
+                raise KeyError(name)
+            return n
+        i = self._s.find(name[:-1])
         n = self._s.edge_count(i, code) if i >= 0 and code is not None else 0
         if not n:
             raise KeyError(name)
@@ -644,11 +702,10 @@ def construct_graph(reads, k, threshold=3, final=False):
 
         def load_later():
             if g.generation != generation:
-                raise RuntimeError("these views belong to a graph that a later build on the same reads replaced: read them "
-                                   "(or dict() them) before the next construct_graph")
+                raise RuntimeError(_STALE_VIEWS)
             return load_arrays()
 
-        store = _NodeStore(k, alphabet, bits, n_nodes, load_later)
+        store = _NodeStore(k, alphabet, bits, n_nodes, load_later, graph=g)
         vertices, edges, ect = _LazyVertices(store), _LazyEdges(store), _LazyEdgeCounts(store)
     else:
         a = load_arrays()
@@ -771,6 +828,37 @@ def output_contigs(g, branch_kmer, already_pull_out):
 def get_score_device(contigs):
     """getScore (II_assembleFromReads.py:14-18) of each contig as computed by the walk kernel."""
     return list(contigs.scores)
+
+
+def score_sequences(edge_count_table, sequences, k):
+    """``[getScore(edge_count_table, s, k) for s in sequences]`` (II_assembleFromReads.py:14-18) as a list of ints.
+
+    On the lazy table of a graph that still lives on the device this is one call (dbg_score_sequences): the text goes
+    over once and every (k+1)-mer window is looked up and added there.  On a dict -- or a lazy table whose graph the
+    library does not look up -- it is the reference's loop.  A sequence with a (k+1)-mer that is no edge raises KeyError
+    with that (k+1)-mer, for the first such window of the first such sequence: what the reference's loop raises."""
+    sequences = list(sequences)
+    store = getattr(edge_count_table, "_s", None)
+    g = getattr(store, "_graph", None) if type(edge_count_table) is _LazyEdgeCounts else None
+    if g is not None and store.k == k and all(type(s) is str for s in sequences):
+        if g.generation != store._generation:
+            raise RuntimeError(_STALE_VIEWS)
+        try:
+            chars, offsets = _pack_reads(sequences)
+            scores, miss = g.score_sequences(chars, offsets)
+        except ValueError:       # a character of more than one byte: no edge holds it, the loop below says where
+            scores = None
+        except _dbg.DbgError as err:
+            if err.code != _dbg.DBG_E_ARG:
+                raise
+            scores = None
+        if scores is not None:
+            bad = np.nonzero(miss != np.iinfo(np.uint64).max)[0]
+            if bad.size:
+                s, i = sequences[int(bad[0])], int(miss[bad[0]])
+                raise KeyError(s[i:i + k + 1])
+            return [int(x) for x in scores]
+    return [sum(edge_count_table[s[i:i + k + 1]] for i in range(len(s) - k)) for s in sequences]
 
 
 # ------------------------------------------------------------------------------------------------------------------
