@@ -119,6 +119,25 @@ typedef struct dbg_ingest_stats {
     double ms_parse;            /* device time of the parse kernels */
 } dbg_ingest_stats_t;
 
+/* what the last streamed contig output (dbg_write_contigs_fasta, or dbg_export_contig_texts with a text buffer) did */
+typedef struct dbg_contig_out_stats {
+    uint64_t bytes_written;     /* bytes handed to write() / copied into the caller's buffer */
+    uint64_t chunks;            /* windows filled on the device and copied to the host */
+    uint64_t chunk_bytes;       /* size of a window */
+    uint64_t peak_device_bytes; /* most device memory the call held at once: the two staging buffers and the per-record arrays
+                                 * (contig list, record positions: 12 B per record), or, before those, the sorts of the
+                                 * driver's order (two key and two id arrays, 24 B per contig, + the sort library's digit
+                                 * counters and look-back state, about n / 4 B).  At most
+                                 * 2 * chunk_bytes + 24 * (n + 1) + 1 MiB for n records while that last term stays below
+                                 * 2 * chunk_bytes + 1 MiB: up to ~4e6 contigs at 4096-byte windows, ~3e7 at the default;
+                                 * a caller's list sorts nothing and always keeps it */
+    uint64_t lift_bytes;        /* binary-lifting tables of the walk (index-only walks; built once per walk, kept by it) */
+    double ms_total;            /* wall time of the call */
+    double ms_io_wait;          /* host time in write() / in the copies into the caller's buffer */
+    double ms_fill;             /* device time of the fill kernel */
+    double ms_d2h;              /* device time of the staging copies */
+} dbg_contig_out_stats_t;
+
 /* ---- lifetime ---------------------------------------------------------- */
 int dbg_create(int device, dbg_t **out);
 void dbg_destroy(dbg_t *h);
@@ -149,7 +168,9 @@ int dbg_abi_version(void);
  * the multisplit has 2^f0 times fewer children per group (0: one segment per workgroup); "shard_stamp64" 1: dbg_shard_extract hands out
  * 64-bit rank-local stamps; "target_distinct": mean distinct k-mers per bucket the geometry aims at (0 = default);
  * "lookup_index" 1: the query calls (dbg_lookup_nodes, dbg_score_sequences) find nodes through the sorted index even where
- * the build's directory would answer (test hook: both ways must agree). */
+ * the build's directory would answer (test hook: both ways must agree);
+ * "ctgout_chunk_bytes": window size of the contig output calls where they are given none (dbg_export_contig_texts;
+ * dbg_write_contigs_fasta with chunk_bytes 0) -- a multiple of 4096, 0 = the library default of 4 MiB. */
 int dbg_set_option(dbg_t *h, const char *name, int64_t value);
 
 /* ---- reads (replaces the `reads` list argument, debruijn.py:206; FASTA
@@ -370,6 +391,25 @@ int dbg_export_sorted_fasta(dbg_t *h, uint32_t *order_out, char *buf, uint64_t b
  * the binary-lifting tables of the chain successors (n_nodes x ceil(log2 n_nodes) x 4 bytes), later calls are one
  * small kernel each. */
 int dbg_export_contig_text(dbg_t *h, uint64_t index, char *buf, uint64_t buf_len);
+/* Contig text in bulk, after any walk that left an index: a materialised one, or an index-only one of the list-ranking
+ * path (an index-only final-mode walk has no per-contig start nodes: DBG_E_ARG).  One kernel fills a window of the output
+ * at a time (chunk_bytes, a multiple of 4096; 0 = library default, 4 MiB; option "ctgout_chunk_bytes" changes that
+ * default) into one of two device staging buffers; the window goes to one of two pinned host buffers, and the host writes
+ * window c (or copies it into the caller's buffer) while window c + 1 is filled and copied.  Neither side ever holds the
+ * whole text; the device holds 2 * chunk_bytes + 24 * (n + 1) bytes + 1 MiB at most besides the walk's own arrays
+ * (dbg_contig_output_stats names the one condition: the sort library's scratch for the driver's order).  An index >= n_contigs is DBG_E_ARG. */
+/* texts of n contigs of the last walk (indices into dbg_export_contig_index, any order, repeats allowed), concatenated:
+ * two-call pattern of dbg_take_reads -- out_offsets[n + 1] (may be NULL) and *n_chars are always set; out_chars NULL:
+ * sizes only, else capacity >= *n_chars (DBG_E_CAPACITY otherwise). */
+int dbg_export_contig_texts(dbg_t *h, const uint64_t *indices, uint64_t n, uint64_t *out_offsets, char *out_chars,
+                            uint64_t capacity, uint64_t *n_chars);
+/* ">SEQUENCE_{first_number + i}_{k_label}mer\n{contig}\n" for i in 0..n-1 written to `path` (append != 0: appended,
+ * else truncated).  indices NULL: every contig in the driver's order (score descending, stable over the emission order --
+ * the order of dbg_export_sorted_fasta); k_label 0: the graph's k.  DBG_E_ARG (text in dbg_last_error) for a path that
+ * cannot be opened for writing and for a chunk_bytes that is no multiple of 4096; n = 0 writes nothing. */
+int dbg_write_contigs_fasta(dbg_t *h, const char *path, int append, const uint64_t *indices, uint64_t n,
+                            uint64_t first_number, int k_label, uint64_t chunk_bytes, uint64_t *bytes_written);
+int dbg_contig_output_stats(dbg_t *h, dbg_contig_out_stats_t *out);
 /* device-side views for callers that stay on the GPU (valid until the next build/destroy) */
 int dbg_device_views(dbg_t *h, const void **d_keys, const void **d_counts, const void **d_stamps,
                      const void **d_flags, const void **d_succ);

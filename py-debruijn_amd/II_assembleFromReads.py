@@ -52,11 +52,13 @@ def assemble(sequences, k_lowerlimit, k_upperlimit, threshold, out_path=None):
             sequences = [contigs[i] for i in order]
             max_len = max((len(x) for x in sequences), default=0)
         if k == k_upperlimit:
-            if out_path is not None:
+            if out_path is not None and isinstance(sequences, db.LazyContigs):
+                sequences.write_fasta(out_path, k)  # append mode; formatted on the device, streamed window by window
+            elif out_path is not None:
                 with open(out_path, mode='a+') as out_file:  # append mode, as in the reference
                     if hasattr(contigs, "sorted_fasta"):
                         out_file.write(contigs.sorted_fasta())  # the same records, sorted and formatted on the device
-                    else:  # record by record: a LazyContigs fetches each text from the device as it is written
+                    else:
                         for i in range(len(sequences)):
                             out_file.write('>SEQUENCE_{}_{}mer\n{}\n'.format(i, k, sequences[i]))
             break

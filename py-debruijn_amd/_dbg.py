@@ -38,6 +38,7 @@ SYMBOLS = (
     "dbg_part_segments", "dbg_part_pflags", "dbg_scan_reads_for_keys", "dbg_set_orders", "dbg_part_segment_text",
     "dbg_build_from_walk", "dbg_build_from_walks",
     "dbg_lookup_nodes", "dbg_lookup_nodes_device", "dbg_gather_nodes", "dbg_score_sequences",
+    "dbg_export_contig_texts", "dbg_write_contigs_fasta", "dbg_contig_output_stats",
 )
 
 
@@ -66,6 +67,15 @@ class IngestStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "bytes_read", "chunks", "chunk_bytes", "peak_device_bytes", "n_reads", "n_bases")] + [
         (n, C.c_double) for n in ("ms_total", "ms_io_wait", "ms_h2d", "ms_parse")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class ContigOutStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in (
+        "bytes_written", "chunks", "chunk_bytes", "peak_device_bytes", "lift_bytes")] + [
+        (n, C.c_double) for n in ("ms_total", "ms_io_wait", "ms_fill", "ms_d2h")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -196,6 +206,9 @@ def load_library():
         "dbg_lookup_nodes_device": (C.c_int, [H, vp, vp, C.c_uint64, vp]),
         "dbg_gather_nodes": (C.c_int, [H, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dbg_score_sequences": (C.c_int, [H, vp, vp, C.c_uint64, vp, vp]),
+        "dbg_export_contig_texts": (C.c_int, [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]),
+        "dbg_write_contigs_fasta": (C.c_int, [H, C.c_char_p, C.c_int, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, u64p]),
+        "dbg_contig_output_stats": (C.c_int, [H, C.POINTER(ContigOutStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -496,6 +509,41 @@ class Graph:
         buf = np.empty(int(length), dtype=np.uint8)
         self._chk(self._lib.dbg_export_contig_text(self._h, int(index), _ptr(buf), int(length)))
         return buf.tobytes()
+
+    def export_contig_texts(self, indices):
+        """-> (offsets uint64[n + 1], chars uint8): the texts of the contigs ``indices`` of the last walk (any order, repeats
+        allowed), concatenated -- spelled by one kernel per window and streamed through pinned buffers, also when the walk
+        kept only its index.  The window size is the handle's option "ctgout_chunk_bytes" (a multiple of 4096; 0: the
+        library default)."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        off = np.zeros(idx.size + 1, dtype=np.uint64)
+        total = C.c_uint64()
+        self._chk(self._lib.dbg_export_contig_texts(self._h, _ptr(idx) if idx.size else None, idx.size, _ptr(off), None, 0,
+                                                    C.byref(total)))
+        chars = np.empty(total.value, dtype=np.uint8)
+        if total.value:
+            self._chk(self._lib.dbg_export_contig_texts(self._h, _ptr(idx), idx.size, None, _ptr(chars), chars.size,
+                                                        C.byref(total)))
+        return off, chars
+
+    def write_contigs_fasta(self, path, indices=None, append=True, first_number=0, k_label=0, chunk_bytes=0):
+        """Writes ``>SEQUENCE_{first_number + i}_{k_label}mer`` records of the contigs ``indices`` of the last walk (None: all
+        of them in the driver's order, score descending and stable) to ``path``, streamed window by window; -> bytes written.
+        ``k_label`` 0: the graph's k; ``chunk_bytes`` 0: the library default."""
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        n_idx = 0 if idx is None else idx.size
+        if idx is not None and not idx.size:
+            idx = np.zeros(1, dtype=np.uint64)  # an empty list is not "all of them": a pointer, and n = 0
+        n = C.c_uint64()
+        self._chk(self._lib.dbg_write_contigs_fasta(self._h, os.fsencode(path), 1 if append else 0, _ptr(idx), n_idx,
+                                                    int(first_number), int(k_label), int(chunk_bytes), C.byref(n)))
+        return int(n.value)
+
+    def contig_output_stats(self):
+        """What the last streamed contig output did: bytes, windows, peak device bytes, ms in write / fill / D2H."""
+        out = ContigOutStats()
+        self._chk(self._lib.dbg_contig_output_stats(self._h, C.byref(out)))
+        return out.as_dict()
 
     def export_contigs(self):
         sz = self.sizes()

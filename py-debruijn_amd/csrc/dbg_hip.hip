@@ -39,6 +39,7 @@
 #include "dbg_wsk.h"
 #include "dbg_fasta.h"
 #include "dbg_lookup.h"
+#include "dbg_ctgout.h"
 
 using namespace dbgk;
 
@@ -141,6 +142,7 @@ struct dbg {
     bool walked = false;          // contig text materialised
     bool walk_final = false;      // the last walk was a final-mode one (all simple paths, not chains)
     bool walk_indexed = false;    // contig index (offsets, scores, start stamps) valid
+    bool walk_sizes_only = false; // the last walk (final-mode DFS) exceeded max_chars: counts valid, no index, no start nodes
     uint64_t walk_jump_min = 1ull << 14;  // non-final walk: list ranking from this many nodes on (below: one thread per start)
 
     // alphabet / node layout: 2 bits and 4 successors for DNA, 5 bits and 32 for the generic engine
@@ -223,6 +225,8 @@ struct dbg {
 
     dbg_stats_t stats{};
     dbg_ingest_stats_t ingest{};  // the last FASTA ingest
+    dbg_contig_out_stats_t ctgout{};  // the last streamed contig output (dbg_ctgout.h)
+    uint64_t ctgout_chunk = 0;        // option "ctgout_chunk_bytes": window size where a call names none (0: CO_DEFAULT_CHUNK)
 };
 
 // What a sharded build leaves behind for the exchange of successors owned by other ranks.
@@ -1584,6 +1588,7 @@ __global__ __launch_bounds__(256) void k_text_fill(uint64_t n_chars, G g, const 
 static const char *const kPartialGraph =
     "this handle holds one shard of a multi-GPU build: gather the shards first (multi_gpu.gather_graph / dbg_import_graph)";
 static int nk_mark_contigs(dbg *h);
+static const char *const kNoCtgStarts = "no per-contig start nodes (walk did not take the list-ranking path)";
 static void free_build(dbg *h) {
     multipass_free(h);
     h->dir_valid = false;
@@ -1616,7 +1621,7 @@ static void free_build(dbg *h) {
     h->partial_graph = false;
     h->sk_src.valid = false;
     h->k = 0; h->cap = 0; h->n_nodes = h->n_edges = 0;
-    h->pruned = h->tipped = h->pull_reads_done = h->walked = h->walk_indexed = false;
+    h->pruned = h->tipped = h->pull_reads_done = h->walked = h->walk_indexed = h->walk_sizes_only = false;
     h->n_branch = h->n_pulled = h->tip_rounds = h->n_pull_reads = 0;
     h->n_starts = h->n_contigs = h->contig_chars = 0;
     h->starts_known = false;
@@ -2481,6 +2486,7 @@ extern "C" int dbg_set_option(dbg_t *h, const char *name, int64_t value) {
     if (n == "wcount_kernel" && (value == 1 || value == 2)) { h->wcount_kernel = (int)value; return DBG_OK; }
     if (n == "count_kernel_u64" && value >= 1 && value <= 3) { h->count_kernel_u64 = (int)value; return DBG_OK; }
     if (n == "lookup_index" && (value == 0 || value == 1)) { h->lookup_index = (int)value; return DBG_OK; }
+    if (n == "ctgout_chunk_bytes" && value >= 0 && dbgk::co_chunk_ok((uint64_t)value)) { h->ctgout_chunk = (uint64_t)value; return DBG_OK; }
     if (n == "shard_node_limit" && value >= 0 && value < (1ll << 29)) { h->shard_node_limit = (uint64_t)value; return DBG_OK; }
     h->err = "unknown option or value out of range: " + n;
     return DBG_E_ARG;
@@ -3041,7 +3047,7 @@ extern "C" int dbg_prune(dbg_t *h, double threshold) {
     h->tipped = false;
     h->n_pulled = 0;
     h->pull_reads_done = false;
-    h->walked = h->walk_indexed = false;
+    h->walked = h->walk_indexed = h->walk_sizes_only = false;
     return DBG_OK;
 }
 
@@ -3087,7 +3093,7 @@ static int remove_tips_impl(dbg *h, const G &g) {
     }
     h->stats.ms_tips = t.stop();
     h->tipped = true;
-    h->walked = h->walk_indexed = false;
+    h->walked = h->walk_indexed = h->walk_sizes_only = false;
     return DBG_OK;
 }
 
@@ -3192,7 +3198,7 @@ static int walk_impl(dbg *h, const G &g, int final_mode, uint64_t max_chars) {
     h->lift_levels = 0;
     h->n_contigs = h->contig_chars = 0;
     h->walked = false;
-    h->walk_indexed = false;
+    h->walk_indexed = h->walk_sizes_only = false;
     { const int rs = ensure_starts(h); if (rs != DBG_OK) return rs; }
     const uint64_t ns = h->n_starts;
     const bool use_jump = !final_mode && h->n_nodes >= h->walk_jump_min && ns;
@@ -3296,6 +3302,7 @@ static int walk_impl(dbg *h, const G &g, int final_mode, uint64_t max_chars) {
         h->contig_chars = n_chr;
         if (n_chr > max_chars && !use_jump) {
             h->err = "contig text exceeds max_chars (sizes are valid, text not materialised)";
+            h->walk_sizes_only = true;
             rc = DBG_E_CAPACITY;
             break;
         }
@@ -3513,6 +3520,23 @@ __global__ __launch_bounds__(256) void k_text_one(G g, uint32_t start, uint64_t 
     chars[j] = g.sym_char(g.last_code(x));
 }
 
+// tables of the 2^j-th chain successors of the last walk's graph, built once per walk (the walk frees them)
+template <class G>
+static int ensure_lift(dbg *h, const G &g) {
+    if (h->d_lift) return DBG_OK;
+    int levels = 1;
+    while ((1ull << levels) <= h->n_nodes + (uint64_t)h->k) ++levels;
+    if ((uint64_t)levels * h->n_nodes * 4 > (64ull << 30)) { h->err = "graph too large for on-demand contig text"; return DBG_E_CAPACITY; }
+    CHK(dev_alloc(h, &h->d_lift, (uint64_t)levels * h->n_nodes));
+    const dim3 ngrid(grid_for(h->n_nodes, 256));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lift_init<G>), ngrid, dim3(256), 0, h->stream, h->n_nodes, g, h->d_lift);
+    for (int l = 1; l < levels; ++l)
+        hipLaunchKernelGGL(k_lift_step, ngrid, dim3(256), 0, h->stream, h->n_nodes, h->d_lift + (uint64_t)(l - 1) * h->n_nodes,
+                           h->d_lift + (uint64_t)l * h->n_nodes);
+    h->lift_levels = levels;
+    return DBG_OK;
+}
+
 template <class G>
 static int contig_text_impl(dbg *h, const G &g, uint64_t index, char *buf, uint64_t buf_len) {
     uint64_t off[2] = {0, 0};
@@ -3522,18 +3546,7 @@ static int contig_text_impl(dbg *h, const G &g, uint64_t index, char *buf, uint6
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const uint64_t len = off[1] - off[0];
     if (buf_len < len) { h->err = "buffer smaller than the contig"; return DBG_E_ARG; }
-    if (!h->d_lift) {  // tables of the 2^j-th chain successors, built once per walk
-        int levels = 1;
-        while ((1ull << levels) <= h->n_nodes + (uint64_t)h->k) ++levels;
-        if ((uint64_t)levels * h->n_nodes * 4 > (64ull << 30)) { h->err = "graph too large for on-demand contig text"; return DBG_E_CAPACITY; }
-        CHK(dev_alloc(h, &h->d_lift, (uint64_t)levels * h->n_nodes));
-        const dim3 ngrid(grid_for(h->n_nodes, 256));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lift_init<G>), ngrid, dim3(256), 0, h->stream, h->n_nodes, g, h->d_lift);
-        for (int l = 1; l < levels; ++l)
-            hipLaunchKernelGGL(k_lift_step, ngrid, dim3(256), 0, h->stream, h->n_nodes, h->d_lift + (uint64_t)(l - 1) * h->n_nodes,
-                               h->d_lift + (uint64_t)l * h->n_nodes);
-        h->lift_levels = levels;
-    }
+    CHK(ensure_lift(h, g));
     char *tmp = nullptr;
     CHK(dev_alloc(h, &tmp, len));
     if (len) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_text_one<G>), dim3(grid_for(len, 256)), dim3(256), 0, h->stream, g, start, len,
@@ -3558,7 +3571,7 @@ extern "C" int dbg_export_contig_text(dbg_t *h, uint64_t index, char *buf, uint6
         HIPCHK(h, hipStreamSynchronize(h->stream));
         return DBG_OK;
     }
-    if (!h->d_ctg_start) { h->err = "no per-contig start nodes (walk did not take the list-ranking path)"; return DBG_E_ARG; }
+    if (!h->d_ctg_start) { h->err = kNoCtgStarts; return DBG_E_ARG; }
     if (h->D == GEN_D) return contig_text_impl(h, gen_view(h), index, buf, buf_len);
     return contig_text_impl(h, dna_view(h), index, buf, buf_len);
 }
@@ -6908,6 +6921,52 @@ __global__ __launch_bounds__(256) void k_fa_text(uint64_t n_bytes, uint64_t n_ct
     out[b] = ch;
 }
 
+// The contigs of the last walk in the driver's order: emission order, then by score, descending and stable.  *order_out: device
+// array of n_contigs contig indices (the caller frees it); *scratch (may be null): device bytes held at the peak.
+static int fa_sorted_order(dbg *h, uint32_t **order_out, uint64_t *scratch) {
+    const uint64_t n = h->n_contigs;
+    uint64_t *ka = nullptr, *kb = nullptr;
+    uint32_t *ia = nullptr, *ib = nullptr, *result = nullptr;
+    void *tmp = nullptr;
+    size_t tmp_bytes = 0;
+    int rc = DBG_OK;
+    *order_out = nullptr;
+    do {
+        if ((rc = dev_alloc(h, &ka, n)) || (rc = dev_alloc(h, &kb, n)) || (rc = dev_alloc(h, &ia, n)) || (rc = dev_alloc(h, &ib, n)))
+            break;
+        // the sorts swap between the two key and the two id arrays: rocprim's own scratch is then its digit counters and
+        // look-back state alone (about n / 4 bytes), not a third copy of keys and ids
+        rocprim::double_buffer<uint64_t> keys(ka, kb);
+        rocprim::double_buffer<uint32_t> ids(ia, ib);
+        hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, ids, (size_t)n, 0u, 64u, h->stream);
+        if (e == hipSuccess) e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1);
+        if (e != hipSuccess) { h->err = std::string("sorted fasta: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
+        if (scratch) *scratch = 24 * n + tmp_bytes;
+        const dim3 grid(grid_for(n, 256));
+        // emission order = (start stamp, emission index inside the start): two stable passes, minor key first
+        hipLaunchKernelGGL(k_iota32, grid, dim3(256), 0, h->stream, n, ids.current());
+        hipLaunchKernelGGL(k_fa_keys, grid, dim3(256), 0, h->stream, n, (const uint32_t *)nullptr, (const uint64_t *)nullptr,
+                           (const uint32_t *)h->d_ctg_seq, 0, keys.current());
+        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, ids, (size_t)n, 0u, 32u, h->stream);
+        hipLaunchKernelGGL(k_fa_keys, grid, dim3(256), 0, h->stream, n, (const uint32_t *)ids.current(),
+                           (const uint64_t *)h->d_ctg_stamp, (const uint32_t *)nullptr, 0, keys.current());
+        if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, ids, (size_t)n, 0u, 64u, h->stream);
+        // ... then the driver's sort: by score, descending, stable
+        hipLaunchKernelGGL(k_fa_keys, grid, dim3(256), 0, h->stream, n, (const uint32_t *)ids.current(),
+                           (const uint64_t *)h->d_ctg_score, (const uint32_t *)nullptr, 1, keys.current());
+        if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, ids, (size_t)n, 0u, 64u, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // the scratch goes before the sorts may still read it
+        if (e != hipSuccess) { h->err = std::string("sorted fasta: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
+        result = ids.current();
+    } while (0);
+    if (tmp) (void)hipFree(tmp);
+    dev_free(ka); dev_free(kb);
+    if (result != ia) dev_free(ia);
+    if (result != ib) dev_free(ib);
+    *order_out = result;
+    return rc;
+}
+
 extern "C" int dbg_export_sorted_fasta(dbg_t *h, uint32_t *order_out, char *buf, uint64_t buf_len, uint64_t *bytes) {
     if (!h || !bytes) return DBG_E_ARG;
     if (!h->walked) {
@@ -6919,33 +6978,14 @@ extern "C" int dbg_export_sorted_fasta(dbg_t *h, uint32_t *order_out, char *buf,
     *bytes = 0;
     if (!n) return DBG_OK;
     if (n >= 0xFFFFFFF0ull) { h->err = "too many contigs for one sort"; return DBG_E_CAPACITY; }
-    uint64_t *ka = nullptr, *kb = nullptr, *pos = nullptr;
-    uint32_t *ia = nullptr, *ib = nullptr;
+    uint64_t *pos = nullptr;
+    uint32_t *ib = nullptr;
     char *d_out = nullptr;
-    void *tmp = nullptr;
-    size_t tmp_bytes = 0;
     int rc = DBG_OK;
     do {
-        if ((rc = dev_alloc(h, &ka, n)) || (rc = dev_alloc(h, &kb, n)) || (rc = dev_alloc(h, &ia, n)) || (rc = dev_alloc(h, &ib, n)) ||
-            (rc = dev_alloc(h, &pos, n + 1)))
-            break;
-        hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, ka, kb, ia, ib, (size_t)n, 0u, 64u, h->stream);
-        if (e == hipSuccess) e = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1);
-        if (e != hipSuccess) { h->err = std::string("sorted fasta: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
-        const dim3 grid(grid_for(n, 256));
-        // emission order = (start stamp, emission index inside the start): two stable passes, minor key first
-        hipLaunchKernelGGL(k_iota32, grid, dim3(256), 0, h->stream, n, ia);
-        hipLaunchKernelGGL(k_fa_keys, grid, dim3(256), 0, h->stream, n, (const uint32_t *)nullptr, (const uint64_t *)nullptr,
-                           (const uint32_t *)h->d_ctg_seq, 0, ka);
-        e = rocprim::radix_sort_pairs(tmp, tmp_bytes, ka, kb, ia, ib, (size_t)n, 0u, 32u, h->stream);
-        hipLaunchKernelGGL(k_fa_keys, grid, dim3(256), 0, h->stream, n, (const uint32_t *)ib, (const uint64_t *)h->d_ctg_stamp,
-                           (const uint32_t *)nullptr, 0, ka);
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, ka, kb, ib, ia, (size_t)n, 0u, 64u, h->stream);
-        // ... then the driver's sort: by score, descending, stable
-        hipLaunchKernelGGL(k_fa_keys, grid, dim3(256), 0, h->stream, n, (const uint32_t *)ia, (const uint64_t *)h->d_ctg_score,
-                           (const uint32_t *)nullptr, 1, ka);
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, ka, kb, ia, ib, (size_t)n, 0u, 64u, h->stream);
-        if (e != hipSuccess) { h->err = std::string("sorted fasta: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
+        if ((rc = fa_sorted_order(h, &ib, nullptr)) != DBG_OK) break;
+        if ((rc = dev_alloc(h, &pos, n + 1)) != DBG_OK) break;
+        hipError_t e = hipSuccess;
         uint64_t total = 0;
         if ((rc = exclusive_scan(h, n, FaRecLen{ib, h->d_ctg_off, FaRecLen::digits((uint64_t)h->k)}, pos, &total)) != DBG_OK) break;
         *bytes = total;
@@ -6965,9 +7005,241 @@ extern "C" int dbg_export_sorted_fasta(dbg_t *h, uint32_t *order_out, char *buf,
         if (e == hipSuccess) e = hipGetLastError();
         if (e != hipSuccess) { h->err = std::string("sorted fasta: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
     } while (0);
-    if (tmp) (void)hipFree(tmp);
-    dev_free(ka); dev_free(kb); dev_free(ia); dev_free(ib); dev_free(pos); dev_free(d_out);
+    dev_free(ib); dev_free(pos); dev_free(d_out);
     return rc;
+}
+
+// ==========================================================================================
+// Streamed contig output (dbg_ctgout.h): batched texts and FASTA records of a list of contigs, window by window
+// ==========================================================================================
+struct CoRecLen {  // bytes of record i of the list
+    const uint32_t *list;
+    const uint64_t *off;
+    uint64_t first_number;
+    uint32_t k_digits;
+    int fasta;
+    __device__ uint64_t operator()(uint64_t i) const {
+        const uint32_t c = list[i];
+        return co_record_len(fasta != 0, first_number + i, k_digits, off[c + 1] - off[c]);
+    }
+};
+
+namespace {
+struct CtgOut {
+    dbg *h;
+    int fd = -1;
+    char *pin[2] = {nullptr, nullptr}, *dev[2] = {nullptr, nullptr};
+    hipEvent_t ev_t0[2] = {nullptr, nullptr}, ev_fill[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+    uint32_t *d_list = nullptr;
+    uint64_t *d_pos = nullptr;
+    uint64_t cur = 0, peak = 0;  // device bytes held by the call
+    explicit CtgOut(dbg *hh) : h(hh) {}
+    template <class T>
+    int alloc(T **p, uint64_t count) {
+        CHK(dev_alloc(h, p, count));
+        hold(std::max<uint64_t>(count, 1) * sizeof(T));
+        return DBG_OK;
+    }
+    void hold(uint64_t bytes) { cur += bytes; peak = std::max(peak, cur); }
+    ~CtgOut() {
+        (void)hipStreamSynchronize(h->stream);
+        if (fd >= 0) close(fd);
+        for (auto &p : pin) if (p) (void)hipHostFree(p);
+        for (auto &p : dev) dev_free(p);
+        for (auto e : {ev_t0[0], ev_t0[1], ev_fill[0], ev_fill[1], ev_copy[0], ev_copy[1]}) if (e) (void)hipEventDestroy(e);
+        dev_free(d_list); dev_free(d_pos);
+        (void)hipGetLastError();
+    }
+};
+}  // namespace
+
+// what both calls refuse before they touch anything
+static int ctgout_check(dbg *h, const uint64_t *indices, uint64_t n) {
+    // a final-mode walk whose text exceeded max_chars kept its counts alone: there is nothing to spell contigs from
+    if (h->walk_sizes_only || (h->walk_indexed && !h->walked && !h->d_ctg_start)) { h->err = kNoCtgStarts; return DBG_E_ARG; }
+    if (!h->walk_indexed) { h->err = "dbg_walk must run first"; return DBG_E_ARG; }
+    if (n >= 0xFFFFFFF0ull || h->n_contigs >= 0xFFFFFFF0ull) { h->err = "too many contigs for one call"; return DBG_E_CAPACITY; }
+    for (uint64_t i = 0; indices && i < n; ++i)
+        if (indices[i] >= h->n_contigs) {
+            h->err = "contig index out of range: " + std::to_string(indices[i]) + " (the walk has " + std::to_string(h->n_contigs) + " contigs)";
+            return DBG_E_ARG;
+        }
+    return DBG_OK;
+}
+
+// the list on the device (the caller's indices, or the driver's order) and the position of every record; *total: bytes
+static int ctgout_layout(CtgOut &co, const uint64_t *indices, uint64_t n, CoText &t, uint64_t *offsets_out) {
+    dbg *h = co.h;
+    if (indices) {
+        std::vector<uint32_t> list(n);
+        for (uint64_t i = 0; i < n; ++i) list[i] = (uint32_t)indices[i];
+        CHK(co.alloc(&co.d_list, n));
+        HIPCHK(h, hipMemcpyAsync(co.d_list, list.data(), n * 4, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));  // `list` goes out of scope
+    } else {
+        uint64_t scratch = 0;
+        CHK(fa_sorted_order(h, &co.d_list, &scratch));
+        co.peak = std::max(co.peak, co.cur + scratch);
+        co.hold(std::max<uint64_t>(n, 1) * 4);
+    }
+    CHK(co.alloc(&co.d_pos, n));
+    co.hold((std::max<uint64_t>((n + SCAN_TILE - 1) / SCAN_TILE, 1) + 1) * 8);  // scan partials (handle arena)
+    t.list = co.d_list;
+    t.pos = co.d_pos;
+    t.off = h->d_ctg_off;
+    t.n = n;
+    CHK(exclusive_scan(h, n, CoRecLen{co.d_list, h->d_ctg_off, t.first_number, t.k_digits, t.fasta}, co.d_pos, &t.total));
+    if (offsets_out) {
+        HIPCHK(h, hipMemcpyAsync(offsets_out, co.d_pos, n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        offsets_out[n] = t.total;
+    }
+    return DBG_OK;
+}
+
+template <class Src>
+static int ctgout_stream(CtgOut &co, const CoText &t, const Src &src, uint64_t chunk, char *dst, const char *path) {
+    dbg *h = co.h;
+    using clk = std::chrono::steady_clock;
+    const uint64_t stage = co_stage_bytes(t.total, chunk), nw = co_n_windows(t.total, chunk);
+    for (auto &p : co.pin) HIPCHK(h, hipHostMalloc((void **)&p, stage, hipHostMallocDefault));
+    for (auto &p : co.dev) CHK(co.alloc(&p, stage));
+    for (auto *e : {&co.ev_t0[0], &co.ev_t0[1], &co.ev_fill[0], &co.ev_fill[1], &co.ev_copy[0], &co.ev_copy[1]}) HIPCHK(h, hipEventCreate(e));
+    double ms_io = 0, ms_fill = 0, ms_d2h = 0;
+    auto consume = [&](uint64_t c) -> int {  // window c has been enqueued: wait for its copy, hand it on
+        const int s = (int)(c & 1);
+        const CoWindow w = co_window(t.total, chunk, c);
+        HIPCHK(h, hipEventSynchronize(co.ev_copy[s]));
+        float a = 0, b = 0;
+        (void)hipEventElapsedTime(&a, co.ev_t0[s], co.ev_fill[s]);
+        (void)hipEventElapsedTime(&b, co.ev_fill[s], co.ev_copy[s]);
+        ms_fill += a;
+        ms_d2h += b;
+        const auto t0 = clk::now();
+        const uint64_t len = w.b1 - w.b0;
+        if (dst) {
+            memcpy(dst + w.b0, co.pin[s], len);
+        } else {
+            for (uint64_t done = 0; done < len;) {
+                const ssize_t got = write(co.fd, co.pin[s] + done, len - done);
+                if (got < 0 && errno == EINTR) continue;
+                if (got <= 0) { h->err = std::string(path) + ": write failed: " + strerror(errno); return DBG_E_ARG; }
+                done += (uint64_t)got;
+            }
+        }
+        ms_io += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+        h->ctgout.bytes_written += len;
+        ++h->ctgout.chunks;
+        return DBG_OK;
+    };
+    for (uint64_t c = 0; c < nw; ++c) {
+        // staging pair s held window c - 2: its copy has been waited for and its bytes handed on (consume(c - 2))
+        const int s = (int)(c & 1);
+        const CoWindow w = co_window(t.total, chunk, c);
+        HIPCHK(h, hipEventRecord(co.ev_t0[s], h->stream));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ctg_window<Src>), dim3((unsigned)w.tiles), dim3(CO_NT), 0, h->stream, t, w.b0, w.b1, src,
+                           co.dev[s]);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipEventRecord(co.ev_fill[s], h->stream));
+        HIPCHK(h, hipMemcpyAsync(co.pin[s], co.dev[s], w.b1 - w.b0, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipEventRecord(co.ev_copy[s], h->stream));
+        if (c) CHK(consume(c - 1));  // the host hands window c - 1 on while the device fills and copies window c
+    }
+    if (nw) CHK(consume(nw - 1));
+    h->ctgout.ms_io_wait = ms_io;
+    h->ctgout.ms_fill = ms_fill;
+    h->ctgout.ms_d2h = ms_d2h;
+    return DBG_OK;
+}
+
+template <class G>
+static int ctgout_run(CtgOut &co, const G &g, const CoText &t, uint64_t chunk, char *dst, const char *path) {
+    dbg *h = co.h;
+    if (!t.total) return DBG_OK;
+    if (h->walked) return ctgout_stream(co, t, CoCharsSrc{h->d_ctg_chars, h->d_ctg_off, nullptr}, chunk, dst, path);
+    CHK(ensure_lift(h, g));
+    h->ctgout.lift_bytes = (uint64_t)h->lift_levels * h->n_nodes * 4;
+    return ctgout_stream(co, t, CoLiftSrc<G>{g, h->d_ctg_start, h->d_lift, h->n_nodes, h->lift_levels, 0u, 0u}, chunk, dst, path);
+}
+
+static int ctgout_dispatch(CtgOut &co, const CoText &t, uint64_t chunk, char *dst, const char *path) {
+    dbg *h = co.h;
+    const int rc = h->D == GEN_D ? ctgout_run(co, gen_view(h), t, chunk, dst, path) : ctgout_run(co, dna_view(h), t, chunk, dst, path);
+    h->ctgout.peak_device_bytes = co.peak;
+    return rc;
+}
+
+static uint64_t ctgout_chunk_of(const dbg *h, uint64_t chunk_bytes) {
+    const uint64_t c = chunk_bytes ? chunk_bytes : (h->ctgout_chunk ? h->ctgout_chunk : CO_DEFAULT_CHUNK);
+    return std::min(c, CO_MAX_CHUNK);
+}
+
+extern "C" int dbg_export_contig_texts(dbg_t *h, const uint64_t *indices, uint64_t n, uint64_t *out_offsets, char *out_chars,
+                                       uint64_t capacity, uint64_t *n_chars) {
+    if (!h) return DBG_E_ARG;
+    using clk = std::chrono::steady_clock;
+    const auto t_call = clk::now();
+    if (!n_chars || (n && !indices)) { h->err = "export_contig_texts: indices and n_chars are required"; return DBG_E_ARG; }
+    *n_chars = 0;
+    CHK(ctgout_check(h, indices, n));
+    if (!n) {
+        if (out_offsets) out_offsets[0] = 0;
+        return DBG_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    CtgOut co(h);
+    CoText t{};
+    CHK(ctgout_layout(co, indices, n, t, out_offsets));
+    *n_chars = t.total;
+    if (!out_chars) return DBG_OK;
+    if (capacity < t.total) { h->err = "export_contig_texts: capacity smaller than the texts"; return DBG_E_CAPACITY; }
+    const uint64_t chunk = ctgout_chunk_of(h, 0);
+    h->ctgout = dbg_contig_out_stats_t{};
+    h->ctgout.chunk_bytes = chunk;
+    const int rc = ctgout_dispatch(co, t, chunk, out_chars, nullptr);
+    h->ctgout.ms_total = std::chrono::duration<double, std::milli>(clk::now() - t_call).count();
+    return rc;
+}
+
+extern "C" int dbg_write_contigs_fasta(dbg_t *h, const char *path, int append, const uint64_t *indices, uint64_t n,
+                                       uint64_t first_number, int k_label, uint64_t chunk_bytes, uint64_t *bytes_written) {
+    if (!h) return DBG_E_ARG;
+    using clk = std::chrono::steady_clock;
+    const auto t_call = clk::now();
+    if (bytes_written) *bytes_written = 0;
+    if (!path) { h->err = "write_contigs_fasta: no path"; return DBG_E_ARG; }
+    if (!co_chunk_ok(chunk_bytes)) {
+        h->err = "write_contigs_fasta: chunk_bytes " + std::to_string(chunk_bytes) + " is no multiple of " + std::to_string(CO_TILE);
+        return DBG_E_ARG;
+    }
+    if (k_label < 0) { h->err = "write_contigs_fasta: k_label is negative"; return DBG_E_ARG; }
+    CHK(ctgout_check(h, indices, indices ? n : 0));
+    if (!indices) n = h->n_contigs;
+    if (n >= 0xFFFFFFF0ull) { h->err = "too many contigs for one call"; return DBG_E_CAPACITY; }
+    HIPCHK(h, hipSetDevice(h->device));
+    CtgOut co(h);
+    co.fd = open(path, O_WRONLY | O_CREAT | O_CLOEXEC | (append ? O_APPEND : O_TRUNC), 0666);
+    if (co.fd < 0) { h->err = std::string(path) + ": " + strerror(errno); return DBG_E_ARG; }
+    const uint64_t chunk = ctgout_chunk_of(h, chunk_bytes);
+    h->ctgout = dbg_contig_out_stats_t{};
+    h->ctgout.chunk_bytes = chunk;
+    if (!n) return DBG_OK;
+    CoText t{};
+    t.fasta = 1;
+    t.first_number = first_number;
+    t.k_label = (uint32_t)(k_label ? k_label : h->k);
+    t.k_digits = co_digits(t.k_label);
+    CHK(ctgout_layout(co, indices, n, t, nullptr));
+    const int rc = ctgout_dispatch(co, t, chunk, nullptr, path);
+    if (bytes_written) *bytes_written = h->ctgout.bytes_written;
+    h->ctgout.ms_total = std::chrono::duration<double, std::milli>(clk::now() - t_call).count();
+    return rc;
+}
+
+extern "C" int dbg_contig_output_stats(dbg_t *h, dbg_contig_out_stats_t *out) {
+    if (!h || !out) return DBG_E_ARG;
+    *out = h->ctgout;
+    return DBG_OK;
 }
 
 #include "dbg_nextk.h"  // dbg_build_from_walk: the next k's graph from the last walk

@@ -436,9 +436,49 @@ class ContigList(list):
 MAX_CONTIG_CHARS = 0  # dbg_walk's max_chars; 0 = the library default (1 GiB of contig text kept on the device)
 
 
+BATCH_CHARS = 256 << 20  # characters of one batched text export (dbg_export_contig_texts): bounds the host copy
+
+
+def _batches(lengths, limit):
+    """Slices of consecutive positions whose lengths add up to ``limit`` at most (a longer contig is a batch of its own)."""
+    ends = np.cumsum(np.asarray(lengths, dtype=np.int64))
+    at, n = 0, len(ends)
+    while at < n:
+        base = int(ends[at - 1]) if at else 0
+        stop = max(int(np.searchsorted(ends, base + limit, side="right")), at + 1)
+        yield slice(at, stop)
+        at = stop
+
+
+def _packed_texts(graph, idx, lengths):
+    """(uint8 characters, lengths) of the contigs ``idx`` of ``graph``, batch by batch: one device call per batch where the
+    handle offers export_contig_texts, one per contig where it does not."""
+    idx, lengths = np.asarray(idx, dtype=np.int64), np.asarray(lengths, dtype=np.int64)
+    many = getattr(graph, "export_contig_texts", None)
+    for sl in _batches(lengths, BATCH_CHARS):
+        if many is not None:
+            off, chars = many(idx[sl])
+            if not np.array_equal(np.diff(off.astype(np.int64)), lengths[sl]):
+                raise RuntimeError("the device contigs of this list are gone (the handle walked again)")
+        else:
+            chars = np.frombuffer(b"".join(graph.export_contig_text(int(c), int(n)) for c, n in zip(idx[sl], lengths[sl])),
+                                  dtype=np.uint8)
+        yield chars, lengths[sl]
+
+
+def _texts(graph, idx, lengths):
+    """The same as strings."""
+    for chars, lens in _packed_texts(graph, idx, lengths):
+        text, at = chars.tobytes().decode("latin-1"), 0
+        for n in lens.tolist():
+            yield text[at:at + n]
+            at += n
+
+
 class _ContigBlock(Sequence):
     """Contigs of one walk by reference: the graph handle, contig indices into its index and their lengths.  A text is
-    fetched from that graph when it is indexed (dbg_export_contig_text); ``len`` and ``take`` move none."""
+    fetched from that graph when it is indexed (dbg_export_contig_text); slices and iteration fetch in batches
+    (dbg_export_contig_texts); ``len`` and ``take`` move none."""
 
     def __init__(self, graph, idx, lengths, final, generation, walk):
         self._graph = graph
@@ -451,8 +491,11 @@ class _ContigBlock(Sequence):
 
     def __getitem__(self, i):
         if isinstance(i, slice):
-            return [self[j] for j in range(*i.indices(len(self)))]
+            return list(_texts(self._graph, self._idx[i], self.lengths[i]))
         return self._graph.export_contig_text(int(self._idx[i]), int(self.lengths[i])).decode("latin-1")
+
+    def __iter__(self):
+        return _texts(self._graph, self._idx, self.lengths)
 
     def take(self, positions):
         p = np.asarray(positions, dtype=np.int64)
@@ -495,9 +538,25 @@ class LazyContigs(Sequence):
     def __len__(self):
         return len(self._order) + self._tail_len
 
+    def _texts_at(self, positions):
+        """[self[p] for p in positions] with one batched export per block the positions fall into."""
+        pos = np.asarray(positions, dtype=np.int64)
+        out = np.empty(len(pos), dtype=object)
+        for first, item in self._segments():
+            here = np.nonzero((pos >= first) & (pos < first + len(item)))[0]
+            if not len(here):
+                continue
+            rel = pos[here] - first
+            out[here] = list(item.take(rel)) if type(item) is _ContigBlock else [item[j] for j in rel.tolist()]
+        return out.tolist()
+
+    def __iter__(self):
+        for _, item in self._segments():
+            yield from item
+
     def __getitem__(self, i):
         if isinstance(i, slice):
-            return [self[j] for j in range(*i.indices(len(self)))]
+            return self._texts_at(np.arange(len(self))[i])
         if i < 0:
             i += len(self)
         if not 0 <= i < len(self):
@@ -543,6 +602,45 @@ class LazyContigs(Sequence):
                 n = len(self._tail) - n
                 self._tail_first.extend(range(self._tail_len, self._tail_len + n))
                 self._tail_len += n
+
+    def packed(self):
+        """-> (uint8 characters, uint64 offsets[len + 1]) of the whole sequence, tail blocks and strings included: one
+        batched export per block, no Python ``str`` per contig."""
+        chars, lens = [], []
+        for _, item in self._segments():
+            if type(item) is _ContigBlock:
+                for c, n in _packed_texts(item._graph, item._idx, item.lengths):
+                    chars.append(c)
+                    lens.append(n)
+            elif item:
+                try:
+                    chars.append(np.frombuffer("".join(item).encode("latin-1"), dtype=np.uint8))
+                except UnicodeEncodeError as e:
+                    raise ValueError("reads must be made of single-byte characters for the device path") from e
+                lens.append(np.fromiter((len(r) for r in item), dtype=np.int64, count=len(item)))
+        offsets = np.zeros(len(self) + 1, dtype=np.uint64)
+        if lens:
+            np.cumsum(np.concatenate(lens), out=offsets[1:])
+        return (np.concatenate(chars) if chars else np.zeros(0, dtype=np.uint8)), offsets
+
+    def write_fasta(self, path, k, append=True):
+        """The driver's loop over this sequence (``>SEQUENCE_{i}_{k}mer`` records, II_assembleFromReads.py:65-69) written to
+        ``path``: the main part and every tail block are formatted on the device of the graph that holds them and
+        streamed to the file (dbg_write_contigs_fasta), runs of plain strings are written by the host in between."""
+        open(path, "a" if append else "w").close()
+        for first, item in self._segments():
+            if not len(item):
+                continue
+            write = getattr(item._graph, "write_contigs_fasta", None) if type(item) is _ContigBlock else None
+            if write is not None:
+                g = item._graph  # the writer takes bare indices: they must still be those of the walk the block came from
+                if item._generation is not None and (g.generation != item._generation or g.walks != item._walk):
+                    raise RuntimeError("the device contigs of this list are gone (the handle built another graph or walked again)")
+                write(path, item._idx, append=True, first_number=first, k_label=k)
+                continue
+            with open(path, mode="a") as out_file:
+                for j, text in enumerate(item):
+                    out_file.write('>SEQUENCE_{}_{}mer\n{}\n'.format(first + j, k, text))
 
     def _main_block(self):
         return _ContigBlock(self._graph, self._order, np.asarray(self.lengths, dtype=np.int64), self._final, self._generation,
@@ -598,6 +696,10 @@ class _PulledReads(Sequence):
         t = bisect.bisect_right(self._first, i) - 1
         return self._parts[t][i - self._first[t]]
 
+    def __iter__(self):
+        for part in self._parts:
+            yield from part
+
     def __eq__(self, other):
         return isinstance(other, (list, Sequence)) and list(self) == list(other)
 
@@ -628,6 +730,8 @@ def _walk_source(reads, k):
 
 
 def _pack_reads(reads):
+    if type(reads) is LazyContigs:
+        return reads.packed()
     try:
         blob = "".join(reads).encode("latin-1")  # one byte per character
     except UnicodeEncodeError as e:
@@ -775,7 +879,12 @@ def construct_graph(reads, k, threshold=3, final=False):
         if src is not None:
             pull_out_read = _PulledReads(reads, pulled_idx)
         else:
-            pull_out_read = reads.take(pulled_idx) if isinstance(reads, DeviceReads) else [reads[i] for i in pulled_idx]
+            if isinstance(reads, DeviceReads):
+                pull_out_read = reads.take(pulled_idx)
+            elif type(reads) is LazyContigs:
+                pull_out_read = reads._texts_at(pulled_idx)  # one batched export per block, not one call per read
+            else:
+                pull_out_read = [reads[i] for i in pulled_idx]
         branch_kmer = _Tracked(marked_labels(_dbg.F_BRANCH))
 
     token = object()
