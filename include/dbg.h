@@ -48,7 +48,8 @@ typedef struct dbg dbg_t;
 #define DBG_E_NOMEM (-5)    /* host or device allocation failed */
 
 #define DBG_ABI_VERSION 6 /* not raised for dbg_build_from_walks, nor for the query calls (dbg_lookup_nodes[_device],
-                            * dbg_gather_nodes, dbg_score_sequences): they only add symbols, every earlier call and struct is
+                            * dbg_gather_nodes, dbg_score_sequences, dbg_part_lookup_nodes[_device],
+                            * dbg_part_score_sequences): they only add symbols, every earlier call and struct is
                             * unchanged, and tests/test_fasta_stream.py pins this number; a binding that needs a new
                             * call fails at symbol lookup on an older library */
 
@@ -279,6 +280,23 @@ int dbg_part_select(dbg_t *h, int part, uint32_t mask, uint32_t want, void *d_id
  * counts u32[n][4] by base code, succ_owner u8[n][4] (virtual shard; 0xFF none), succ_local u32[n][4], pflags u8[n] */
 int dbg_part_gather(dbg_t *h, int part, const void *d_ids, uint64_t n, void *d_keys, void *d_keys_hi, void *d_stamps,
                     void *d_counts, void *d_succ_owner, void *d_succ_local, void *d_pflags);
+/* ---- point queries on a graph in parts (the counterpart of dbg_lookup_nodes / dbg_score_sequences, which refuse such a
+ *      graph): after dbg_build_multipass and dbg_shard_build_multipass[_from] (any n_passes, k <= 31 and k > 31), before and
+ *      after dbg_multipass_finish, dbg_part_prune, the tip marks and dbg_part_segments.  The owner of a k-mer is a function
+ *      of the key alone -- the top log2(n_virtual) bits of its minimizer's bucket hash -- so the kernel routes every query
+ *      to its part and asks that part's directory (one table of part descriptors per handle, 144 B a part, built on the
+ *      first query of a graph).  Rows of found nodes: dbg_part_gather.  DBG_E_ARG (text in dbg_last_error) for a handle
+ *      without a graph in parts, for null pointers, and for a part that finished without a directory of the LDS engine
+ *      (the text names the part).  n = 0 / n_seq = 0 return DBG_OK and touch nothing. */
+/* owner[i] = virtual shard that owns k-mer i (0xFF: bits above 2k set); local[i] = its local id in that part if this handle
+ * holds the part and the k-mer is a node, else DBG_NO_NODE.  keys_hi NULL = zeros. */
+int dbg_part_lookup_nodes(dbg_t *h, const uint64_t *keys, const uint64_t *keys_hi, uint64_t n, uint8_t *owner, uint32_t *local);
+int dbg_part_lookup_nodes_device(dbg_t *h, const void *d_keys, const void *d_keys_hi, uint64_t n, void *d_owner, void *d_local);
+/* dbg_score_sequences over the windows whose k-mer THIS handle's parts own: a single-handle multi-pass graph gives the full
+ * scores; on a rank of ranks x passes the sums over ranks are getScore and the minimum over ranks is first_missing.
+ * A window whose k-mer another rank owns adds nothing and is not missing; a window that holds a character outside ACGT has
+ * no owner and is missing on every handle.  offsets[0] == 0, offsets non-decreasing (DBG_E_ARG otherwise). */
+int dbg_part_score_sequences(dbg_t *h, const char *chars, const uint64_t *offsets, uint64_t n_seq, uint64_t *scores, uint64_t *first_missing);
 /* sets flag bits on n nodes; d_newly (u8[n], device, may be NULL) = 1 where the bits were not all set before */
 int dbg_part_mark(dbg_t *h, int part, const void *d_ids, uint64_t n, uint32_t bits, void *d_newly);
 int dbg_part_clear(dbg_t *h, int part, uint32_t bits); /* ... and clears them on every node */
@@ -350,6 +368,7 @@ int dbg_get_stats(dbg_t *h, dbg_stats_t *out);
  *   directory entry alone / after reading keys; counted only while option "resolve_count" is 1.
  * "lookup_dir_calls" / "lookup_index_calls": dbg_lookup_nodes[_device] / dbg_score_sequences calls answered through the
  *   build's directory / through the sorted index; "lookup_index_builds": sorts that built such an index (one per graph).
+ * "part_lookup_calls": dbg_part_lookup_nodes[_device] / dbg_part_score_sequences calls that ran a kernel.
  * DBG_E_ARG for an unknown name. */
 int dbg_get_counter(dbg_t *h, const char *name, uint64_t *out);
 
@@ -418,7 +437,8 @@ int dbg_device_views(dbg_t *h, const void **d_keys, const void **d_counts, const
  *      `edge_count_table[edge]`, getScore): answered on the device, nothing of size n_nodes moves.
  *      They work on the graph of dbg_build (both engines, ACGT at k = 1..63; any other alphabet at k <= 11),
  *      dbg_build_from_walk(s) and dbg_import_graph, before and after prune, tips and walk.  DBG_E_ARG (text in
- *      dbg_last_error) without a graph, for a graph in parts (dbg_build_multipass), for one shard of several, and for the
+ *      dbg_last_error) without a graph, for a graph in parts (dbg_build_multipass: ask dbg_part_lookup_nodes /
+ *      dbg_part_score_sequences instead), for one shard of several, and for the
  *      generic alphabet at k >= 12, whose nodes have no packed key.  n = 0 returns DBG_OK and touches nothing.
  *      Two ways to a node, same answers: where the handle still holds the directory of the build that made the graph (a
  *      single-GPU dbg_build on the partitioned engines, k <= 31 and k > 31) a query costs its bucket hash, one directory

@@ -38,6 +38,7 @@ SYMBOLS = (
     "dbg_part_segments", "dbg_part_pflags", "dbg_scan_reads_for_keys", "dbg_set_orders", "dbg_part_segment_text",
     "dbg_build_from_walk", "dbg_build_from_walks",
     "dbg_lookup_nodes", "dbg_lookup_nodes_device", "dbg_gather_nodes", "dbg_score_sequences",
+    "dbg_part_lookup_nodes", "dbg_part_lookup_nodes_device", "dbg_part_score_sequences",
     "dbg_export_contig_texts", "dbg_write_contigs_fasta", "dbg_contig_output_stats",
 )
 
@@ -91,7 +92,8 @@ class WalkBlock(C.Structure):
 # lookup_*: which way the query calls found their nodes (the build's directory / the sorted index) and how often such an
 # index was built
 COUNTERS = ("extract_presplit_fallbacks", "extract_presplit_rehists", "resolve_direct_hits", "resolve_keyed",
-            "refine_crowded", "pull_crowded", "lookup_index_builds", "lookup_dir_calls", "lookup_index_calls")
+            "refine_crowded", "pull_crowded", "lookup_index_builds", "lookup_dir_calls", "lookup_index_calls",
+            "part_lookup_calls")
 
 
 class DbgError(RuntimeError):
@@ -206,6 +208,9 @@ def load_library():
         "dbg_lookup_nodes_device": (C.c_int, [H, vp, vp, C.c_uint64, vp]),
         "dbg_gather_nodes": (C.c_int, [H, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]),
         "dbg_score_sequences": (C.c_int, [H, vp, vp, C.c_uint64, vp, vp]),
+        "dbg_part_lookup_nodes": (C.c_int, [H, vp, vp, C.c_uint64, vp, vp]),
+        "dbg_part_lookup_nodes_device": (C.c_int, [H, vp, vp, C.c_uint64, vp, vp]),
+        "dbg_part_score_sequences": (C.c_int, [H, vp, vp, C.c_uint64, vp, vp]),
         "dbg_export_contig_texts": (C.c_int, [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]),
         "dbg_write_contigs_fasta": (C.c_int, [H, C.c_char_p, C.c_int, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, u64p]),
         "dbg_contig_output_stats": (C.c_int, [H, C.POINTER(ContigOutStats)]),
@@ -741,6 +746,54 @@ class Graph:
                 "flags": device_tensor(p[2].value, n, "uint8", dev), "row_ptr": device_tensor(p[3].value, n + 1, "int32", dev),
                 "col": device_tensor(p[4].value, ne, "int32", dev), "col_part": device_tensor(p[5].value, ne, "uint8", dev),
                 "cnt": device_tensor(p[6].value, ne, "int32", dev)}
+
+    # ---- point queries on a graph in parts (the kernel routes every key to the part that owns it)
+    def part_lookup_nodes(self, keys, keys_hi=None):
+        """-> (owner uint8, local uint32): the virtual shard that owns each packed k-mer (0xFF: bits above 2k set) and its
+        local id in that part where this handle holds the part and the k-mer is a node, else NO_NODE.  keys / keys_hi: numpy
+        uint64 arrays (keys_hi None: all zero), or int64 torch tensors on this handle's device -- then owner (uint8) and
+        local (int32) come back as device tensors (dbg_part_lookup_nodes_device)."""
+        if not isinstance(keys, np.ndarray) and hasattr(keys, "data_ptr"):
+            import torch
+            dev = self._dev()
+            for t in (keys, keys_hi):
+                if t is not None and t.device != dev:
+                    raise DbgError(DBG_E_ARG, f"part_lookup_nodes: a tensor on {t.device}, the handle is on {dev}")
+            if keys_hi is not None and keys_hi.numel() != keys.numel():
+                raise ValueError("keys and keys_hi differ in length")
+            keys = keys.contiguous()
+            keys_hi = None if keys_hi is None else keys_hi.contiguous()
+            n = keys.numel()
+            owner = torch.empty(n, dtype=torch.uint8, device=dev)
+            local = torch.empty(n, dtype=torch.int32, device=dev)
+            self._chk(self._lib.dbg_part_lookup_nodes_device(self._h, C.c_void_p(keys.data_ptr()) if n else None,
+                                                             C.c_void_p(keys_hi.data_ptr()) if keys_hi is not None and n else None,
+                                                             n, C.c_void_p(owner.data_ptr()) if n else None,
+                                                             C.c_void_p(local.data_ptr()) if n else None))
+            return owner, local
+        k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        hi = None if keys_hi is None else np.ascontiguousarray(keys_hi, dtype=np.uint64).reshape(-1)
+        if hi is not None and hi.size != k.size:
+            raise ValueError("keys and keys_hi differ in length")
+        owner, local = np.empty(k.size, dtype=np.uint8), np.empty(k.size, dtype=np.uint32)
+        self._chk(self._lib.dbg_part_lookup_nodes(self._h, _ptr(k) if k.size else None, _ptr(hi) if hi is not None and hi.size else None,
+                                                  k.size, _ptr(owner) if k.size else None, _ptr(local) if k.size else None))
+        return owner, local
+
+    def part_score_sequences(self, chars, offsets):
+        """score_sequences over the windows whose k-mer this handle's parts own -> (scores uint64[n], first_missing
+        uint64[n]); the sum / the minimum over the ranks of a sharded build are getScore / the first missing edge."""
+        c = np.frombuffer(chars, dtype=np.uint8) if not isinstance(chars, np.ndarray) else chars
+        c = np.ascontiguousarray(c, dtype=np.uint8).reshape(-1)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if o.size < 1 or int(o[-1]) != c.size:
+            raise ValueError("offsets must hold n + 1 entries and end at len(chars)")
+        n = o.size - 1
+        scores = np.zeros(n, dtype=np.uint64)
+        miss = np.full(n, np.iinfo(np.uint64).max, dtype=np.uint64)
+        self._chk(self._lib.dbg_part_score_sequences(self._h, _ptr(c) if c.size else None, _ptr(o), n, _ptr(scores) if n else None,
+                                                     _ptr(miss) if n else None))
+        return scores, miss
 
     # ---- traversal of a graph in parts (part_traversal.py): per-part primitives; ids and rows are torch tensors on the device
     def _dev(self):

@@ -222,6 +222,10 @@ struct dbg {
     Buf ar_lookup[3];         // sorted index of the current graph: keys, ids, keys_hi (two-word keys) -- 12 or 20 B per node
     bool lookup_built = false;
     uint64_t lookup_index_builds = 0, lookup_dir_calls = 0, lookup_index_calls = 0;  // dbg_get_counter
+    // a part of a multi-pass build: ar_dir, the SkRange array, sk_geom and the node arrays are those the part finished its
+    // count with on the LDS engine (multipass_parts says so; like dir_valid never inferred from a pointer)
+    bool part_dir_ok = false;
+    uint64_t part_lookup_calls = 0;  // dbg_part_lookup_nodes[_device] / dbg_part_score_sequences calls that ran (dbg_get_counter)
 
     dbg_stats_t stats{};
     dbg_ingest_stats_t ingest{};  // the last FASTA ingest
@@ -3407,6 +3411,7 @@ extern "C" int dbg_get_counter(dbg_t *h, const char *name, uint64_t *out) {
     if (n == "lookup_index_builds") { *out = h->lookup_index_builds; return DBG_OK; }
     if (n == "lookup_dir_calls") { *out = h->lookup_dir_calls; return DBG_OK; }
     if (n == "lookup_index_calls") { *out = h->lookup_index_calls; return DBG_OK; }
+    if (n == "part_lookup_calls") { *out = h->part_lookup_calls; return DBG_OK; }
     h->err = "unknown counter: " + n;
     return DBG_E_ARG;
 }
@@ -5650,6 +5655,11 @@ struct MultiPass {
     std::vector<uint8_t *> col_owner;  // per part: [n_edges of the part] owner part of every CSR column
     std::vector<uint8_t *> pflags;     // per part: [n_nodes] traversal flags (DBG_F_* layout + DBG_PF_*), dbg_part_prune allocates them
     std::vector<uint64_t> base;        // global id of the part's first node (prefix sums of the part sizes)
+    // query side (dbg_part_lookup_nodes, dbg_part_score_sequences): one LkPart per part in device memory, uploaded by the
+    // first query of this graph.  lk_table_valid says that d_lk_table describes THIS graph's parts; every multi-pass build
+    // starts a new MultiPass, so it starts false
+    LkPart *d_lk_table = nullptr;
+    bool lk_table_valid = false;
 };
 
 // A finished part keeps only what later reads need -- node arrays, CSR, ranges and directory -- cut to their real
@@ -5683,7 +5693,7 @@ static int part_compact(dbg *sub, uint64_t n_dir_entries) {
     CHK(buf_shrink(sub, sub->ar_csr[3], (n + 1) * 4));
     CHK(buf_shrink(sub, sub->ar_csr[1], ne * 4));
     CHK(buf_shrink(sub, sub->ar_csr[2], ne * 4));
-    sub->dir_valid = false;  // a part's directory serves dbg_part_answer only
+    sub->dir_valid = false;  // a part's directory serves dbg_part_answer and the part queries (part_dir_ok), never dbg_lookup_nodes
     CHK(buf_shrink(sub, sub->ar_dir, n_dir_entries * sizeof(SkDirEnt)));
     CHK(buf_shrink(sub, sub->ar_misc[MISC_RANGES], sub->sk_n_ranges * sizeof(SkRange)));
     sub->d_keys = (uint64_t *)sub->ar_node[0].p;
@@ -5707,6 +5717,8 @@ static void multipass_free(dbg *h) {
     if (!mp) return;
     for (auto *o : mp->col_owner) if (o) (void)hipFreeAsync(o, h->stream);
     for (auto *o : mp->pflags) if (o) (void)hipFree(o);
+    if (mp->d_lk_table) (void)hipFree(mp->d_lk_table);
+    mp->lk_table_valid = false;
     for (dbg *sub : mp->part) {
         if (!sub) continue;
         // A one-pass sharded build repeats on one handle (bench.py): its part handle is parked with its grow-only arenas,
@@ -5802,6 +5814,7 @@ static int multipass_parts(dbg *h, int k, int n_virtual, int v_first, int n_pass
         sub->est_scale_pct = h->est_scale_pct;
         if (!sub->d_scalars) HIPCHK(h, hipMalloc((void **)&sub->d_scalars, 128 * sizeof(uint64_t)));
         sub->k = k;
+        sub->part_dir_ok = false;
         uint64_t n_rec_p = 0;
         for (int r = 0; r < n_senders; ++r) {
             uint64_t before = 0;
@@ -5837,6 +5850,7 @@ static int multipass_parts(dbg *h, int k, int n_virtual, int v_first, int n_pass
             rc = sk_count_from_segments<ST, 4096, STI>(sub, k, nullptr, nullptr, 0, nullptr, n_rec_p, n_rec_p * (uint64_t)w, n_rec_p * (uint64_t)w,
                                                        in_w0, in_w1, (const ST *)nullptr, pw0, pw1, pst, 0, shard_bits, v_first + p, &pre);
         if (rc != DBG_OK) { h->err = "pass " + std::to_string(p) + ": " + sub->err; return rc; }
+        sub->part_dir_ok = n_rec_p != 0;  // both counts above are the LDS engines' and leave directory and ranges behind
         if (n_rec_p && n_passes > 1) {  // parts parked side by side: cut to size (one part: the estimate's slack may stay)
             const uint64_t own_cnt = sub->sk_n_buckets >> shard_bits;
             rc = part_compact(sub, (own_cnt + (sub->sk_n_ranges - sub->sk_n_buckets)) * (4096 / 64));
@@ -6383,6 +6397,157 @@ extern "C" int dbg_part_gather(dbg_t *h, int part, const void *d_ids, uint64_t n
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (e) { h->err = "dbg_part_gather: a node id is out of range"; return DBG_E_ARG; }
     return DBG_OK;
+}
+
+// ---- query side of a graph in parts (dbg_lookup.h): dbg_part_lookup_nodes, dbg_part_score_sequences
+static const char *const kNoParts =
+    "this handle holds no graph in parts (dbg_build_multipass / dbg_shard_build_multipass must run first)";
+
+// The descriptor table of the current graph's parts, in device memory: built from the MultiPass on the first query.
+static int part_table_ensure(dbg *h, MultiPass *mp) {
+    if (mp->n_passes < 1 || mp->n_passes > LK_MAX_PARTS) { h->err = "a handle holds at most 64 parts"; return DBG_E_ARG; }
+    for (int p = 0; p < mp->n_passes; ++p) {
+        const dbg *sub = mp->part[p];
+        if (sub && sub->n_nodes && (!sub->part_dir_ok || sub->sk_cap != 4096 || (sub->k > 31 && !sub->d_keys_hi))) {
+            h->err = "part " + std::to_string(p) + " finished without a directory of the LDS engine: no lookup by key";
+            return DBG_E_ARG;
+        }
+    }
+    if (mp->lk_table_valid) return DBG_OK;
+    std::vector<LkPart> tab((size_t)mp->n_passes);
+    for (int p = 0; p < mp->n_passes; ++p) {
+        const dbg *sub = mp->part[p];
+        LkPart &d = tab[p];
+        memset(&d, 0, sizeof(d));
+        if (!sub || !sub->n_nodes) continue;  // an empty part has no arrays: every key routed to it is absent
+        d.g = sub->sk_geom;
+        d.ranges = (const SkRange *)sub->ar_misc[MISC_RANGES].p;
+        d.n_buckets = sub->sk_n_buckets;
+        d.n_ranges = sub->sk_n_ranges;
+        d.dirs = (const SkDirEnt *)sub->ar_dir.p;
+        d.keys = sub->d_keys;
+        d.keys_hi = sub->k > 31 ? sub->d_keys_hi : nullptr;
+        d.n_nodes = sub->n_nodes;
+        d.flags = sub->d_flags;
+        d.row_ptr32 = sub->d_rowptr32;
+        d.ecnt = sub->d_ecnt;
+    }
+    if (!mp->d_lk_table) HIPCHK(h, hipMalloc((void **)&mp->d_lk_table, LK_MAX_PARTS * sizeof(LkPart)));
+    HIPCHK(h, hipMemcpyAsync(mp->d_lk_table, tab.data(), tab.size() * sizeof(LkPart), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // tab is a local
+    mp->lk_table_valid = true;
+    return DBG_OK;
+}
+
+template <bool WIDE>
+static LkPartsFinder<WIDE> parts_finder(const dbg *h, const MultiPass *mp) {
+    int shard_bits = 0;
+    while ((1 << shard_bits) < mp->n_virtual) ++shard_bits;
+    return LkPartsFinder<WIDE>{mp->d_lk_table, mp->n_passes, mp->v_first, shard_bits, h->k, sk_m_for_k(h->k)};
+}
+
+extern "C" int dbg_part_lookup_nodes_device(dbg_t *h, const void *d_keys, const void *d_keys_hi, uint64_t n, void *d_owner,
+                                            void *d_local) {
+    if (!h) return DBG_E_ARG;
+    if (!n) return DBG_OK;
+    if (!d_keys || !d_owner || !d_local) { h->err = "dbg_part_lookup_nodes: null keys, owner or local"; return DBG_E_ARG; }
+    MultiPass *mp = (MultiPass *)h->multipass;
+    if (!mp || !h->k) { h->err = kNoParts; return DBG_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(part_table_ensure(h, mp));
+    const LkMask m = lk_mask(2, h->k);
+    if (h->k > 31)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_part_lookup<true>), dim3(grid_for(n, 256)), dim3(256), 0, h->stream,
+                           parts_finder<true>(h, mp), (const uint64_t *)d_keys, (const uint64_t *)d_keys_hi, n, m,
+                           (uint8_t *)d_owner, (uint32_t *)d_local);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_part_lookup<false>), dim3(grid_for(n, 256)), dim3(256), 0, h->stream,
+                           parts_finder<false>(h, mp), (const uint64_t *)d_keys, (const uint64_t *)d_keys_hi, n, m,
+                           (uint8_t *)d_owner, (uint32_t *)d_local);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    ++h->part_lookup_calls;
+    return DBG_OK;
+}
+
+extern "C" int dbg_part_lookup_nodes(dbg_t *h, const uint64_t *keys, const uint64_t *keys_hi, uint64_t n, uint8_t *owner,
+                                     uint32_t *local) {
+    if (!h) return DBG_E_ARG;
+    if (!n) return DBG_OK;
+    if (!keys || !owner || !local) { h->err = "dbg_part_lookup_nodes: null keys, owner or local"; return DBG_E_ARG; }
+    if (!h->multipass || !h->k) { h->err = kNoParts; return DBG_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    uint64_t *d_k = nullptr, *d_hi = nullptr;
+    uint32_t *d_local = nullptr;
+    uint8_t *d_owner = nullptr;
+    int rc = DBG_OK;
+    do {
+        if ((rc = dev_alloc(h, &d_k, n)) != DBG_OK || (rc = dev_alloc(h, &d_local, n)) != DBG_OK ||
+            (rc = dev_alloc(h, &d_owner, n)) != DBG_OK)
+            break;
+        if (keys_hi && (rc = dev_alloc(h, &d_hi, n)) != DBG_OK) break;
+        hipError_t e = hipMemcpyAsync(d_k, keys, n * 8, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess && keys_hi) e = hipMemcpyAsync(d_hi, keys_hi, n * 8, hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) { h->err = std::string("dbg_part_lookup_nodes: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
+        if ((rc = dbg_part_lookup_nodes_device(h, d_k, d_hi, n, d_owner, d_local)) != DBG_OK) break;
+        e = hipMemcpy(owner, d_owner, n, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(local, d_local, n * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { h->err = std::string("dbg_part_lookup_nodes: ") + hipGetErrorString(e); rc = DBG_E_HIP; }
+    } while (0);
+    dev_free(d_k); dev_free(d_hi); dev_free(d_local); dev_free(d_owner);
+    return rc;
+}
+
+extern "C" int dbg_part_score_sequences(dbg_t *h, const char *chars, const uint64_t *offsets, uint64_t n_seq, uint64_t *scores,
+                                        uint64_t *first_missing) {
+    if (!h) return DBG_E_ARG;
+    if (!n_seq) return DBG_OK;
+    if (!offsets || !scores || !first_missing) { h->err = "dbg_part_score_sequences: null offsets, scores or first_missing"; return DBG_E_ARG; }
+    if (offsets[0] != 0) { h->err = "offsets[0] must be 0"; return DBG_E_ARG; }
+    for (uint64_t i = 0; i < n_seq; ++i)
+        if (offsets[i + 1] < offsets[i]) { h->err = "offsets must be non-decreasing"; return DBG_E_ARG; }
+    const uint64_t n_chars = offsets[n_seq];
+    if (n_chars && !chars) { h->err = "dbg_part_score_sequences: null chars"; return DBG_E_ARG; }
+    MultiPass *mp = (MultiPass *)h->multipass;
+    if (!mp || !h->k) { h->err = kNoParts; return DBG_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    CHK(part_table_ensure(h, mp));
+    for (uint64_t i = 0; i < n_seq; ++i) { scores[i] = 0; first_missing[i] = ~0ull; }
+    if (n_chars <= (uint64_t)h->k) return DBG_OK;  // no sequence holds a (k+1)-mer
+    uint8_t lut[256];
+    memset(lut, LK_BAD_CODE, sizeof(lut));
+    lut['A'] = 0; lut['C'] = 1; lut['T'] = 2; lut['G'] = 3;  // code = (ascii >> 1) & 3
+    // one device block: scores, first_missing, offsets, lut, text
+    const uint64_t at_miss = n_seq * 8, at_off = at_miss + n_seq * 8, at_lut = at_off + (n_seq + 1) * 8, at_txt = at_lut + 256;
+    uint8_t *blk = nullptr;
+    CHK(dev_alloc(h, &blk, at_txt + n_chars));
+    int rc = DBG_OK;
+    do {
+        hipError_t e = hipMemsetAsync(blk, 0, n_seq * 8, h->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(blk + at_miss, 0xFF, n_seq * 8, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(blk + at_off, offsets, (n_seq + 1) * 8, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(blk + at_lut, lut, 256, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(blk + at_txt, chars, n_chars, hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) { h->err = std::string("dbg_part_score_sequences: ") + hipGetErrorString(e); rc = DBG_E_HIP; break; }
+        const unsigned grid = grid_for(n_chars - (uint64_t)h->k, LK_TILE);
+#define DBG_PS_ARGS (const char *)(blk + at_txt), n_chars, (const uint64_t *)(blk + at_off), n_seq, (const uint8_t *)(blk + at_lut), \
+                    (unsigned long long *)blk, (unsigned long long *)(blk + at_miss)
+        if (h->k > 31)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_part_score_sequences<true>), dim3(grid), dim3(LK_NT), 0, h->stream,
+                               parts_finder<true>(h, mp), DBG_PS_ARGS);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_part_score_sequences<false>), dim3(grid), dim3(LK_NT), 0, h->stream,
+                               parts_finder<false>(h, mp), DBG_PS_ARGS);
+#undef DBG_PS_ARGS
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(scores, blk, n_seq * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(first_missing, blk + at_miss, n_seq * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) { h->err = std::string("dbg_part_score_sequences: ") + hipGetErrorString(e); rc = DBG_E_HIP; }
+    } while (0);
+    dev_free(blk);
+    if (rc == DBG_OK) ++h->part_lookup_calls;
+    return rc;
 }
 
 __global__ __launch_bounds__(256) void k_part_mark(const uint32_t *__restrict__ ids, uint64_t n, uint64_t n_nodes, uint8_t bits,

@@ -5,9 +5,13 @@
 //   directory     the builds of the LDS engines leave (SkDirEnt, SkRange) behind; dir_find / wdir_find in their comparing
 //                 form replay the table's probing: bucket hash, one directory entry, one run of keys
 //   sorted index  every other graph: (keys_hi, keys, id) sorted once on the device, then a lower bound per query
+// A graph in parts (multi-pass, a rank of a sharded build, ranks x passes) has a directory per part: LkPartsFinder names the
+// part that owns a key from the key's minimizer hash and asks that part's directory (dbg_part_lookup_nodes,
+// dbg_part_score_sequences).
 //
-// The first part of this file -- the lower-bound search and the rolling window encoder -- is plain C++: a host compiler
-// can include this file alone (tests/test_lookup_host.py does).  The kernels follow under __HIPCC__.
+// The first part of this file -- the lower-bound search, the rolling window encoder, the owner rule and the CSR count of the
+// part queries -- is plain C++: a host compiler can include this file alone (tests/test_lookup_host.py and
+// tests/test_part_lookup_host.py do).  The kernels follow under __HIPCC__.
 #pragma once
 #include <stdint.h>
 
@@ -90,6 +94,25 @@ DBG_LK_HD inline LkWindow lk_encode(const uint8_t *lut, const char *s, int k, in
 
 // A key handed in by a caller names a k-mer only if no bit above bits * k is set.
 DBG_LK_HD inline bool lk_key_in_range(uint64_t hi, uint64_t lo, LkMask m) { return !(hi & ~m.hi) && !(lo & ~m.lo); }
+
+// ---- graphs in parts -------------------------------------------------------------------------------------------------------
+// The virtual shard (part of a multi-pass build, rank of a sharded one, rank x pass) that owns a k-mer: the top shard_bits
+// of the 22-bit bucket hash of its minimizer -- the rule the builds split their records by (SkGeom::shard_bits).
+constexpr int LK_BUCKET_BITS = 22;
+
+DBG_LK_HD inline uint32_t lk_owner_of(uint32_t bucket_hash22, int shard_bits) {
+    return shard_bits ? bucket_hash22 >> (LK_BUCKET_BITS - shard_bits) : 0u;
+}
+
+// Count of out-edge `code` of `node` in a part's CSR.  A row holds one column per set successor bit ((flags >> 1) & 15),
+// in ascending code order (k_part_gather reads them that way): the column of `code` is the row's start plus the number of
+// successor bits below it; 0 where the node has no such edge.
+DBG_LK_HD inline uint32_t lk_csr_count(const uint8_t *flags, const uint32_t *row_ptr32, const uint32_t *ecnt, uint64_t node,
+                                       uint32_t code) {
+    const uint32_t pres = ((uint32_t)flags[node] >> 1) & 15u;
+    if (!((pres >> code) & 1u)) return 0u;
+    return ecnt[row_ptr32[node] + (uint32_t)__builtin_popcount(pres & ((1u << code) - 1u))];
+}
 
 }  // namespace dbgk
 
@@ -271,6 +294,162 @@ __global__ __launch_bounds__(LK_NT) void k_score_sequences(F f, const char *__re
                 else if (miss == ~0ull) miss = p - seq_beg;  // positions ascend: the first one is the smallest
             }
             lk_push(w, code, bits, m);
+        }
+    }
+    s_seq[threadIdx.x] = seq;
+    s_sum[threadIdx.x] = sum;
+    s_miss[threadIdx.x] = miss;
+    __syncthreads();
+    if (seq != ~0ull && (threadIdx.x == 0 || s_seq[threadIdx.x - 1] != seq)) {  // first thread of a group that ended in `seq`
+        for (int t = threadIdx.x + 1; t < LK_NT && s_seq[t] == seq; ++t) {
+            sum += s_sum[t];
+            if (s_miss[t] < miss) miss = s_miss[t];
+        }
+        lk_flush(seq, sum, miss, scores, first_missing);
+    }
+}
+
+// ---- graphs in parts: the finder routes to the part inside the kernel --------------------------------------------------------
+static_assert(LK_BUCKET_BITS == SK_BUCKET_BITS, "lk_owner_of splits the bucket hash the builds carry");
+
+// Everything a query needs of one part.  An empty part has no arrays: n_nodes == 0 and every pointer null.
+struct LkPart {
+    SkGeom g;
+    const SkRange *ranges;
+    uint64_t n_buckets, n_ranges;
+    const SkDirEnt *dirs;
+    const uint64_t *keys, *keys_hi;  // keys_hi null for k <= 31
+    uint64_t n_nodes;
+    const uint8_t *flags;
+    const uint32_t *row_ptr32, *ecnt;
+    uint64_t pad_;
+};
+static_assert(sizeof(LkPart) % 16 == 0, "the table is copied in 16-byte pieces");
+constexpr int LK_MAX_PARTS = 64;
+
+struct LkFound {
+    uint32_t owner;  // virtual shard of the k-mer
+    uint32_t part;   // its part on this handle, LK_MAX_PARTS or more: another rank's
+    uint32_t local;  // node id in that part, NO_NODE: no node (or not this handle's)
+};
+
+// The descriptor table (device memory, n_passes entries) is copied into LDS once per workgroup: load() by every thread of
+// the workgroup, then find().  Parts are built with 4096-slot tables only, so the directory has 64 entries per range.
+template <bool WIDE>
+struct LkPartsFinder {
+    const LkPart *table;  // device memory
+    int n_passes, v_first, shard_bits, k, m;
+
+    __device__ inline void load(uint4 *s_tab) const {
+        const uint4 *src = reinterpret_cast<const uint4 *>(table);
+        const int n16 = n_passes * (int)(sizeof(LkPart) / 16);
+        for (int i = threadIdx.x; i < n16; i += blockDim.x) s_tab[i] = src[i];
+        __syncthreads();
+    }
+
+    __device__ inline LkFound find(const uint4 *s_tab, uint64_t hi, uint64_t lo) const {
+        const K128 key{hi, lo};
+        const uint32_t bh = WIDE ? wkmer_bucket22(key, k, m) : kmer_bucket22(lo, k, m);
+        const uint32_t v = lk_owner_of(bh, shard_bits);
+        const uint32_t p = v - (uint32_t)v_first;  // wraps for v < v_first
+        LkFound r{v, p, NO_NODE};
+        if (p >= (uint32_t)n_passes) { r.part = LK_MAX_PARTS; return r; }
+        const LkPart *pt = reinterpret_cast<const LkPart *>(s_tab) + p;
+        const uint64_t n_nodes = pt->n_nodes;
+        if (!n_nodes) return r;
+        const SkGeom g = pt->g;
+        const uint64_t bucket = sk_bucket_of(bh, g);
+        if (bucket < g.own_lo || bucket >= g.own_lo + g.own_cnt) return r;
+        const SkDirEnt *dirs = pt->dirs;
+        const uint64_t *keys = pt->keys;
+        bool whole = true;
+        uint64_t ri = 0;
+        if (WIDE) {
+            const uint64_t *keys_hi = pt->keys_hi;
+            r.local = wdir_find(dirs, bucket - g.own_lo, keys, keys_hi, n_nodes, key, &whole);
+            if (!whole && lk_range_of(pt->ranges, bucket, pt->n_ranges, wsub_hash(key), &ri))
+                r.local = wdir_find(dirs, g.own_cnt + (ri - pt->n_buckets), keys, keys_hi, n_nodes, key);
+        } else {
+            r.local = dir_find<4096>(dirs, bucket - g.own_lo, keys, n_nodes, lo, &whole);
+            if (!whole && lk_range_of(pt->ranges, bucket, pt->n_ranges, sub_hash(lo), &ri))
+                r.local = dir_find<4096>(dirs, g.own_cnt + (ri - pt->n_buckets), keys, n_nodes, lo);
+        }
+        return r;
+    }
+};
+
+constexpr int LK_TAB16 = LK_MAX_PARTS * (int)(sizeof(LkPart) / 16);
+
+// owner[i] / local[i] of (keys_hi[i], keys[i]); one thread per query.  An absent key sets nothing anywhere else.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void k_part_lookup(LkPartsFinder<WIDE> f, const uint64_t *__restrict__ keys,
+                                                     const uint64_t *__restrict__ keys_hi, uint64_t n, LkMask m, uint8_t *owner,
+                                                     uint32_t *local) {
+    __shared__ uint4 s_tab[LK_TAB16];
+    f.load(s_tab);
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t lo = keys[i], hi = keys_hi ? keys_hi[i] : 0ull;
+    if (!lk_key_in_range(hi, lo, m)) { owner[i] = 0xFF; local[i] = NO_NODE; return; }
+    const LkFound r = f.find(s_tab, hi, lo);
+    owner[i] = (uint8_t)r.owner;
+    local[i] = r.local;
+}
+
+// k_score_sequences over the windows whose k-mer this handle's parts own (ACGT only: a graph in parts has no other
+// alphabet).  The body is the one above with two differences: the count comes from the found part's CSR, and a window of
+// another rank's k-mer adds nothing and is not missing.  A window that holds a character outside ACGT has no owner: every
+// handle records it as missing (the minimum over ranks does not care how many did).  Kept as a kernel of its own: the
+// finder's extra state (the LDS table, the part of a found node) would change the code of k_score_sequences.
+template <bool WIDE>
+__global__ __launch_bounds__(LK_NT) void k_part_score_sequences(LkPartsFinder<WIDE> f, const char *__restrict__ chars,
+                                                                uint64_t n_chars, const uint64_t *__restrict__ offsets,
+                                                                uint64_t n_seq, const uint8_t *__restrict__ lut,
+                                                                unsigned long long *scores, unsigned long long *first_missing) {
+    __shared__ uint4 s_tab[LK_TAB16];
+    __shared__ uint64_t s_seq[LK_NT];
+    __shared__ unsigned long long s_sum[LK_NT], s_miss[LK_NT];
+    f.load(s_tab);
+    const int k = f.k;
+    const uint64_t p0 = ((uint64_t)blockIdx.x * LK_NT + threadIdx.x) * LK_RUN;
+    uint64_t seq = ~0ull;
+    unsigned long long sum = 0, miss = ~0ull;
+    if (p0 + (uint64_t)k < n_chars) {
+        uint64_t a = 0, b = n_seq;  // invariant: offsets[a] <= p0 < offsets[b]
+        while (b - a > 1) {
+            const uint64_t mid = a + ((b - a) >> 1);
+            if (offsets[mid] <= p0) a = mid;
+            else b = mid;
+        }
+        seq = a;
+        uint64_t seq_beg = offsets[seq], seq_end = offsets[seq + 1];
+        const LkMask m = lk_mask(2, k);
+        LkWindow w = lk_empty();
+        for (int i = 0; i < k; ++i) lk_push(w, lut[(uint8_t)chars[p0 + i]], 2, m);
+        const uint64_t p_lim = n_chars - (uint64_t)k, p_end = p0 + (uint64_t)LK_RUN < p_lim ? p0 + (uint64_t)LK_RUN : p_lim;
+        for (uint64_t p = p0; p < p_end; ++p) {
+            if (p >= seq_end) {  // the next sequence that is not empty
+                lk_flush(seq, sum, miss, scores, first_missing);
+                sum = 0;
+                miss = ~0ull;
+                do { ++seq; seq_beg = offsets[seq]; seq_end = offsets[seq + 1]; } while (p >= seq_end);
+            }
+            const uint8_t code = lut[(uint8_t)chars[p + k]];
+            if (p + (uint64_t)k < seq_end) {
+                uint32_t c = 0;
+                bool mine = true;  // a window with a character outside ACGT is everybody's, and missing
+                if (w.run >= (uint32_t)k && code != LK_BAD_CODE) {
+                    const LkFound r = f.find(s_tab, w.hi, w.lo);
+                    mine = r.part < (uint32_t)LK_MAX_PARTS;
+                    if (r.local != NO_NODE) {
+                        const LkPart *pt = reinterpret_cast<const LkPart *>(s_tab) + r.part;
+                        c = lk_csr_count(pt->flags, pt->row_ptr32, pt->ecnt, r.local, code);
+                    }
+                }
+                if (c) sum += c;
+                else if (mine && miss == ~0ull) miss = p - seq_beg;  // positions ascend: the first one is the smallest
+            }
+            lk_push(w, code, 2, m);
         }
     }
     s_seq[threadIdx.x] = seq;

@@ -93,12 +93,35 @@ class _Net:
 
     def route(self, dest_rank, *cols):
         """Rows (parallel 1-D tensors) to the rank dest_rank[i]; returns the received columns."""
+        return self.route_there(dest_rank, *cols)[0]
+
+    def route_there(self, dest_rank, *cols):
+        """route() that also returns what the return leg needs: -> (received columns, plan)."""
         if self.world == 1:
-            return cols
+            return cols, None
         order = torch.argsort(dest_rank, stable=True)
         send = torch.bincount(dest_rank, minlength=self.world).tolist()
         recv = multi_gpu.exchange_counts(self.dist, send, self.device)
-        return tuple(multi_gpu.alltoallv(self.dist, c[order].contiguous(), send, recv) for c in cols)
+        got = tuple(multi_gpu.alltoallv(self.dist, c[order].contiguous(), send, recv) for c in cols)
+        return got, (order, send, recv)
+
+    def route_back(self, plan, *cols):
+        """The return leg of route_there: one answer row per received row (in the order received) back to the rank that sent
+        it, in the order of ITS rows -- the same counts swapped, then the inverse of the stable sort."""
+        if plan is None:
+            return cols
+        order, send, recv = plan
+        out = []
+        for c in cols:
+            if c.numel() != sum(recv):
+                raise RuntimeError(f"route_back: {c.numel()} answers for {sum(recv)} received rows")
+            back = multi_gpu.alltoallv(self.dist, c.contiguous(), recv, send)
+            if back.numel() != order.numel():
+                raise RuntimeError(f"route_back: {back.numel()} answers came back for {order.numel()} rows sent")
+            placed = torch.empty_like(back)
+            placed[order] = back
+            out.append(placed)
+        return tuple(out)
 
     def gather_all(self, *cols, widths=None):
         """Every rank's rows on every rank (rank order).  widths[i]: elements per row of column i (1 unless given)."""
@@ -127,6 +150,16 @@ class _Net:
         m = parts.min(dim=0).values.cpu().numpy().astype(np.uint64)
         m[m == np.uint64((1 << 63) - 1)] = np.iinfo(np.uint64).max
         return m.reshape(arr.shape)
+
+    def sum_u64(self, arr):
+        """element-wise sum over ranks of a numpy uint64 array (the sums stay below 2^63: they are edge-instance counts)"""
+        if self.world == 1:
+            return arr
+        t = torch.from_numpy(arr.view(np.int64).copy())
+        if self.dist.get_backend() == "nccl":
+            t = t.to(self.device)
+        parts = self.gather_all(t.reshape(-1))[0].reshape(self.world, -1)
+        return parts.sum(dim=0).cpu().numpy().astype(np.uint64).reshape(arr.shape)
 
 
 class PartTraversal:
@@ -169,6 +202,60 @@ class PartTraversal:
     def _cat(rows):
         keys = rows[0].keys()
         return {c: torch.cat([r[c] for r in rows]) for c in keys}
+
+    # ---- point queries on the graph in parts (include/dbg.h: dbg_part_lookup_nodes, dbg_part_score_sequences)
+    def lookup(self, keys, keys_hi=None):
+        """Collective.  Global ids (v << 32 | local, int64; -1 where the k-mer is no node of the whole graph) of THIS rank's
+        queries: packed k-mers as numpy uint64 arrays (-> numpy int64) or int64 tensors on the handle's device (-> tensor);
+        keys_hi None: zeros.  The kernel names the owner of every key; keys of other ranks travel to rank owner // P, are
+        answered there and come back in query order.  One process makes no exchange."""
+        as_numpy = isinstance(keys, np.ndarray) or not hasattr(keys, "data_ptr")
+        if as_numpy:
+            lo = torch.from_numpy(np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1).view(np.int64)).to(self.device)
+            hi = None if keys_hi is None else \
+                torch.from_numpy(np.ascontiguousarray(keys_hi, dtype=np.uint64).reshape(-1).view(np.int64)).to(self.device)
+        else:
+            lo, hi = keys.reshape(-1), None if keys_hi is None else keys_hi.reshape(-1)
+        if hi is not None and hi.numel() != lo.numel():
+            raise ValueError("keys and keys_hi differ in length")
+        owner, local = self.g.part_lookup_nodes(lo, hi)
+        owner, local = owner.to(torch.int64), _u32(local)
+        named = owner != 0xFF                       # 0xFF: bits above 2k, no k-mer at all
+        if bool((named & (owner >= self.nv)).any()):
+            raise RuntimeError(f"lookup: an owner byte names a virtual shard beyond the {self.nv} of this build")
+        dest = torch.div(owner, self.P, rounding_mode="floor")
+        if self.world > 1:
+            far = torch.nonzero(named & (dest != self.rank)).reshape(-1)
+            if bool((local[far] != NO_NODE).any()):
+                raise RuntimeError("lookup: a local id came back for a key that another rank owns")
+            z = torch.zeros(far.numel(), dtype=torch.int64, device=self.device)
+            (q_lo, q_hi), plan = self.net.route_there(dest[far], lo[far], z if hi is None else hi[far])
+            a_owner, a_local = self.g.part_lookup_nodes(q_lo.contiguous(), q_hi.contiguous())
+            a_owner = a_owner.to(torch.int64)
+            if bool((torch.div(a_owner, self.P, rounding_mode="floor") != self.rank).any()):
+                raise RuntimeError(f"lookup: rank {self.rank} was asked about a key it does not own (the ranks disagree on the owner rule)")
+            b_owner, b_local = self.net.route_back(plan, a_owner, _u32(a_local))
+            if bool((b_owner != owner[far]).any()):
+                raise RuntimeError("lookup: the owner of a key differs between the asking and the answering rank")
+            local[far] = b_local
+        gid = torch.where(named & (local != NO_NODE), (owner << 32) | local, torch.full_like(local, -1))
+        return gid.cpu().numpy() if as_numpy else gid
+
+    def score_sequences(self, chars, offsets):
+        """Collective; every rank passes the SAME sequences (chars + offsets[n + 1], as _dbg.Graph.score_sequences takes them).
+        -> (scores uint64[n], first_missing uint64[n]) of the whole graph on every rank: the sum over ranks of the partial
+        scores and the minimum over ranks of the first missing window."""
+        c = np.frombuffer(chars, dtype=np.uint8) if not isinstance(chars, np.ndarray) else chars
+        c = np.ascontiguousarray(c, dtype=np.uint8).reshape(-1)
+        o = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        mine = [int(o.size) - 1, int(c.size), int(c.sum(dtype=np.uint64)) & ((1 << 63) - 1)]
+        seen = self.net.all_ints(mine)
+        if any(list(s) != mine for s in seen):
+            raise RuntimeError(f"score_sequences: the ranks passed different sequences (n_seq, n_chars, text sum): {seen}")
+        scores, miss = self.g.part_score_sequences(c, o)
+        if scores.size == 0:
+            return scores, miss
+        return self.net.sum_u64(scores), self.net.min_u64(miss)
 
     # ---- a5 + a6
     def prune(self, threshold):
