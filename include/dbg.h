@@ -429,6 +429,38 @@ int dbg_export_contig_texts(dbg_t *h, const uint64_t *indices, uint64_t n, uint6
 int dbg_write_contigs_fasta(dbg_t *h, const char *path, int append, const uint64_t *indices, uint64_t n,
                             uint64_t first_number, int k_label, uint64_t chunk_bytes, uint64_t *bytes_written);
 int dbg_contig_output_stats(dbg_t *h, dbg_contig_out_stats_t *out);
+/* ---- the same two outputs for the walk over a graph in parts (csrc/dbg_partout.h).  The caller ranks the skeleton of
+ *      segments (one row per entry node, sorted by global id = virtual shard << 32 | local id) and hands it over once:
+ *      device pointers, d_gid int64[n], d_next int64[n] (row index of the entry the segment hands over to), d_go_on
+ *      uint8[n] (0 / 1), d_hops int64[n], d_rest uint64[n] with rest = hops + go_on * (1 + rest[next]) -- the characters
+ *      the chain appends from the entry to its end -- or UINT64_MAX where no contig can start (dead or unresolved).  The
+ *      library validates every row in a kernel before anything walks them (gid strictly ascending and inside the build's
+ *      virtual shards, next < n, local ids of the parts it holds below their n_nodes, hops within 32 bits, the rest
+ *      recurrence; DBG_E_ARG names what failed and nothing is kept), copies the rows (26 B a row), notes for each which of
+ *      its parts holds it, and builds the binary-lifting table up[l][i] (4 B a row and level; levels = the smallest count
+ *      with 2^levels - 1 >= the jumps of the longest chain).  The copy belongs to the graph: the next build, the next
+ *      dbg_part_set_skeleton (also a refused one) and dbg_destroy free it.  More than 2^32 - 1 rows: DBG_E_ARG.
+ *      dbg_part_prune must have run on every non-empty part. */
+int dbg_part_set_skeleton(dbg_t *h, uint64_t n_entries, const void *d_gid, const void *d_next, const void *d_go_on,
+                          const void *d_hops, const void *d_rest);
+/* Bytes [b0, b1) of the virtual text of n records -- record i is the contig that starts at skeleton row d_starts[i]
+ * (uint64[n], device; k + rest characters), bare (fasta 0: the texts concatenated) or as the FASTA records of
+ * dbg_write_contigs_fasta -- into d_out (device, 16-byte aligned, room for b1 - b0 rounded up to 16).  Characters of
+ * segments, and of start k-mers, in virtual shards this handle does not hold are the byte 0; headers and newlines are
+ * written by every handle: the bytewise maximum over the handles of a build is the text.  *total (may be NULL) receives
+ * the size of the whole text; b1 is cut to it; d_out NULL or b0 >= b1: sizes only.  b0 is a multiple of 4096, a window
+ * holds 1 GiB at most. */
+int dbg_part_contig_window(dbg_t *h, const void *d_starts, uint64_t n, int fasta, uint64_t first_number, int k_label, uint64_t b0,
+                           uint64_t b1, void *d_out, uint64_t *total);
+/* dbg_export_contig_texts / dbg_write_contigs_fasta with skeleton rows for contig indices (host arrays, the same streaming
+ * and dbg_contig_output_stats; peak_device_bytes includes the skeleton's copy and table).  Every chain listed must lie in
+ * parts of this handle (DBG_E_ARG otherwise: use dbg_part_contig_window on every rank).  DBG_E_ARG also for: no skeleton
+ * set for the current graph, a start >= n_entries or without rest, chunk_bytes no multiple of 4096, a path that cannot be
+ * opened.  n = 0 returns DBG_OK and touches nothing (not the file either); a refused call leaves the handle usable. */
+int dbg_part_export_contig_texts(dbg_t *h, const uint64_t *starts, uint64_t n, uint64_t *out_offsets, char *out_chars,
+                                 uint64_t capacity, uint64_t *n_chars);
+int dbg_part_write_contigs_fasta(dbg_t *h, const char *path, int append, const uint64_t *starts, uint64_t n,
+                                 uint64_t first_number, int k_label, uint64_t chunk_bytes, uint64_t *bytes_written);
 /* device-side views for callers that stay on the GPU (valid until the next build/destroy) */
 int dbg_device_views(dbg_t *h, const void **d_keys, const void **d_counts, const void **d_stamps,
                      const void **d_flags, const void **d_succ);

@@ -40,6 +40,7 @@ SYMBOLS = (
     "dbg_lookup_nodes", "dbg_lookup_nodes_device", "dbg_gather_nodes", "dbg_score_sequences",
     "dbg_part_lookup_nodes", "dbg_part_lookup_nodes_device", "dbg_part_score_sequences",
     "dbg_export_contig_texts", "dbg_write_contigs_fasta", "dbg_contig_output_stats",
+    "dbg_part_set_skeleton", "dbg_part_contig_window", "dbg_part_export_contig_texts", "dbg_part_write_contigs_fasta",
 )
 
 
@@ -214,6 +215,10 @@ def load_library():
         "dbg_export_contig_texts": (C.c_int, [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]),
         "dbg_write_contigs_fasta": (C.c_int, [H, C.c_char_p, C.c_int, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, u64p]),
         "dbg_contig_output_stats": (C.c_int, [H, C.POINTER(ContigOutStats)]),
+        "dbg_part_set_skeleton": (C.c_int, [H, C.c_uint64, vp, vp, vp, vp, vp]),
+        "dbg_part_contig_window": (C.c_int, [H, vp, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, vp, u64p]),
+        "dbg_part_export_contig_texts": (C.c_int, [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]),
+        "dbg_part_write_contigs_fasta": (C.c_int, [H, C.c_char_p, C.c_int, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, u64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -873,6 +878,56 @@ class Graph:
             self._chk(self._lib.dbg_part_segment_text(self._h, int(part), C.c_void_p(entries.data_ptr()), entries.numel(),
                                                       C.c_void_p(off.data_ptr()), C.c_void_p(chars.data_ptr()), total))
         return chars
+
+    def part_set_skeleton(self, gid, nxt, go_on, hops, rest):
+        """The ranked skeleton of the walk in parts (part_traversal.rank_skeleton): device tensors of equal length -- gid,
+        next, hops, rest int64 (rest -1 = UINT64_MAX: no contig), go_on bool or uint8.  The library validates the rows,
+        copies them and builds the lifting table; DbgError where a row is broken."""
+        import torch
+        cols = [gid, nxt, go_on, hops, rest]
+        n = gid.numel()
+        for c, want in zip(cols, (8, 8, 1, 8, 8)):
+            if c.numel() != n or c.element_size() != want or not c.is_contiguous() or c.dtype.is_floating_point:
+                raise ValueError("part_set_skeleton: five contiguous columns of equal length: int64, int64, bool / uint8, int64, int64")
+        torch.cuda.synchronize(self._dev())  # the library reads them on its own stream
+        self._chk(self._lib.dbg_part_set_skeleton(self._h, n, *[C.c_void_p(c.data_ptr()) if n else None for c in cols]))
+
+    def part_contig_window(self, starts, b0, b1, out=None, fasta=False, first_number=0, k_label=0):
+        """Bytes [b0, b1) of the virtual text of the records that start at the skeleton rows ``starts`` (int64 device tensor)
+        into ``out`` (uint8 device tensor, room for b1 - b0 rounded up to 16; None: sizes only) -> size of the whole text.
+        Bytes of parts another handle holds are 0."""
+        import torch
+        total = C.c_uint64()
+        if out is not None and out.numel() < (int(b1) - int(b0) + 15) // 16 * 16:
+            raise ValueError("part_contig_window: out is smaller than the window rounded up to 16 bytes")
+        torch.cuda.synchronize(self._dev())
+        self._chk(self._lib.dbg_part_contig_window(self._h, C.c_void_p(starts.data_ptr()) if starts.numel() else None, starts.numel(),
+                                                   1 if fasta else 0, int(first_number), int(k_label), int(b0), int(b1),
+                                                   None if out is None else C.c_void_p(out.data_ptr()), C.byref(total)))
+        return int(total.value)
+
+    def part_export_contig_texts(self, starts):
+        """-> (offsets uint64[n + 1], chars uint8): the texts of the contigs that start at the skeleton rows ``starts`` (host
+        array, any order, repeats allowed), concatenated; every listed chain must lie in parts of this handle."""
+        idx = np.ascontiguousarray(starts, dtype=np.uint64).reshape(-1)
+        off = np.zeros(idx.size + 1, dtype=np.uint64)
+        total = C.c_uint64()
+        self._chk(self._lib.dbg_part_export_contig_texts(self._h, _ptr(idx) if idx.size else None, idx.size, _ptr(off), None, 0,
+                                                         C.byref(total)))
+        chars = np.empty(total.value, dtype=np.uint8)
+        if total.value:
+            self._chk(self._lib.dbg_part_export_contig_texts(self._h, _ptr(idx), idx.size, None, _ptr(chars), chars.size,
+                                                             C.byref(total)))
+        return off, chars
+
+    def part_write_contigs_fasta(self, path, starts, append=True, first_number=0, k_label=0, chunk_bytes=0):
+        """``>SEQUENCE_{first_number + i}_{k_label}mer`` records of the contigs that start at the skeleton rows ``starts`` to
+        ``path``, streamed window by window; -> bytes written.  An empty list touches nothing."""
+        idx = np.ascontiguousarray(starts, dtype=np.uint64).reshape(-1)
+        n = C.c_uint64()
+        self._chk(self._lib.dbg_part_write_contigs_fasta(self._h, os.fsencode(path), 1 if append else 0, _ptr(idx) if idx.size else None,
+                                                         idx.size, int(first_number), int(k_label), int(chunk_bytes), C.byref(n)))
+        return int(n.value)
 
     def scan_reads_for_keys(self, k, keys, keys_hi=None, first_seen=True):
         """-> (read_flags uint8[n_reads], first_seen uint64[n_keys, 4] or None); numpy in and out (dbg_scan_reads_for_keys)."""

@@ -5660,7 +5660,11 @@ struct MultiPass {
     // starts a new MultiPass, so it starts false
     LkPart *d_lk_table = nullptr;
     bool lk_table_valid = false;
+    // output side (dbg_part_set_skeleton): the ranked skeleton of this graph's walk, its lifting table and the part table of
+    // the text source.  It belongs to THIS graph: a build starts a new MultiPass, so it starts without one
+    struct PartSkel *skel = nullptr;
 };
+static void part_skel_free(MultiPass *mp);
 
 // A finished part keeps only what later reads need -- node arrays, CSR, ranges and directory -- cut to their real
 // sizes (they were sized from an estimate, x 1.2): the parts are parked in HBM side by side.
@@ -5719,6 +5723,7 @@ static void multipass_free(dbg *h) {
     for (auto *o : mp->pflags) if (o) (void)hipFree(o);
     if (mp->d_lk_table) (void)hipFree(mp->d_lk_table);
     mp->lk_table_valid = false;
+    part_skel_free(mp);
     for (dbg *sub : mp->part) {
         if (!sub) continue;
         // A one-pass sharded build repeats on one handle (bench.py): its part handle is parked with its grow-only arenas,
@@ -7405,6 +7410,416 @@ extern "C" int dbg_contig_output_stats(dbg_t *h, dbg_contig_out_stats_t *out) {
     if (!h || !out) return DBG_E_ARG;
     *out = h->ctgout;
     return DBG_OK;
+}
+
+// ==========================================================================================
+// The same two outputs for a walk over a graph in parts (dbg_partout.h): the ranked skeleton of segments is copied to
+// the device once (dbg_part_set_skeleton: validation, copy, lifting table), then k_ctg_window runs with a text source
+// that descends the skeleton and steps through the parts this handle holds.
+// ==========================================================================================
+#include "dbg_partout.h"
+
+struct PartSkel {
+    uint64_t n = 0, max_segs = 1;  // entries; segments of the longest chain a contig starts
+    int levels = 0;
+    uint64_t *gid = nullptr, *rest = nullptr;
+    uint32_t *next = nullptr, *hops = nullptr, *up = nullptr;
+    uint8_t *go_on = nullptr, *part = nullptr;
+    PoPart *tab = nullptr;          // one descriptor per part, then n_nodes[n_passes] (PoHold reads those)
+    unsigned long long *err = nullptr;
+    uint64_t bytes = 0;             // device bytes of all of the above
+    PoSkel view() const { return PoSkel{gid, next, hops, rest, go_on, part, up, n, levels}; }
+};
+
+static void part_skel_free(MultiPass *mp) {
+    PartSkel *s = mp->skel;
+    if (!s) return;
+    dev_free(s->gid); dev_free(s->rest); dev_free(s->next); dev_free(s->hops); dev_free(s->up);
+    dev_free(s->go_on); dev_free(s->part); dev_free(s->tab); dev_free(s->err);
+    delete s;
+    mp->skel = nullptr;
+}
+
+__global__ __launch_bounds__(256) void k_po_check(PoRawSkel r, PoHold hd, unsigned long long *err) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= r.n) return;
+    const int f = po_row_fault(r, hd, i);
+    if (f) atomicOr(err, (unsigned long long)f);
+}
+
+// the validated rows in the library's own types; up0 is level 0 of the lifting table
+__global__ __launch_bounds__(256) void k_po_pack(PoRawSkel r, PoHold hd, uint64_t *gid, uint32_t *next, uint32_t *hops, uint64_t *rest,
+                                                 uint8_t *go_on, uint8_t *part, uint32_t *up0, uint32_t *cnt0) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= r.n) return;
+    const int p = po_part_of(hd, (uint64_t)r.gid[i]);
+    const uint8_t go = r.go_on[i] ? 1 : 0;
+    gid[i] = (uint64_t)r.gid[i];
+    next[i] = (uint32_t)r.next[i];
+    hops[i] = (uint32_t)r.hops[i];
+    rest[i] = r.rest[i];
+    go_on[i] = go;
+    part[i] = p < 0 ? PO_ELSEWHERE : (uint8_t)p;
+    up0[i] = go ? (uint32_t)r.next[i] : (uint32_t)i;
+    cnt0[i] = go;
+}
+
+// One doubling of (2^r-th segment after i, segments passed on the way); the end of a chain loops to itself and counts
+// nothing.  *more: a chain a contig may start on has not reached its end yet.
+__global__ __launch_bounds__(256) void k_po_count_round(uint64_t n, const uint32_t *__restrict__ ptr_in, const uint32_t *__restrict__ cnt_in,
+                                                        uint32_t *__restrict__ ptr_out, uint32_t *__restrict__ cnt_out,
+                                                        const uint64_t *__restrict__ rest, const uint8_t *__restrict__ go_on,
+                                                        unsigned long long *more) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t t = ptr_in[i], u = ptr_in[t];
+    ptr_out[i] = u;
+    cnt_out[i] = cnt_in[i] + cnt_in[t];
+    if (rest[i] != PO_NO_REST && go_on[u]) atomicOr(more, 1ull);
+}
+
+__global__ __launch_bounds__(256) void k_po_max_live(uint64_t n, const uint32_t *__restrict__ cnt, const uint64_t *__restrict__ rest,
+                                                     unsigned long long *out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t m = i < n && rest[i] != PO_NO_REST ? cnt[i] : 0u;
+    for (int d = 32; d; d >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, d));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, (unsigned long long)m);
+}
+
+// level l of the lifting table from level l - 1
+__global__ __launch_bounds__(256) void k_po_lift_level(uint64_t n, const uint32_t *__restrict__ below, uint32_t *__restrict__ lvl) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) lvl[i] = below[below[i]];
+}
+
+static const char *const kNoSkeleton =
+    "no skeleton set for this graph (dbg_part_set_skeleton must run after the build and the walk in parts)";
+
+static std::string po_fault_text(uint64_t f) {
+    std::string s;
+    auto add = [&](uint64_t bit, const char *what) { if (f & bit) s += std::string(s.empty() ? "" : "; ") + what; };
+    add(PO_BAD_GID, "a gid is negative or names a virtual shard beyond the build's");
+    add(PO_BAD_ORDER, "gid is not strictly ascending");
+    add(PO_BAD_LOCAL, "a local id is not below its part's n_nodes");
+    add(PO_BAD_NEXT, "a next is not below n_entries");
+    add(PO_BAD_HOPS, "a hops is negative or above 2^32 - 1");
+    add(PO_BAD_REST, "a rest is not hops + go_on * (1 + rest[next]) or continues at an entry without one");
+    return s;
+}
+
+extern "C" int dbg_part_set_skeleton(dbg_t *h, uint64_t n_entries, const void *d_gid, const void *d_next, const void *d_go_on,
+                                     const void *d_hops, const void *d_rest) {
+    if (!h) return DBG_E_ARG;
+    MultiPass *mp = (MultiPass *)h->multipass;
+    if (!mp || !h->k) { h->err = kNoParts; return DBG_E_ARG; }
+    part_skel_free(mp);  // the skeleton of an earlier walk goes, whatever becomes of this one
+    if (n_entries > 0xFFFFFFFFull) { h->err = "dbg_part_set_skeleton: more than 2^32 - 1 entries"; return DBG_E_ARG; }
+    if (n_entries && (!d_gid || !d_next || !d_go_on || !d_hops || !d_rest)) { h->err = "dbg_part_set_skeleton: null column"; return DBG_E_ARG; }
+    if (mp->n_passes < 1 || mp->n_passes > LK_MAX_PARTS) { h->err = "a handle holds at most 64 parts"; return DBG_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    const uint64_t n = n_entries;
+    const int P = mp->n_passes;
+    // the part table: descriptors, then the node counts the validation reads
+    const size_t tab_bytes = (size_t)P * sizeof(PoPart) + (size_t)P * 8;
+    std::vector<uint8_t> tab_host(tab_bytes, 0);
+    PoPart *tp = reinterpret_cast<PoPart *>(tab_host.data());
+    uint64_t *tn = reinterpret_cast<uint64_t *>(tab_host.data() + (size_t)P * sizeof(PoPart));
+    for (int p = 0; p < P; ++p) {
+        const dbg *sub = mp->part[p];
+        if (!sub || !sub->n_nodes) continue;  // an empty part holds no entry: any row that names it is refused
+        if (!mp->pflags[p]) { h->err = "dbg_part_set_skeleton: dbg_part_prune must run first"; return DBG_E_ARG; }
+        if (sub->k > 31 && !sub->d_keys_hi) { h->err = "dbg_part_set_skeleton: part " + std::to_string(p) + " has no high key words"; return DBG_E_ARG; }
+        tp[p] = PoPart{sub->d_keys, sub->k > 31 ? sub->d_keys_hi : nullptr, sub->d_flags, mp->pflags[p], sub->d_rowptr32, sub->d_col,
+                       mp->col_owner[p], sub->n_nodes};
+        tn[p] = sub->n_nodes;
+    }
+    PartSkel *s = new PartSkel();
+    mp->skel = s;  // owned from here on: every failure below frees it through part_skel_free
+    uint32_t *tmp[4] = {nullptr, nullptr, nullptr, nullptr};
+    auto body = [&]() -> int {
+        CHK(dev_alloc(h, (uint8_t **)&s->tab, tab_bytes));
+        CHK(dev_alloc(h, &s->err, 1));
+        HIPCHK(h, hipMemcpyAsync(s->tab, tab_host.data(), tab_bytes, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemsetAsync(s->err, 0, 8, h->stream));
+        s->bytes = tab_bytes + 8;
+        if (!n) { HIPCHK(h, hipStreamSynchronize(h->stream)); return DBG_OK; }
+        const PoRawSkel raw{(const int64_t *)d_gid, (const int64_t *)d_next, (const uint8_t *)d_go_on, (const int64_t *)d_hops,
+                            (const uint64_t *)d_rest, n};
+        const PoHold hd{mp->v_first, P, mp->n_virtual, reinterpret_cast<const uint64_t *>(reinterpret_cast<const uint8_t *>(s->tab) + (size_t)P * sizeof(PoPart))};
+        const unsigned grid = grid_for(n, 256);
+        // nothing below reads through a row before this kernel has passed all of them
+        hipLaunchKernelGGL(k_po_check, dim3(grid), dim3(256), 0, h->stream, raw, hd, s->err);
+        HIPCHK(h, hipGetLastError());
+        uint64_t f = 0;
+        HIPCHK(h, hipMemcpyAsync(&f, s->err, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (f) { h->err = "dbg_part_set_skeleton: " + po_fault_text(f); return DBG_E_ARG; }
+        CHK(dev_alloc(h, &s->gid, n)); CHK(dev_alloc(h, &s->rest, n)); CHK(dev_alloc(h, &s->next, n)); CHK(dev_alloc(h, &s->hops, n));
+        CHK(dev_alloc(h, &s->go_on, n)); CHK(dev_alloc(h, &s->part, n));
+        for (auto &t : tmp) CHK(dev_alloc(h, &t, n));
+        hipLaunchKernelGGL(k_po_pack, dim3(grid), dim3(256), 0, h->stream, raw, hd, s->gid, s->next, s->hops, s->rest, s->go_on, s->part,
+                           tmp[0], tmp[1]);
+        HIPCHK(h, hipGetLastError());
+        // segments of the longest chain: doubling until every chain a contig may start on has reached its end (rest falls
+        // strictly along those chains, so they end; the rows without rest may loop and are not waited for)
+        int in = 0;
+        for (int round = 0;; ++round) {
+            if (round > PO_MAX_LEVELS) { h->err = "dbg_part_set_skeleton: a chain did not end"; return DBG_E_HIP; }
+            HIPCHK(h, hipMemsetAsync(s->err, 0, 8, h->stream));
+            hipLaunchKernelGGL(k_po_count_round, dim3(grid), dim3(256), 0, h->stream, n, tmp[in], tmp[in + 1], tmp[2 - in], tmp[3 - in],
+                               s->rest, s->go_on, s->err);
+            HIPCHK(h, hipGetLastError());
+            HIPCHK(h, hipMemcpyAsync(&f, s->err, 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            in = 2 - in;
+            if (!f) break;
+        }
+        HIPCHK(h, hipMemsetAsync(s->err, 0, 8, h->stream));
+        hipLaunchKernelGGL(k_po_max_live, dim3(grid), dim3(256), 0, h->stream, n, tmp[in + 1], s->rest, s->err);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(&f, s->err, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemsetAsync(s->err, 0, 8, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        s->max_segs = f + 1;
+        s->levels = po_levels_for(f);
+        CHK(dev_alloc(h, &s->up, (uint64_t)s->levels * n));
+        if (s->levels) {
+            hipLaunchKernelGGL(k_po_pack, dim3(grid), dim3(256), 0, h->stream, raw, hd, s->gid, s->next, s->hops, s->rest, s->go_on, s->part,
+                               s->up, tmp[0]);
+            for (int l = 1; l < s->levels; ++l)  // one level per launch: level l reads all of level l - 1
+                hipLaunchKernelGGL(k_po_lift_level, dim3(grid), dim3(256), 0, h->stream, n, s->up + (uint64_t)(l - 1) * n, s->up + (uint64_t)l * n);
+            HIPCHK(h, hipGetLastError());
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        s->n = n;
+        s->bytes += n * (8 + 8 + 4 + 4 + 1 + 1) + std::max<uint64_t>((uint64_t)s->levels * n, 1) * 4;
+        return DBG_OK;
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(h->stream);
+    for (auto &t : tmp) dev_free(t);
+    if (rc != DBG_OK) part_skel_free(mp);
+    return rc;
+}
+
+// ---- the per-call arrays: text length of every record, its offsets, the record positions
+__global__ __launch_bounds__(256) void k_po_lengths(const uint64_t *__restrict__ starts, uint64_t n, PoSkel sk, int k, uint64_t walk_segs,
+                                                    uint64_t *len, uint32_t *list, unsigned long long *err) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    list[i] = (uint32_t)i;  // record i spells "contig" i of this call: the source maps it to starts[i]
+    len[i] = 0;
+    const uint64_t e = starts[i];
+    if (e >= sk.n) { atomicOr(err, 2ull); return; }
+    const uint64_t r = sk.rest[e];
+    if (r == PO_NO_REST) { atomicOr(err, 4ull); return; }
+    len[i] = (uint64_t)k + r;
+    // walk_segs != 0: every segment of the chain must be in a part of this handle (at most max_segs of them)
+    uint32_t s = (uint32_t)e;
+    for (uint64_t q = 0; q < walk_segs; ++q) {
+        if (sk.part[s] == PO_ELSEWHERE) { atomicOr(err, 8ull); return; }
+        if (!sk.go_on[s]) return;
+        s = sk.next[s];
+    }
+}
+
+struct PoLenAt {
+    const uint64_t *len;
+    __device__ uint64_t operator()(uint64_t i) const { return len[i]; }
+};
+struct PoRecLen {
+    const uint64_t *len;
+    uint64_t first_number;
+    uint32_t k_digits;
+    int fasta;
+    __device__ uint64_t operator()(uint64_t i) const { return co_record_len(fasta != 0, first_number + i, k_digits, len[i]); }
+};
+
+namespace {
+struct PartOut : CtgOut {
+    uint64_t *d_starts = nullptr, *d_len = nullptr, *d_off = nullptr;
+    explicit PartOut(dbg *hh) : CtgOut(hh) {}
+    ~PartOut() {
+        (void)hipStreamSynchronize(h->stream);
+        dev_free(d_starts); dev_free(d_len); dev_free(d_off);
+    }
+};
+}  // namespace
+
+static int partout_skel(dbg *h, MultiPass **mp_out, PartSkel **s_out) {
+    MultiPass *mp = (MultiPass *)h->multipass;
+    if (!mp || !h->k) { h->err = kNoParts; return DBG_E_ARG; }
+    if (!mp->skel) { h->err = kNoSkeleton; return DBG_E_ARG; }
+    *mp_out = mp;
+    *s_out = mp->skel;
+    return DBG_OK;
+}
+
+// d_starts (device) -> t: list, off, pos, total.  all_here: refuse chains that leave this handle's parts.
+static int partout_layout(PartOut &co, const PartSkel *s, const uint64_t *d_starts, uint64_t n, bool all_here, CoText &t) {
+    dbg *h = co.h;
+    if (n >= 0xFFFFFFF0ull) { h->err = "too many contigs for one call"; return DBG_E_CAPACITY; }
+    CHK(co.alloc(&co.d_len, n));
+    CHK(co.alloc(&co.d_off, n + 1));
+    CHK(co.alloc(&co.d_list, n));
+    CHK(co.alloc(&co.d_pos, n));
+    co.hold((std::max<uint64_t>((n + SCAN_TILE - 1) / SCAN_TILE, 1) + 1) * 8);  // scan partials (handle arena)
+    HIPCHK(h, hipMemsetAsync(s->err, 0, 8, h->stream));
+    hipLaunchKernelGGL(k_po_lengths, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, d_starts, n, s->view(), h->k,
+                       all_here ? s->max_segs : 0ull, co.d_len, co.d_list, s->err);
+    HIPCHK(h, hipGetLastError());
+    uint64_t f = 0, chars = 0;
+    HIPCHK(h, hipMemcpyAsync(&f, s->err, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemsetAsync(s->err, 0, 8, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (f & 2) { h->err = "a start is not below the skeleton's " + std::to_string(s->n) + " entries"; return DBG_E_ARG; }
+    if (f & 4) { h->err = "a start has no contig: its chain is dead or never resolved (rest is the sentinel)"; return DBG_E_ARG; }
+    if (f & 8) {
+        h->err = "a listed chain passes through a virtual shard this handle does not hold: fill windows on every rank with "
+                 "dbg_part_contig_window and combine them";
+        return DBG_E_ARG;
+    }
+    CHK(exclusive_scan(h, n, PoLenAt{co.d_len}, co.d_off, &chars));
+    HIPCHK(h, hipMemcpyAsync(co.d_off + n, &chars, 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // `chars` is a local
+    t.list = co.d_list;
+    t.off = co.d_off;
+    t.pos = co.d_pos;
+    t.n = n;
+    CHK(exclusive_scan(h, n, PoRecLen{co.d_len, t.first_number, t.k_digits, t.fasta}, co.d_pos, &t.total));
+    return DBG_OK;
+}
+
+static CoPartsSrc<PoDevParts> partout_src(const dbg *h, const MultiPass *mp, const PartSkel *s, const uint64_t *d_starts) {
+    return CoPartsSrc<PoDevParts>{PoDevParts{s->tab, mp->v_first, h->k, s->err}, s->view(), d_starts, h->k, 0u, 0u, 0u, 0u, -1};
+}
+
+// after the kernels: did the source meet a node that is no chain node where the skeleton says the segment goes on?
+static int partout_verdict(dbg *h, const PartSkel *s) {
+    uint64_t f = 0;
+    HIPCHK(h, hipMemcpyAsync(&f, s->err, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (f) {
+        (void)hipMemsetAsync(s->err, 0, 8, h->stream);
+        h->err = "the skeleton does not fit the graph's flags: a segment is longer than its chain (prune or marks changed since the walk?)";
+        return DBG_E_ARG;
+    }
+    return DBG_OK;
+}
+
+extern "C" int dbg_part_contig_window(dbg_t *h, const void *d_starts, uint64_t n, int fasta, uint64_t first_number, int k_label,
+                                      uint64_t b0, uint64_t b1, void *d_out, uint64_t *total) {
+    if (!h) return DBG_E_ARG;
+    if (total) *total = 0;
+    if (!n) return DBG_OK;
+    MultiPass *mp; PartSkel *s;
+    CHK(partout_skel(h, &mp, &s));
+    if (!d_starts) { h->err = "part_contig_window: null starts"; return DBG_E_ARG; }
+    if (b0 % (uint64_t)CO_TILE) { h->err = "part_contig_window: b0 " + std::to_string(b0) + " is no multiple of " + std::to_string(CO_TILE); return DBG_E_ARG; }
+    if (b1 < b0) { h->err = "part_contig_window: b1 below b0"; return DBG_E_ARG; }
+    if (k_label < 0) { h->err = "part_contig_window: k_label is negative"; return DBG_E_ARG; }
+    if (b1 - b0 > CO_MAX_CHUNK) { h->err = "part_contig_window: a window holds at most 1 GiB"; return DBG_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    PartOut co(h);
+    CoText t{};
+    t.fasta = fasta ? 1 : 0;
+    t.first_number = first_number;
+    t.k_label = (uint32_t)(k_label ? k_label : h->k);
+    t.k_digits = co_digits(t.k_label);
+    CHK(partout_layout(co, s, (const uint64_t *)d_starts, n, false, t));
+    if (total) *total = t.total;
+    if (b1 > t.total) b1 = t.total;
+    if (!d_out || b0 >= b1) return DBG_OK;
+    const uint64_t tiles = (b1 - b0 + (uint64_t)CO_TILE - 1) / (uint64_t)CO_TILE;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ctg_window<CoPartsSrc<PoDevParts>>), dim3((unsigned)tiles), dim3(CO_NT), 0, h->stream, t, b0, b1,
+                       partout_src(h, mp, s, (const uint64_t *)d_starts), (char *)d_out);
+    HIPCHK(h, hipGetLastError());
+    return partout_verdict(h, s);
+}
+
+// the host-facing calls: starts from the host, every listed chain on this handle, streamed through ctgout_stream
+static int partout_host_layout(PartOut &co, const PartSkel *s, const uint64_t *starts, uint64_t n, CoText &t) {
+    dbg *h = co.h;
+    CHK(co.alloc(&co.d_starts, n));
+    HIPCHK(h, hipMemcpyAsync(co.d_starts, starts, n * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return partout_layout(co, s, co.d_starts, n, true, t);
+}
+
+static int partout_run(PartOut &co, const MultiPass *mp, const PartSkel *s, const CoText &t, uint64_t chunk, char *dst, const char *path) {
+    dbg *h = co.h;
+    h->ctgout.lift_bytes = (uint64_t)s->levels * s->n * 4;
+    int rc = t.total ? ctgout_stream(co, t, partout_src(h, mp, s, co.d_starts), chunk, dst, path) : DBG_OK;
+    if (rc == DBG_OK) rc = partout_verdict(h, s);
+    h->ctgout.peak_device_bytes = co.peak + s->bytes;  // the skeleton's copy and its table stay on the device between calls
+    return rc;
+}
+
+extern "C" int dbg_part_export_contig_texts(dbg_t *h, const uint64_t *starts, uint64_t n, uint64_t *out_offsets, char *out_chars,
+                                            uint64_t capacity, uint64_t *n_chars) {
+    if (!h) return DBG_E_ARG;
+    using clk = std::chrono::steady_clock;
+    const auto t_call = clk::now();
+    if (!n_chars || (n && !starts)) { h->err = "part_export_contig_texts: starts and n_chars are required"; return DBG_E_ARG; }
+    *n_chars = 0;
+    if (!n) {
+        if (out_offsets) out_offsets[0] = 0;
+        return DBG_OK;
+    }
+    MultiPass *mp; PartSkel *s;
+    CHK(partout_skel(h, &mp, &s));
+    HIPCHK(h, hipSetDevice(h->device));
+    PartOut co(h);
+    CoText t{};
+    CHK(partout_host_layout(co, s, starts, n, t));
+    if (out_offsets) {
+        HIPCHK(h, hipMemcpyAsync(out_offsets, co.d_pos, n * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        out_offsets[n] = t.total;
+    }
+    *n_chars = t.total;
+    if (!out_chars) return DBG_OK;
+    if (capacity < t.total) { h->err = "part_export_contig_texts: capacity smaller than the texts"; return DBG_E_CAPACITY; }
+    const uint64_t chunk = ctgout_chunk_of(h, 0);
+    h->ctgout = dbg_contig_out_stats_t{};
+    h->ctgout.chunk_bytes = chunk;
+    const int rc = partout_run(co, mp, s, t, chunk, out_chars, nullptr);
+    h->ctgout.ms_total = std::chrono::duration<double, std::milli>(clk::now() - t_call).count();
+    return rc;
+}
+
+extern "C" int dbg_part_write_contigs_fasta(dbg_t *h, const char *path, int append, const uint64_t *starts, uint64_t n,
+                                            uint64_t first_number, int k_label, uint64_t chunk_bytes, uint64_t *bytes_written) {
+    if (!h) return DBG_E_ARG;
+    using clk = std::chrono::steady_clock;
+    const auto t_call = clk::now();
+    if (bytes_written) *bytes_written = 0;
+    if (!n) return DBG_OK;
+    if (!path || !starts) { h->err = "part_write_contigs_fasta: path and starts are required"; return DBG_E_ARG; }
+    if (!co_chunk_ok(chunk_bytes)) {
+        h->err = "part_write_contigs_fasta: chunk_bytes " + std::to_string(chunk_bytes) + " is no multiple of " + std::to_string(CO_TILE);
+        return DBG_E_ARG;
+    }
+    if (k_label < 0) { h->err = "part_write_contigs_fasta: k_label is negative"; return DBG_E_ARG; }
+    MultiPass *mp; PartSkel *s;
+    CHK(partout_skel(h, &mp, &s));
+    HIPCHK(h, hipSetDevice(h->device));
+    PartOut co(h);
+    CoText t{};
+    t.fasta = 1;
+    t.first_number = first_number;
+    t.k_label = (uint32_t)(k_label ? k_label : h->k);
+    t.k_digits = co_digits(t.k_label);
+    CHK(partout_host_layout(co, s, starts, n, t));  // a refused list leaves the file alone
+    co.fd = open(path, O_WRONLY | O_CREAT | O_CLOEXEC | (append ? O_APPEND : O_TRUNC), 0666);
+    if (co.fd < 0) { h->err = std::string(path) + ": " + strerror(errno); return DBG_E_ARG; }
+    const uint64_t chunk = ctgout_chunk_of(h, chunk_bytes);
+    h->ctgout = dbg_contig_out_stats_t{};
+    h->ctgout.chunk_bytes = chunk;
+    const int rc = partout_run(co, mp, s, t, chunk, nullptr, path);
+    if (bytes_written) *bytes_written = h->ctgout.bytes_written;
+    h->ctgout.ms_total = std::chrono::duration<double, std::milli>(clk::now() - t_call).count();
+    return rc;
 }
 
 #include "dbg_nextk.h"  // dbg_build_from_walk: the next k's graph from the last walk

@@ -45,11 +45,15 @@ def rank_skeleton(e, k, keep=False):
     gid (global id), kind (K_*), next (global id of the entry a REMOTE segment hands over to), hops, score, exit (count of the
     leaving edge), stamp, start (1: indegree 0).  Entering a pulled node ends the path at the previous one (debruijn.py:
     292-302); a chain that meets a cycle inside a part (K_CYCLE) or across parts (never resolves) emits nothing (:289-290), nor
-    does a start that is itself pulled.  -> (dict(stamp, length, score) numpy in dict order of the starts, skeleton or None)."""
+    does a start that is itself pulled.  -> (dict(stamp, length, score) numpy in dict order of the starts, skeleton or None).
+    The skeleton (``keep``) stays where ``e`` lives: the columns sorted by gid -- gid, next (row index), go_on, hops -- and
+    rest, the characters the chain appends from the entry's segment to its end: hops + go_on * (1 + rest[next]), -1 (the
+    library's UINT64_MAX) where the chain is dead or never resolved; emit (numpy): the row of contig i's start."""
     n = e["gid"].numel()
     if n == 0:
         z = np.empty(0, dtype=np.int64)
-        sk = {"gid": z, "next": z, "go_on": z.astype(bool), "hops": z, "emit": z} if keep else None
+        zt = e["gid"].reshape(-1)
+        sk = {"gid": zt, "next": zt, "go_on": zt.to(torch.bool), "hops": zt, "rest": zt, "emit": z} if keep else None
         return {"stamp": z.astype(np.uint64), "length": z, "score": z}, sk
     o = torch.argsort(e["gid"])
     e = {c: t[o] for c, t in e.items()}
@@ -58,7 +62,7 @@ def rank_skeleton(e, k, keep=False):
     j = torch.searchsorted(e["gid"], want).clamp_(max=n - 1)
     assert bool((e["gid"][j] == want).all()), "a chain continues at a node that is no entry"
     go_on = remote & (e["kind"][j] != K_PULLED)     # entering a pulled node ends the path at the previous one
-    sk = {"gid": e["gid"].cpu().numpy(), "next": j.cpu().numpy(), "go_on": go_on.cpu().numpy(), "hops": e["hops"].cpu().numpy()} if keep else None
+    sk = {"gid": e["gid"].contiguous(), "next": j.contiguous(), "go_on": go_on.contiguous(), "hops": e["hops"].contiguous()} if keep else None
     hops = e["hops"] + go_on.to(torch.int64)
     score = e["score"] + torch.where(go_on, e["exit"], torch.zeros_like(e["exit"]))
     dead = e["kind"] == K_CYCLE
@@ -78,6 +82,7 @@ def rank_skeleton(e, k, keep=False):
     em = torch.nonzero(emit).reshape(-1)
     em = em[torch.argsort(e["stamp"][em])]           # dict order of the starts (stamps are distinct), sorted on the device
     if keep:
+        sk["rest"] = torch.where(done & ~dead, hops, torch.full_like(hops, -1))   # the jumping left the chain's sum in hops
         sk["emit"] = em.cpu().numpy()                # skeleton index of contig i's start
     return {"stamp": e["stamp"][em].cpu().numpy().astype(np.uint64), "length": (hops[em] + k).cpu().numpy(),
             "score": score[em].cpu().numpy()}, sk
@@ -406,8 +411,9 @@ class PartTraversal:
     def walk_index(self, keep_skeleton=False):
         """output_contigs (debruijn.py:326-347) with the branch list of construct_graph: the contig index in dict order of the
         starts -- dict(stamp uint64, length int64, score int64) numpy arrays.  A start whose chain runs into a cycle emits
-        nothing (debruijn.py:289-290), nor does a start that was pulled.  keep_skeleton: keep the segment skeleton on the
-        host (26 bytes per entry) so that ``contig_texts`` can spell contigs afterwards."""
+        nothing (debruijn.py:289-290), nor does a start that was pulled.  keep_skeleton: hand the ranked skeleton to the
+        library (dbg_part_set_skeleton: it stays on the device, with its lifting table) so that ``contig_texts`` and
+        ``write_contigs_fasta`` can spell contigs afterwards; the host keeps 16 bytes per CONTIG (start row, length)."""
         g, P, dev = self.g, self.P, self.device
         # entries: the starts (indegree 0) and every node a chain of another part continues at
         sends = []
@@ -440,87 +446,99 @@ class PartTraversal:
         e = dict(zip(cols, self.net.gather_all(*[mine[c] for c in cols])))
         index, skeleton = rank_skeleton(e, self.k, keep_skeleton)
         if keep_skeleton:
-            self.skeleton = skeleton
+            g.part_set_skeleton(skeleton["gid"], skeleton["next"], skeleton["go_on"], skeleton["hops"], skeleton["rest"])
+            self.skeleton = {"emit": skeleton["emit"].astype(np.int64), "length": index["length"], "score": index["score"]}
         return index
+
+    # ---- contig text (include/dbg.h: dbg_part_export_contig_texts, dbg_part_write_contigs_fasta, dbg_part_contig_window)
+    WINDOW_BYTES = 4 << 20   # window of the several-rank path where the caller names none (the library's default)
+
+    def _starts(self, which):
+        """contig positions -> skeleton rows of their starts (numpy int64); None: the driver's order, score descending and
+        stable over the index order (II_assembleFromReads.py:64)."""
+        sk = getattr(self, "skeleton", None)
+        if sk is None:
+            raise _dbg.DbgError(_dbg.DBG_E_ARG, "part_traversal: walk_index(keep_skeleton=True) must run first")
+        if which is None:
+            which = np.argsort(-sk["score"], kind="stable")
+        which = np.asarray(list(which) if not isinstance(which, np.ndarray) else which, dtype=np.int64).reshape(-1)
+        n = sk["emit"].size
+        if which.size and (int(which.min()) < -n or int(which.max()) >= n):
+            raise IndexError(f"contig index out of range (the walk has {n} contigs)")
+        return which, sk["emit"][which]
+
+    def _windows(self, starts, fasta, first_number, k_label, chunk, sink):
+        """Several ranks: every rank fills window after window with the bytes of ITS parts (the others' are 0), the windows
+        are gathered and combined by an elementwise maximum, ``sink(bytes as a numpy view)`` takes each.  -> total bytes."""
+        dev = self.device
+        d_starts = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.int64)).to(dev)
+        total = self.g.part_contig_window(d_starts, 0, 0, None, fasta, first_number, k_label)
+        buf = torch.empty(min(chunk, -(-total // 4096) * 4096), dtype=torch.uint8, device=dev)
+        for b0 in range(0, total, chunk):
+            b1 = min(total, b0 + chunk)
+            self.g.part_contig_window(d_starts, b0, b1, buf, fasta, first_number, k_label)
+            (parts,) = self.net.gather_all(buf[:b1 - b0])
+            sink(parts.reshape(self.world, -1).max(dim=0).values.cpu().numpy())
+        return total
+
+    def contig_texts_packed(self, which):
+        """-> (offsets uint64[n + 1], chars uint8): the texts of the contigs ``which`` (positions in the index, any order,
+        repeats allowed), concatenated.  Collective: every rank calls it with the same list and gets the same bytes."""
+        which, starts = self._starts(which)
+        if self.world == 1:
+            return self.g.part_export_contig_texts(starts)
+        off = np.zeros(which.size + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(self.skeleton["length"][which], dtype=np.uint64)
+        chars = np.empty(int(off[-1]), dtype=np.uint8)
+        if which.size:
+            at = [0]
+
+            def sink(w):
+                chars[at[0]:at[0] + w.size] = w
+                at[0] += w.size
+            total = self._windows(starts, False, 0, 0, self.WINDOW_BYTES, sink)
+            if total != chars.size or at[0] != total:
+                raise RuntimeError(f"contig_texts: the library lays out {total} characters, the index {chars.size}")
+        return off, chars
+
+    def write_contigs_fasta(self, path, which=None, first_number=0, k_label=0, append=True, chunk_bytes=0):
+        """``>SEQUENCE_{first_number + i}_{k_label}mer\\n{contig}\\n`` (II_assembleFromReads.py:64-69) for the contigs ``which``
+        (None: all of them in the driver's order) to ``path``; k_label 0: this k.  Collective; rank 0 alone opens and
+        writes the file, every rank returns the bytes written.  chunk_bytes: window size, a multiple of 4096 (0: default)."""
+        which, starts = self._starts(which)
+        if chunk_bytes % 4096:
+            raise _dbg.DbgError(_dbg.DBG_E_ARG, f"write_contigs_fasta: chunk_bytes {chunk_bytes} is no multiple of 4096")
+        if self.world == 1:
+            return self.g.part_write_contigs_fasta(path, starts, append=append, first_number=first_number, k_label=k_label,
+                                                   chunk_bytes=chunk_bytes)
+        if not which.size:
+            return 0
+        f = open(path, "ab" if append else "wb") if self.rank == 0 else None
+        try:
+            return self._windows(starts, True, first_number, k_label, chunk_bytes or self.WINDOW_BYTES,
+                                 (lambda w: f.write(w.tobytes())) if f else (lambda w: None))
+        finally:
+            if f:
+                f.close()
 
     def contig_texts(self, which):
         """The text of the contigs ``which`` (positions in the index ``walk_index(keep_skeleton=True)`` returned) -- every rank
         calls it with the same list and gets the same strings.  A contig is its start k-mer followed by the last base of every
-        node its chain appends (debruijn.py:296-299); every part spells the segments it holds (dbg_part_segment_text)."""
-        sk, g, dev = self.skeleton, self.g, self.device
-        which = [int(c) for c in which]
-        if not which:
-            return []
-        seg, owner_of_seg, first = [], [], []
-        for c in which:
-            i = int(sk["emit"][c])
-            first.append(len(seg))
-            seg.append(i)
-            while sk["go_on"][i]:
-                i = int(sk["next"][i])
-                seg.append(i)
-        first.append(len(seg))
-        seg = np.asarray(seg, dtype=np.int64)
-        gid = sk["gid"][seg] if seg.size else np.empty(0, dtype=np.int64)
-        v = gid >> 32
-        plen = 1 + sk["hops"][seg] if seg.size else np.empty(0, dtype=np.int64)
-        # my pieces, in segment order; then everybody's
-        pos_l, bytes_l = [], []
-        for p in range(self.P):
-            mine = np.nonzero(v == self._v(p))[0]
-            if not mine.size:
-                continue
-            ent = torch.from_numpy((gid[mine] & 0xFFFFFFFF).astype(np.uint32).view(np.int32).copy()).to(dev)
-            off = torch.zeros(mine.size + 1, dtype=torch.int64, device=dev)
-            off[1:] = torch.cumsum(torch.from_numpy(plen[mine]).to(dev), 0)
-            bytes_l.append(g.part_segment_text(p, ent, off))
-            pos_l.append(torch.from_numpy(mine).to(dev))
-        pos = torch.cat(pos_l) if pos_l else torch.empty(0, dtype=torch.int64, device=dev)
-        byts = torch.cat(bytes_l) if bytes_l else torch.empty(0, dtype=torch.uint8, device=dev)
-        # the start k-mers
-        starts = np.asarray([int(sk["emit"][c]) for c in which], dtype=np.int64)
-        sg = sk["gid"][starts] if starts.size else np.empty(0, dtype=np.int64)
-        kl, kh, kg = [], [], []
-        for p in range(self.P):
-            mine = np.nonzero((sg >> 32) == self._v(p))[0]
-            if mine.size:
-                ids = torch.from_numpy((sg[mine] & 0xFFFFFFFF).astype(np.uint32).view(np.int32).copy()).to(dev)
-                r = g.part_gather(p, ids, what=("keys", "keys_hi"))
-                kl.append(r["keys"]); kh.append(r["keys_hi"]); kg.append(torch.from_numpy(sg[mine]).to(dev))
-        z = torch.empty(0, dtype=torch.int64, device=dev)
-        kl, kh, kg = (torch.cat(x) if x else z for x in (kl, kh, kg))
-        if self.world > 1:
-            n_mine = pos.numel()
-            sizes = [m[0] for m in self.net.all_ints([n_mine])]
-            (pos,) = self.net.gather_all(pos)
-            # the bytes: variable-length rows, gathered as one flat column of known per-rank sizes
-            nb = [m[0] for m in self.net.all_ints([byts.numel()])]
-            byts = multi_gpu.alltoallv(self.net.dist, byts.repeat(self.world), [byts.numel()] * self.world, nb)
-            kl, kh, kg = self.net.gather_all(kl, kh, kg)
-            del sizes
-        pos, byts = pos.cpu().numpy(), byts.cpu().numpy()
-        # pieces arrive grouped by rank and part, each group in ascending segment position: place them by position
-        lens = plen[pos]
-        src_off = np.concatenate([[0], np.cumsum(lens)])
-        dst_off = np.concatenate([[0], np.cumsum(plen)])
-        flat = np.empty(int(dst_off[-1]), dtype=np.uint8)
-        for q, a in zip(pos.tolist(), range(pos.size)):
-            flat[dst_off[q]:dst_off[q + 1]] = byts[src_off[a]:src_off[a + 1]]
-        kmers = dict(zip(kg.cpu().numpy().tolist(), _dbg.decode_keys(kl.cpu().numpy().astype(np.uint64), self.k,
-                                                                        keys_hi=kh.cpu().numpy().astype(np.uint64))))
-        out = []
-        for ci, c in enumerate(which):
-            a, b = first[ci], first[ci + 1]
-            body = flat[dst_off[a] + 1:dst_off[b]].tobytes().decode("ascii")   # the start segment's first character is the start's own last base
-            # drop the entry character of no later segment: entering a node appends its last base
-            out.append(kmers[int(sg[ci])] + body)
-        return out
+        node its chain appends (debruijn.py:296-299); one batched export, one ``str`` per contig at the end."""
+        off, chars = self.contig_texts_packed(which)
+        text = chars.tobytes().decode("ascii")
+        o = off.tolist()
+        return [text[o[i]:o[i + 1]] for i in range(len(o) - 1)]
+
+
+BATCH_CHARS = 256 << 20  # characters of one batched text export: bounds the host copy (as debruijn.BATCH_CHARS does)
 
 
 class PartContigs:
     """The contigs of a graph in parts, in the reference's order (dict order of the starts): ``lengths``, ``scores`` (getScore,
-    II_assembleFromReads.py:14-18), ``start_stamps``; ``texts(indices)`` spells any of them (collective: every rank asks for
-    the same ones).  At scale the contigs overlap massively -- 2e12 characters for 10 M reads -- so the text is on demand."""
+    II_assembleFromReads.py:14-18), ``start_stamps``; ``texts(indices)``, slices, iteration and ``packed()`` spell them (all
+    collective: every rank asks for the same ones), one batched export per block of contigs; ``write_fasta`` writes the
+    driver's file.  At scale the contigs overlap massively -- 2e12 characters for 10 M reads -- so the text is on demand."""
 
     def __init__(self, traversal, index):
         self._t = traversal
@@ -529,8 +547,34 @@ class PartContigs:
     def __len__(self):
         return int(self.start_stamps.size)
 
+    def _blocks(self, idx):
+        """slices of ``idx`` whose texts add up to BATCH_CHARS at most (a longer contig is a block of its own)"""
+        ends = np.cumsum(self.lengths[idx], dtype=np.int64)
+        at = 0
+        while at < idx.size:
+            base = int(ends[at - 1]) if at else 0
+            stop = max(int(np.searchsorted(ends, base + BATCH_CHARS, side="right")), at + 1)
+            yield idx[at:stop]
+            at = stop
+
     def texts(self, indices):
-        return self._t.contig_texts(indices)
+        idx = np.asarray(list(indices), dtype=np.int64).reshape(-1)
+        out = []
+        for block in self._blocks(idx):
+            out += self._t.contig_texts(block)
+        return out
+
+    def packed(self):
+        """-> (uint8 characters, uint64 offsets[len + 1]) of all contigs in index order, as ``LazyContigs.packed`` gives
+        them: one batched export per block, no ``str`` per contig."""
+        chars = [self._t.contig_texts_packed(block)[1] for block in self._blocks(np.arange(len(self)))]
+        off = np.zeros(len(self) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(self.lengths, dtype=np.uint64)
+        return (np.concatenate(chars) if chars else np.empty(0, dtype=np.uint8)), off
+
+    def __iter__(self):
+        for block in self._blocks(np.arange(len(self))):
+            yield from self._t.contig_texts(block)
 
     def __getitem__(self, i):
         if isinstance(i, slice):
@@ -540,6 +584,12 @@ class PartContigs:
         if not 0 <= i < len(self):
             raise IndexError(i)
         return self.texts([i])[0]
+
+    def write_fasta(self, path, k, append=True):
+        """The driver's output (II_assembleFromReads.py:64-69): every contig as ``>SEQUENCE_{i}_{k}mer``, sorted by score
+        descending and stable like ``sequences.sort(key=getScore, reverse=True)``, written to ``path`` (rank 0 writes; a
+        list of the caller's goes through ``PartTraversal.write_contigs_fasta``).  -> bytes written."""
+        return self._t.write_contigs_fasta(path, None, k_label=k, append=append)
 
 
 def construct_graph(g, k, threshold=3, dist=None):
