@@ -403,12 +403,14 @@ int dbg_export_contig_index(dbg_t *h, uint64_t *offsets, uint64_t *scores, uint6
  * sorted by score descending and stable like `sequences.sort(key=getScore, reverse=True)`, as the text the driver
  * writes: ">SEQUENCE_{i}_{k}mer\n{contig}\n" per contig.  *bytes receives the size of the text (call with buf == NULL to
  * ask for it); order_out (may be NULL): [n_contigs] index of the contig at every output position, indices as in
- * dbg_export_contigs. */
+ * dbg_export_contigs.  The same bytes as dbg_write_contigs_fasta with indices NULL writes, but the whole text is held on
+ * the device for the one copy; dbg_contig_output_stats is not touched. */
 int dbg_export_sorted_fasta(dbg_t *h, uint32_t *order_out, char *buf, uint64_t buf_len, uint64_t *bytes);
 /* Text of ONE contig (buf_len >= its length from the index): what a caller uses when dbg_walk kept the index only
  * because the whole text exceeds max_chars (contigs overlap massively at scale).  The first call after a walk builds
- * the binary-lifting tables of the chain successors (n_nodes x ceil(log2 n_nodes) x 4 bytes), later calls are one
- * small kernel each. */
+ * the binary-lifting tables of the chain successors (n_nodes x ceil(log2(n_nodes + k)) x 4 bytes, shared with
+ * dbg_export_contig_texts and dbg_write_contigs_fasta; refused above 64 GiB), later calls are one small kernel each
+ * (one thread per character).  After a materialised walk the call is a copy out of the walk's text. */
 int dbg_export_contig_text(dbg_t *h, uint64_t index, char *buf, uint64_t buf_len);
 /* Contig text in bulk, after any walk that left an index: a materialised one, or an index-only one of the list-ranking
  * path (an index-only final-mode walk has no per-contig start nodes: DBG_E_ARG).  One kernel fills a window of the output

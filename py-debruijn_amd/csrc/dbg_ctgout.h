@@ -114,7 +114,7 @@ DBG_CO_HD inline uint64_t co_stage_bytes(uint64_t total, uint64_t chunk) {
 // ---- the virtual text ------------------------------------------------------------------------------------------------------
 struct CoText {
     const uint64_t *pos;    // [n] first byte of every record
-    const uint32_t *list;   // [n] contig of every record
+    const uint32_t *list;   // [n] contig of every record; null: record i is contig i
     const uint64_t *off;    // contig offsets of the walk (contig c has off[c + 1] - off[c] characters)
     uint64_t n, total;      // records, bytes
     uint64_t first_number;  // record i is numbered first_number + i
@@ -139,7 +139,7 @@ template <class Src>
 DBG_CO_HD inline void co_fill_run(const CoText &t, uint64_t rec, uint64_t b, Src &src, uint32_t w[4]) {
     w[0] = w[1] = w[2] = w[3] = 0;
     uint64_t rel = b - t.pos[rec];
-    uint32_t c = t.list[rec], nd = 0;
+    uint32_t c = t.list ? t.list[rec] : (uint32_t)rec, nd = 0;
     uint64_t len = t.off[c + 1] - t.off[c], number = t.first_number + rec, hdr = 0, rec_len = len;
     if (t.fasta) { nd = co_digits(number); hdr = co_header_len(nd, t.k_digits); rec_len = hdr + len + 1; }
     bool open = false;
@@ -151,7 +151,7 @@ DBG_CO_HD inline void co_fill_run(const CoText &t, uint64_t rec, uint64_t b, Src
         while (rel >= rec_len) {  // the next record (b + q < total: there is one)
             rel -= rec_len;
             ++rec;
-            c = t.list[rec];
+            c = t.list ? t.list[rec] : (uint32_t)rec;
             len = t.off[c + 1] - t.off[c];
             rec_len = len;
             if (t.fasta) { number = t.first_number + rec; nd = co_digits(number); hdr = co_header_len(nd, t.k_digits); rec_len = hdr + len + 1; }

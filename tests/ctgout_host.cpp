@@ -100,8 +100,10 @@ static void check_windows() {
 }
 
 // The kernel's work on the host: every window, every tile, every thread's run, compared with the text built record by record.
-static void check_fill(const std::vector<std::string> &texts, const std::vector<uint32_t> &list, bool fasta, uint64_t first_number,
-                       unsigned k, uint64_t chunk, const char *what) {
+// identity: the list goes to the emitter as a null pointer ("record i is contig i"; `list` must then say the same).
+// -> the text as the emitter spelled it
+static std::string check_fill(const std::vector<std::string> &texts, const std::vector<uint32_t> &list, bool fasta, uint64_t first_number,
+                              unsigned k, uint64_t chunk, const char *what, bool identity = false) {
     std::string want;
     std::vector<uint64_t> pos, off(1, 0);
     for (const std::string &t : texts) off.push_back(off.back() + t.size());
@@ -110,7 +112,7 @@ static void check_fill(const std::vector<std::string> &texts, const std::vector<
         want += fasta ? record(first_number + i, k, texts[list[i]]) : texts[list[i]];
     }
     CoText t;
-    t.pos = pos.data(); t.list = list.data(); t.off = off.data();
+    t.pos = pos.data(); t.list = identity ? nullptr : list.data(); t.off = off.data();
     t.n = list.size(); t.total = want.size(); t.first_number = first_number;
     t.k_label = k; t.k_digits = co_digits(k); t.fasta = fasta ? 1 : 0;
     for (size_t i = 0; i < list.size(); ++i)
@@ -144,6 +146,18 @@ static void check_fill(const std::vector<std::string> &texts, const std::vector<
         got.replace(w.b0, w.b1 - w.b0, staging.data(), w.b1 - w.b0);
     }
     EXPECT(got == want, "%s: text differs (%zu bytes)", what, want.size());
+    return got;
+}
+
+// every contig once, in order: the null list spells what the explicit list 0, 1, 2, ... does, bare and as FASTA
+static void check_identity(const std::vector<std::string> &texts, uint64_t first_number, unsigned k, uint64_t chunk, const char *what) {
+    std::vector<uint32_t> iota;
+    for (uint32_t i = 0; i < texts.size(); ++i) iota.push_back(i);
+    for (bool fasta : {false, true}) {
+        const std::string listed = check_fill(texts, iota, fasta, first_number, k, chunk, what);
+        const std::string bare = check_fill(texts, iota, fasta, first_number, k, chunk, what, true);
+        EXPECT(listed == bare && listed.size() > 0, "%s (%s): the null list differs from the list 0, 1, 2, ...", what, fasta ? "fasta" : "bare");
+    }
 }
 
 static std::string random_text(uint64_t len) {
@@ -169,11 +183,14 @@ static void check_fills() {
         check_fill(texts, {0}, false, 0, 11, chunk, "one character");
         check_fill(texts, {0}, true, 7, 11, chunk, "one short record");
         check_fill(texts, {17, 17}, true, 0, 63, chunk, "two long records");
+        check_identity(texts, 0, 11, chunk, "identity list");
+        check_identity(texts, 995, 12, chunk, "identity list from 995");
     }
     // every alignment of a border inside a record: a growing pad contig in front moves the records over the tile border
     for (uint64_t pad = 4000; pad < 4000 + 140; ++pad) {
         std::vector<std::string> tx = {random_text(pad), random_text(13), random_text(11)};
         check_fill(tx, {0, 1, 2, 1}, true, 8, 11, CO_TILE, "border sweep");
+        check_identity(tx, 8, 11, CO_TILE, "border sweep, identity list");
     }
     // many one-character contigs: hundreds of records inside one tile (bare) and tens (fasta)
     std::vector<std::string> tiny;
@@ -182,6 +199,8 @@ static void check_fills() {
     for (int i = 0; i < 10000; ++i) many.push_back((uint32_t)(rnd() % tiny.size()));
     check_fill(tiny, many, false, 0, 1, CO_TILE, "bare, one character each");
     check_fill(tiny, many, true, 0, 1, CO_TILE, "fasta, one character each");
+    for (int i = 0; i < 10000; ++i) tiny.push_back(random_text(1));  // more records than a tile has bytes
+    check_identity(tiny, 0, 1, CO_TILE, "one character each, identity list");
 }
 
 int main() {

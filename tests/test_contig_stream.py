@@ -1,6 +1,8 @@
 """Contig text streamed off the device: batched texts (dbg_export_contig_texts) and the FASTA writer
-(dbg_write_contigs_fasta) on materialised and index-only walks, against the same graph's materialised walk
-(export_contigs, export_sorted_fasta, host formatting of those texts), through the binding, debruijn.py and the driver.
+(dbg_write_contigs_fasta) on materialised and index-only walks, against the same graph's chain walk (one thread per start
+spells its contig: none of the code under test) and the host's formatting of those texts, through the binding,
+debruijn.py and the driver.  The materialised list-ranking walk and export_sorted_fasta, which spell their text with the
+same window kernel, and the one-contig call (one thread per character, the same descent) are held to the same reference.
 
 Input H: synth.reads_list(82, 10000, 8000, 60, 0.03), k = 11, threshold 1 -- 2 111 contigs of 11 .. 2 632 characters, so the
 record numbers cross 9 -> 10, 99 -> 100 and 999 -> 1000, records are shorter than a thread's run and contigs longer than
@@ -36,9 +38,32 @@ def _quiet(fn, *a, **kw):
         return fn(*a, **kw)
 
 
+def _chain_walk(g):
+    """The reference of this file: a materialised non-final walk in which one thread per start spells its chain character by
+    character (k_walk_chain) -- no lifting table, no window kernel, no record layout
+    -> (the text of every contig by index, scores, start stamps, emission indices inside the start)."""
+    g.set_option("walk_jump_min_nodes", 1 << 40)
+    try:
+        g.walk(False, 0)
+        assert g.sizes()["contigs_materialised"] == 1
+        off, chars, score, stamp, seq = g.export_contigs()
+    finally:
+        g.set_option("walk_jump_min_nodes", 1)
+    text, o = chars.tobytes(), off.tolist()
+    return [text[o[i]:o[i + 1]] for i in range(len(score))], score, stamp, seq
+
+
+def _driver_order(score, stamp, seq):
+    """Contig indices in the driver's order: the emission order (start stamp, index inside the start), sorted by score,
+    descending and stable."""
+    emission = np.lexsort((seq, stamp))
+    return emission[np.argsort(-score[emission].astype(np.int64), kind="stable")]
+
+
 class Walked:
-    """A graph, and what its materialised non-final walk gave: the text of every contig under (start stamp, emission index
-    inside the start) -- contig indices belong to one walk --, the emission order and the driver's sorted FASTA."""
+    """A graph, and what its chain walk (_chain_walk) gave: the text of every contig under (start stamp, emission index
+    inside the start) -- contig indices belong to one walk --, the texts in the driver's order and their FASTA as the host
+    formats it.  The materialised list-ranking walk and export_sorted_fasta are checked against those here, once."""
 
     def __init__(self, reads, k, thr):
         old = os.environ.get("DBG_WALK_JUMP_MIN")
@@ -51,15 +76,23 @@ class Walked:
             else:
                 os.environ["DBG_WALK_JUMP_MIN"] = old
         self.k, self.g = k, self.res[0][0]._graph
+        texts, score, stamp, seq = _chain_walk(self.g)
+        self.by_key = {(int(stamp[i]), int(seq[i])): texts[i] for i in range(len(score))}
+        self.n = len(score)
+        self.sorted_texts = [texts[i] for i in _driver_order(score, stamp, seq).tolist()]
+        self.fasta = _fasta(self.sorted_texts, 0, k)
+        self.lengths = np.array([len(t) for t in texts], dtype=np.int64)
+        # the materialised list-ranking walk spells the same contigs, and its sorted FASTA is the host's
         self.g.walk(False, 0)
         assert self.g.sizes()["contigs_materialised"] == 1
         off, chars, score, stamp, seq = self.g.export_contigs()
-        text = chars.tobytes()
-        self.by_key = {(int(stamp[i]), int(seq[i])): text[int(off[i]):int(off[i + 1])] for i in range(len(score))}
-        self.n = len(score)
-        self.fasta, order = self.g.export_sorted_fasta()
-        self.sorted_texts = [text[int(off[i]):int(off[i + 1])] for i in order.tolist()]
-        self.lengths = np.diff(off.astype(np.int64))
+        text, o = chars.tobytes(), off.tolist()
+        assert len(score) == self.n
+        for i in range(self.n):
+            assert text[o[i]:o[i + 1]] == self.by_key[(int(stamp[i]), int(seq[i]))], i
+        fasta, order = self.g.export_sorted_fasta()
+        assert fasta == self.fasta
+        assert order.tolist() == _driver_order(score, stamp, seq).tolist()
 
     def walk(self, materialised):
         """Walks again in the asked state -> (the texts by contig index of THIS walk, its emission order)."""
@@ -222,6 +255,32 @@ def test_writer_against_host_formatting(H, tmp_path):
     assert H.g.write_contigs_fasta(path, None, append=False, chunk_bytes=4096) == len(H.fasta)
     with open(path, "rb") as fh:
         assert fh.read() == H.fasta
+    # export_sorted_fasta spells its text the same way and leaves the stats of the last streaming call alone
+    st = H.g.contig_output_stats()
+    assert H.g.export_sorted_fasta()[0] == H.fasta
+    assert H.g.contig_output_stats() == st
+
+
+def _off_of_index_only_walk(w):
+    texts, _ = w.walk(False)
+    return texts, w.g.export_contig_index()[0].astype(np.int64)
+
+
+def test_one_contig_per_call_after_an_index_only_walk(H, I31):
+    """dbg_export_contig_text for every contig of H -- its first character at every offset inside a 16-byte run of the
+    walk's text, with and without a 4096-byte border inside it, so that the call may spell the contig as a piece of that
+    text as well as by itself -- and for the contigs of I31 that are longer than 4096 characters."""
+    texts, off = _off_of_index_only_walk(H)
+    first, last = off[:-1], off[1:] - 1
+    assert set((first % 16).tolist()) == set(range(16))
+    assert np.any(first // 4096 != last // 4096) and np.any(first // 16 == last // 16)
+    for i in range(H.n):
+        assert H.g.export_contig_text(i, len(texts[i])) == texts[i], i
+    texts, off = _off_of_index_only_walk(I31)
+    longer = np.flatnonzero(np.diff(off) > 4096).tolist()
+    assert longer
+    for i in longer:
+        assert I31.g.export_contig_text(i, len(texts[i])) == texts[i], i
 
 
 def test_memory_bound_and_stats(I31, tmp_path):
@@ -255,8 +314,8 @@ def test_memory_bound_where_the_sort_scratch_dominates(tmp_path):
     g.prune(2)
     g.remove_tips()
     g.mark_pull_reads()
-    g.walk(False, 0)
-    want, _ = g.export_sorted_fasta()
+    texts, score, stamp, seq = _chain_walk(g)
+    want = _fasta([texts[i] for i in _driver_order(score, stamp, seq).tolist()], 0, 31)
     g.walk(False, 16)
     sz = g.sizes()
     n, chunk = sz["n_contigs"], 4096
