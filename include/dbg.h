@@ -463,6 +463,47 @@ int dbg_part_export_contig_texts(dbg_t *h, const uint64_t *starts, uint64_t n, u
                                  uint64_t capacity, uint64_t *n_chars);
 int dbg_part_write_contigs_fasta(dbg_t *h, const char *path, int append, const uint64_t *starts, uint64_t n,
                                  uint64_t first_number, int k_label, uint64_t chunk_bytes, uint64_t *bytes_written);
+/* ---- final-mode walk (debruijn.py:288-316 with branch_kmer == [], the driver's last k) over a graph in parts
+ *      (csrc/dbg_partfinal.h).  The caller contracts the graph: one row per entry node of the ranked skeleton -- the
+ *      starts, the targets of chain edges that leave a part and every kept successor of a branch node -- and one row of a
+ *      branch table per branch node of the whole graph.  All pointers are device arrays:
+ *        d_kind    uint8[n_entries]   0 the chain ends at a node without kept successor (emitted, that node included)
+ *                                     1 the entry itself is pulled
+ *                                     2 the chain ends in front of a pulled node (emitted up to the node before it)
+ *                                     3 dead: the chain closes on itself or never resolved
+ *                                     4 the chain ends at the branch node of branch-table row d_branch[i]
+ *        d_append  uint64[n_entries]  nodes the chain appends after the entry (the skeleton's rest; kinds 0, 2, 4)
+ *        d_score   uint64[n_entries]  sum of the edge counts along them
+ *        d_branch  uint32[n_entries]  read where the kind is 4
+ *        d_succ_row / d_succ_count    uint32[n_branch * 4]: per branch node the entry rows of its KEPT successors in
+ *                                     Counter.most_common order (debruijn.py:159-165) and the counts of the edges to them;
+ *                                     DBG_NO_NODE: an empty slot
+ *        d_starts  uint32[n_starts]   entry rows of the nodes with indegree 0 in dict order
+ *      One kernel validates all of it first (kinds in range, branch rows below n_branch, successor rows below n_entries
+ *      or DBG_NO_NODE, starts below n_entries): DBG_E_ARG names what failed and no walk ran.  Then one walker per thread
+ *      enumerates every simple path of every start in two passes (count, scan, write).  A walker holds a stack of
+ *      n_branch + 1 levels of 24 bytes and n_branch bits -- only branch nodes need an on-path mark -- interleaved with the
+ *      other walkers'; their number follows dbg_walk's rule (4 GiB of stacks, 2^16 at most).  Every walker counts its
+ *      steps: above option "part_final_walk_steps" (dbg_set_option, default 2^24 per walker and pass -- a step measured 1.3 us, a refusal 22 s --, at least 1) the call
+ *      stops with DBG_E_CAPACITY, keeps nothing and the handle stays usable.  max_chars (0 = 1 GiB) is checked after the
+ *      counting pass like dbg_walk's: DBG_E_CAPACITY with valid sizes, nothing written.
+ *      *n_contigs, *n_pieces (rows over all contigs) and *n_chars (sum of the contig lengths) are always set.
+ *      n_starts == 0 or n_entries == 0: DBG_OK with zeros.  A handle without a graph in parts: DBG_E_ARG.  The result
+ *      belongs to the handle's current graph: the next build, the next final walk and dbg_destroy free it. */
+typedef struct dbg_final_skeleton {
+    uint64_t n_entries, n_branch, n_starts;
+    const void *d_kind, *d_append, *d_score, *d_branch, *d_succ_row, *d_succ_count, *d_starts;
+} dbg_final_skeleton_t;
+int dbg_part_final_walk(dbg_t *h, const dbg_final_skeleton_t *s, uint64_t max_chars, uint64_t *n_contigs, uint64_t *n_pieces,
+                        uint64_t *n_chars);
+/* The index of the last final walk to caller-owned host arrays (NULL pointers are skipped): per contig the ordinal of its
+ * start in d_starts, its ordinal within that start (contigs come grouped by start, in DFS order), its length
+ * k + nodes - 1 and its score (the sum of the edge counts along the path); piece_off[n_contigs + 1] into
+ * piece_row[n_pieces], the entry rows the path is made of.  The text of a contig is the text of its first piece followed
+ * by every later piece's text without its first k - 1 characters.  DBG_E_ARG without a walk, or after one that kept its
+ * sizes only. */
+int dbg_part_final_export(dbg_t *h, uint32_t *start_ordinal, uint32_t *seq, uint64_t *length, uint64_t *score,
+                          uint64_t *piece_off, uint32_t *piece_row);
 /* device-side views for callers that stay on the GPU (valid until the next build/destroy) */
 int dbg_device_views(dbg_t *h, const void **d_keys, const void **d_counts, const void **d_stamps,
                      const void **d_flags, const void **d_succ);

@@ -41,7 +41,14 @@ SYMBOLS = (
     "dbg_part_lookup_nodes", "dbg_part_lookup_nodes_device", "dbg_part_score_sequences",
     "dbg_export_contig_texts", "dbg_write_contigs_fasta", "dbg_contig_output_stats",
     "dbg_part_set_skeleton", "dbg_part_contig_window", "dbg_part_export_contig_texts", "dbg_part_write_contigs_fasta",
+    "dbg_part_final_walk", "dbg_part_final_export",
 )
+
+
+class FinalSkeleton(C.Structure):
+    """dbg_final_skeleton_t: the contracted graph of dbg_part_final_walk (device pointers)"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_entries", "n_branch", "n_starts")] + [
+        (n, C.c_void_p) for n in ("d_kind", "d_append", "d_score", "d_branch", "d_succ_row", "d_succ_count", "d_starts")]
 
 
 class Sizes(C.Structure):
@@ -219,6 +226,8 @@ def load_library():
         "dbg_part_contig_window": (C.c_int, [H, vp, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, vp, u64p]),
         "dbg_part_export_contig_texts": (C.c_int, [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]),
         "dbg_part_write_contigs_fasta": (C.c_int, [H, C.c_char_p, C.c_int, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, u64p]),
+        "dbg_part_final_walk": (C.c_int, [H, C.POINTER(FinalSkeleton), C.c_uint64, u64p, u64p, u64p]),
+        "dbg_part_final_export": (C.c_int, [H, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -928,6 +937,36 @@ class Graph:
         self._chk(self._lib.dbg_part_write_contigs_fasta(self._h, os.fsencode(path), 1 if append else 0, _ptr(idx) if idx.size else None,
                                                          idx.size, int(first_number), int(k_label), int(chunk_bytes), C.byref(n)))
         return int(n.value)
+
+    def part_final_walk(self, kind, append, score, branch, succ_row, succ_count, starts, max_chars=0):
+        """The final-mode walk over the contracted graph of a graph in parts (include/dbg.h: dbg_part_final_walk).  Device
+        tensors: kind uint8[n], append / score int64[n], branch int32[n], succ_row / succ_count int32[n_branch * 4] (the
+        uint32 values; -1 = DBG_NO_NODE), starts int32[n_starts].  -> dict(n_contigs, n_pieces, n_chars, start_ordinal, seq,
+        length, score, piece_off, piece_row) with numpy arrays.  A text above max_chars raises DbgError (DBG_E_CAPACITY)
+        whose ``sizes`` attribute holds the three counts."""
+        import torch
+        n, nb, ns = kind.numel(), succ_row.numel() // 4, starts.numel()
+        for c, size, count, what in ((kind, 1, n, "kind"), (append, 8, n, "append"), (score, 8, n, "score"), (branch, 4, n, "branch"),
+                                     (succ_row, 4, nb * 4, "succ_row"), (succ_count, 4, nb * 4, "succ_count"), (starts, 4, ns, "starts")):
+            if c.numel() != count or c.element_size() != size or not c.is_contiguous() or c.dtype.is_floating_point:
+                raise ValueError(f"part_final_walk: {what} must be a contiguous integer column of {count} elements of {size} bytes")
+        sk = FinalSkeleton(n, nb, ns, *[c.data_ptr() if c.numel() else None for c in (kind, append, score, branch, succ_row, succ_count, starts)])
+        nc, npc, nch = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        torch.cuda.synchronize(self._dev())  # the library reads the columns on its own stream
+        rc = self._lib.dbg_part_final_walk(self._h, C.byref(sk), int(max_chars), C.byref(nc), C.byref(npc), C.byref(nch))
+        if rc != DBG_OK:
+            try:
+                self._chk(rc)
+            except DbgError as e:
+                e.sizes = {"n_contigs": nc.value, "n_pieces": npc.value, "n_chars": nch.value}
+                raise
+        out = {"n_contigs": nc.value, "n_pieces": npc.value, "n_chars": nch.value,
+               "start_ordinal": np.empty(nc.value, dtype=np.uint32), "seq": np.empty(nc.value, dtype=np.uint32),
+               "length": np.empty(nc.value, dtype=np.uint64), "score": np.empty(nc.value, dtype=np.uint64),
+               "piece_off": np.zeros(nc.value + 1, dtype=np.uint64), "piece_row": np.empty(npc.value, dtype=np.uint32)}
+        self._chk(self._lib.dbg_part_final_export(self._h, *[_ptr(out[c]) if out[c].size else None
+                                                             for c in ("start_ordinal", "seq", "length", "score", "piece_off", "piece_row")]))
+        return out
 
     def scan_reads_for_keys(self, k, keys, keys_hi=None, first_seen=True):
         """-> (read_flags uint8[n_reads], first_seen uint64[n_keys, 4] or None); numpy in and out (dbg_scan_reads_for_keys)."""

@@ -48,12 +48,15 @@ def rank_skeleton(e, k, keep=False):
     does a start that is itself pulled.  -> (dict(stamp, length, score) numpy in dict order of the starts, skeleton or None).
     The skeleton (``keep``) stays where ``e`` lives: the columns sorted by gid -- gid, next (row index), go_on, hops -- and
     rest, the characters the chain appends from the entry's segment to its end: hops + go_on * (1 + rest[next]), -1 (the
-    library's UINT64_MAX) where the chain is dead or never resolved; emit (numpy): the row of contig i's start."""
+    library's UINT64_MAX) where the chain is dead or never resolved; emit (numpy): the row of contig i's start.  For the
+    final-mode walk it also carries, per row: terminal (the row the chain ends in, valid where rest is), chain_score (the
+    edge counts along the chain), and the sorted input columns kind, exit, stamp and start."""
     n = e["gid"].numel()
     if n == 0:
         z = np.empty(0, dtype=np.int64)
         zt = e["gid"].reshape(-1)
-        sk = {"gid": zt, "next": zt, "go_on": zt.to(torch.bool), "hops": zt, "rest": zt, "emit": z} if keep else None
+        sk = {"gid": zt, "next": zt, "go_on": zt.to(torch.bool), "hops": zt, "rest": zt, "emit": z, "terminal": zt, "chain_score": zt,
+              "kind": zt, "exit": zt, "stamp": zt, "start": zt} if keep else None
         return {"stamp": z.astype(np.uint64), "length": z, "score": z}, sk
     o = torch.argsort(e["gid"])
     e = {c: t[o] for c, t in e.items()}
@@ -84,6 +87,7 @@ def rank_skeleton(e, k, keep=False):
     if keep:
         sk["rest"] = torch.where(done & ~dead, hops, torch.full_like(hops, -1))   # the jumping left the chain's sum in hops
         sk["emit"] = em.cpu().numpy()                # skeleton index of contig i's start
+        sk.update(terminal=jump, chain_score=score, kind=e["kind"], exit=e["exit"], stamp=e["stamp"], start=e["start"])
     return {"stamp": e["stamp"][em].cpu().numpy().astype(np.uint64), "length": (hops[em] + k).cpu().numpy(),
             "score": score[em].cpu().numpy()}, sk
 
@@ -180,6 +184,8 @@ class PartTraversal:
         self.rank, self.world = self.net.rank, self.net.world
         self.nv = self.world * self.P
         self.n_nodes = [g.part_sizes(p)["n_nodes"] for p in range(self.P)]
+        self.final_mode = False   # construct_graph(final=True): output_contigs walks every simple path
+        self.final = None         # the pieces of the last walk_final (None: the last walk was a non-final one)
 
     # ---- helpers
     def _v(self, p):
@@ -414,6 +420,13 @@ class PartTraversal:
         nothing (debruijn.py:289-290), nor does a start that was pulled.  keep_skeleton: hand the ranked skeleton to the
         library (dbg_part_set_skeleton: it stays on the device, with its lifting table) so that ``contig_texts`` and
         ``write_contigs_fasta`` can spell contigs afterwards; the host keeps 16 bytes per CONTIG (start row, length)."""
+        self.final = None
+        index, _ = self._ranked_skeleton(keep_skeleton)
+        return index
+
+    def _ranked_skeleton(self, keep_skeleton, extra_entries=None):
+        """walk_index's work: entries, one segment each, ranking.  extra_entries: global ids (this rank's own among them are
+        used) that are entries besides the starts and the cross-part targets.  -> (index, skeleton or None)"""
         g, P, dev = self.g, self.P, self.device
         # entries: the starts (indegree 0) and every node a chain of another part continues at
         sends = []
@@ -425,6 +438,10 @@ class PartTraversal:
                 owner = torch.repeat_interleave(torch.arange(self.nv, device=dev), torch.tensor(counts, device=dev))
                 sends.append((owner << 32) | _u32(targets))
         got = self._to_parts(torch.cat(sends) if sends else torch.empty(0, dtype=torch.int64, device=dev))
+        if extra_entries is not None:
+            v = extra_entries >> 32
+            for p in range(P):
+                got[p] = torch.cat([got[p], (extra_entries[v == self._v(p)] & 0xFFFFFFFF).to(torch.int32)])
         segs = []
         for p in range(P):
             if not self.n_nodes[p]:
@@ -448,7 +465,181 @@ class PartTraversal:
         if keep_skeleton:
             g.part_set_skeleton(skeleton["gid"], skeleton["next"], skeleton["go_on"], skeleton["hops"], skeleton["rest"])
             self.skeleton = {"emit": skeleton["emit"].astype(np.int64), "length": index["length"], "score": index["score"]}
+        return index, skeleton
+
+    # ---- a11 + a12 + a13, final mode (the driver's last k: branch_kmer == [], debruijn.py:281-283)
+    def walk_final(self, max_chars=0):
+        """output_contigs with an empty branch list: every simple path from every start (debruijn.py:288-316), stopped only by
+        dead ends and pulled nodes -- dict(stamp uint64, seq uint32, length int64, score int64) in the reference's order (the
+        starts in dict order, DFS order within a start).  The kept successors of all branch nodes become entries besides
+        those of ``walk_index``; the ranked skeleton then names, for every entry, the end of its chain, and the library walks
+        the contracted graph of entries and branch nodes (include/dbg.h: dbg_part_final_walk).  Every rank holds the same
+        contracted graph and runs the same walk.  Without a branch node in the whole graph this is the non-final index.
+        max_chars: refuse (DbgError, DBG_E_CAPACITY) contig text beyond it, 0 = 1 GiB."""
+        b = getattr(self, "branch", None)
+        if b is None:
+            raise _dbg.DbgError(_dbg.DBG_E_ARG, "part_traversal: prune() must run before walk_final()")
+        dev, nb = self.device, int(b["gid"].size)
+        if nb == 0:
+            index = self.walk_index(keep_skeleton=True)
+            index["seq"] = np.zeros(index["stamp"].size, dtype=np.uint32)
+            return index
+        if getattr(self, "first_seen", None) is None:
+            raise _dbg.DbgError(_dbg.DBG_E_ARG, "part_traversal: pull_out_reads() must run before walk_final() (it ranks the successors of the branch nodes)")
+        # the branch table in Counter order, kept edges only: (successor gid, edge count) per rank
+        keep = ((b["pflags"].astype(np.int64)[:, None] >> (F_KEEP_SHIFT + np.arange(4))[None, :]) & 1) == 1
+        counts = np.where(keep, b["counts"].astype(np.int64), 0)
+        order = self._order_bytes(counts, self.first_seen)
+        code = (order[:, None].astype(np.int64) >> (2 * np.arange(4))[None, :]) & 3      # code at rank r
+        kept_r = np.take_along_axis(keep, code, axis=1)
+        succ_r = np.where(kept_r, np.take_along_axis(b["succ"].astype(np.int64), code, axis=1), -1)
+        cnt_r = np.where(kept_r, np.take_along_axis(counts, code, axis=1), 0)
+        if bool((kept_r & (succ_r < 0)).any()):
+            raise RuntimeError("walk_final: a kept edge of a branch node has no successor node")
+        slot = np.argsort(~kept_r, axis=1, kind="stable")                                # kept ranks first, in rank order
+        succ_r, cnt_r = np.take_along_axis(succ_r, slot, axis=1), np.take_along_axis(cnt_r, slot, axis=1)
+        d_succ = torch.from_numpy(succ_r.reshape(-1)).to(dev)
+        self.final = None
+        _, sk = self._ranked_skeleton(True, extra_entries=torch.unique(d_succ[d_succ >= 0]))
+        n = sk["gid"].numel()
+        gid, term, kind = sk["gid"], sk["terminal"], sk["kind"]
+        live = sk["rest"] >= 0
+        tk = kind[term]
+        # the node a live chain ends at, joined with the branch list
+        end_gid = (gid[term] & ~0xFFFFFFFF) | sk["exit"][term]
+        bo = np.argsort(b["gid"], kind="stable")
+        b_sorted = torch.from_numpy(b["gid"][bo].astype(np.int64)).to(dev)
+        at = torch.searchsorted(b_sorted, end_gid).clamp_(max=nb - 1)
+        at_branch = live & (tk == K_EMIT) & (b_sorted[at] == end_gid)
+        out_kind = torch.full((n,), 3, dtype=torch.uint8, device=dev)                    # dead, unless:
+        out_kind[live & (tk == K_EMIT)] = 0
+        out_kind[live & ((tk == K_NEXT_PULLED) | (tk == K_REMOTE))] = 2
+        out_kind[at_branch] = 4
+        out_kind[kind == K_PULLED] = 1
+        stray = live & (kind != K_PULLED) & ((tk == K_PULLED) | (tk == K_CYCLE))
+        row = torch.searchsorted(gid, torch.where(d_succ >= 0, d_succ, torch.zeros_like(d_succ))).clamp_(max=max(n - 1, 0))
+        lost = (d_succ >= 0) & (gid[row] != d_succ) if n else (d_succ >= 0)
+        bad = torch.stack([stray.any(), lost.any()]).cpu().tolist()                      # one host sync for both checks
+        if bad[0]:
+            raise RuntimeError("walk_final: a resolved chain ends in a pulled entry or a cycle")
+        if bad[1]:
+            raise RuntimeError("walk_final: a kept successor of a branch node is no entry of the skeleton")
+        out_branch = torch.zeros(n, dtype=torch.int32, device=dev)
+        out_branch[at_branch] = torch.from_numpy(bo.astype(np.int32)).to(dev)[at[at_branch]]
+        zero = torch.zeros_like(sk["rest"])
+        st = torch.nonzero(sk["start"] == 1).reshape(-1)
+        st = st[torch.argsort(sk["stamp"][st])]                                          # dict order of the starts
+        res = self.g.part_final_walk(out_kind, torch.where(live, sk["rest"], zero).contiguous(),
+                                     torch.where(live, sk["chain_score"], zero).contiguous(), out_branch,
+                                     torch.where(d_succ >= 0, row, torch.full_like(row, -1)).to(torch.int32).contiguous(),
+                                     torch.from_numpy(cnt_r.reshape(-1)).to(dev).to(torch.int32).contiguous(),
+                                     st.to(torch.int32).contiguous(), max_chars=max_chars)
+        stamps = sk["stamp"][st].cpu().numpy().astype(np.uint64)
+        index = {"stamp": stamps[res["start_ordinal"]], "seq": res["seq"], "length": res["length"].astype(np.int64),
+                 "score": res["score"].astype(np.int64)}
+        # pieces: the skeleton rows a contig is stitched from (the library holds the skeleton: _ranked_skeleton set it)
+        self.final = {"piece_off": res["piece_off"].astype(np.int64), "piece_row": res["piece_row"].astype(np.int64),
+                      "length": index["length"], "score": index["score"], "rest": sk["rest"]}
         return index
+
+    STITCH_CHARS = 32 << 20   # contig characters of one stitch: its gather index is 8 bytes a character
+
+    def _rows_texts_packed(self, rows):
+        """-> (offsets int64[n + 1], chars uint8): the texts of the chains that start at the skeleton rows ``rows`` (numpy
+        int64; k + rest characters each), concatenated.  Collective like ``contig_texts_packed``."""
+        if self.world == 1:
+            off, chars = self.g.part_export_contig_texts(rows)
+            return off.astype(np.int64), chars
+        rest = self.final["rest"][torch.from_numpy(rows).to(self.device)].cpu().numpy()
+        off = np.zeros(rows.size + 1, dtype=np.int64)
+        off[1:] = np.cumsum(rest + self.k)
+        chars = np.empty(int(off[-1]), dtype=np.uint8)
+        if rows.size:
+            at = [0]
+
+            def sink(w):
+                chars[at[0]:at[0] + w.size] = w
+                at[0] += w.size
+            total = self._windows(rows, False, 0, 0, self.WINDOW_BYTES, sink)
+            if total != chars.size or at[0] != total:
+                raise RuntimeError(f"contig_texts: the library lays out {total} characters, the skeleton {chars.size}")
+        return off, chars
+
+    def _final_which(self, which):
+        f = self.final
+        n = f["length"].size
+        if which is None:
+            which = np.argsort(-f["score"], kind="stable")
+        which = np.asarray(list(which) if not isinstance(which, np.ndarray) else which, dtype=np.int64).reshape(-1)
+        if which.size and (int(which.min()) < -n or int(which.max()) >= n):
+            raise IndexError(f"contig index out of range (the walk has {n} contigs)")
+        return np.where(which < 0, which + n, which)
+
+    def _final_blocks(self, which):
+        """slices of ``which`` of at most min(BATCH_CHARS, STITCH_CHARS) characters (a longer contig is a block of its own)"""
+        ends = np.cumsum(self.final["length"][which], dtype=np.int64)
+        limit, at = min(BATCH_CHARS, self.STITCH_CHARS), 0
+        while at < which.size:
+            base = int(ends[at - 1]) if at else 0
+            stop = max(int(np.searchsorted(ends, base + limit, side="right")), at + 1)
+            yield which[at:stop]
+            at = stop
+
+    def _final_stitch(self, which):
+        """The texts of the final contigs ``which`` (one block): the first piece's text, then every later piece's without its
+        first k - 1 characters (a branch node's successor overlaps it by k - 1).  The distinct pieces are spelled once by
+        the window path; the stitch is one gather over their packed characters.  -> (offsets int64[n + 1], chars uint8)"""
+        f, k = self.final, self.k
+        p0, p1 = f["piece_off"][which], f["piece_off"][which + 1]
+        n_p = p1 - p0
+        first = np.zeros(which.size + 1, dtype=np.int64)
+        first[1:] = np.cumsum(n_p)
+        pieces = f["piece_row"][np.repeat(p0 - first[:-1], n_p) + np.arange(int(first[-1]))]
+        rows, inv = np.unique(pieces, return_inverse=True)
+        r_off, r_chars = self._rows_texts_packed(rows)
+        skip = np.full(pieces.size, k - 1, dtype=np.int64)
+        skip[first[:-1]] = 0
+        src = r_off[inv] + skip
+        length = r_off[inv + 1] - src
+        dst = np.zeros(pieces.size + 1, dtype=np.int64)
+        dst[1:] = np.cumsum(length)
+        off = dst[first]
+        if not np.array_equal(off[1:] - off[:-1], f["length"][which]):
+            raise RuntimeError("walk_final: the pieces of a contig do not add up to its length")
+        chars = r_chars[np.repeat(src - dst[:-1], length) + np.arange(int(dst[-1]))]
+        return off, chars
+
+    def _final_texts_packed(self, which):
+        which = self._final_which(which)
+        offs, chars, base = [np.zeros(1, dtype=np.int64)], [], 0
+        for block in self._final_blocks(which):
+            o, c = self._final_stitch(block)
+            offs.append(o[1:] + base)
+            chars.append(c)
+            base += int(o[-1])
+        return np.concatenate(offs).astype(np.uint64), (np.concatenate(chars) if chars else np.empty(0, dtype=np.uint8))
+
+    def _final_write_fasta(self, path, which, first_number, k_label, append):
+        which = self._final_which(which)
+        if not which.size:
+            return 0
+        f = open(path, "ab" if append else "wb") if self.rank == 0 else None
+        written, number = 0, int(first_number)
+        try:
+            for block in self._final_blocks(which):
+                o, c = self._final_stitch(block)
+                rec = []
+                for i in range(block.size):
+                    rec += [b">SEQUENCE_%d_%dmer\n" % (number + i, k_label or self.k), c[o[i]:o[i + 1]].tobytes(), b"\n"]
+                number += block.size
+                data = b"".join(rec)
+                written += len(data)
+                if f:
+                    f.write(data)
+        finally:
+            if f:
+                f.close()
+        return written
 
     # ---- contig text (include/dbg.h: dbg_part_export_contig_texts, dbg_part_write_contigs_fasta, dbg_part_contig_window)
     WINDOW_BYTES = 4 << 20   # window of the several-rank path where the caller names none (the library's default)
@@ -484,6 +675,8 @@ class PartTraversal:
     def contig_texts_packed(self, which):
         """-> (offsets uint64[n + 1], chars uint8): the texts of the contigs ``which`` (positions in the index, any order,
         repeats allowed), concatenated.  Collective: every rank calls it with the same list and gets the same bytes."""
+        if self.final is not None:
+            return self._final_texts_packed(which)
         which, starts = self._starts(which)
         if self.world == 1:
             return self.g.part_export_contig_texts(starts)
@@ -505,6 +698,8 @@ class PartTraversal:
         """``>SEQUENCE_{first_number + i}_{k_label}mer\\n{contig}\\n`` (II_assembleFromReads.py:64-69) for the contigs ``which``
         (None: all of them in the driver's order) to ``path``; k_label 0: this k.  Collective; rank 0 alone opens and
         writes the file, every rank returns the bytes written.  chunk_bytes: window size, a multiple of 4096 (0: default)."""
+        if self.final is not None:   # stitched on the host: chunk_bytes sizes no window here
+            return self._final_write_fasta(path, which, first_number, k_label, append)
         which, starts = self._starts(which)
         if chunk_bytes % 4096:
             raise _dbg.DbgError(_dbg.DBG_E_ARG, f"write_contigs_fasta: chunk_bytes {chunk_bytes} is no multiple of 4096")
@@ -592,31 +787,39 @@ class PartContigs:
         return self._t.write_contigs_fasta(path, None, k_label=k, append=append)
 
 
-def construct_graph(g, k, threshold=3, dist=None):
+def construct_graph(g, k, threshold=3, dist=None, final=False):
     """construct_graph (debruijn.py:206-285) after a build in parts (``g.build_multipass`` or, with ``dist``,
     ``multi_gpu.sharded_build_multipass``), every rank calling it: -> (traversal, pull_out_read_flags, branch_kmer,
     already_pull_out) with the reference's lists as str (dict order / append order; the same on every rank) and the
-    pull-out reads as uint8 flags over THIS rank's reads (the reference's list is the flagged reads of rank 0, 1, ... in order)."""
+    pull-out reads as uint8 flags over THIS rank's reads (the reference's list is the flagged reads of rank 0, 1, ... in order).
+    final (the driver's last k): no pull-out reads and an empty branch list (debruijn.py:281-283); ``output_contigs`` then
+    walks every simple path."""
     t = PartTraversal(g, k, dist)
+    t.final_mode = bool(final)
     b = t.prune(threshold)
     flags = t.pull_out_reads()
     p = t.remove_tips()
+    if final:
+        return t, np.zeros_like(flags), [], _dbg.decode_keys(p["keys"], t.k, keys_hi=p["keys_hi"])
     branch_kmer = _dbg.decode_keys(b["keys"].astype(np.uint64), t.k, keys_hi=b["keys_hi"].astype(np.uint64))
     already_pull_out = _dbg.decode_keys(p["keys"], t.k, keys_hi=p["keys_hi"])
     return t, flags, branch_kmer, already_pull_out
 
 
 def output_contigs(traversal):
-    """output_contigs (debruijn.py:326-347) for the branch list ``construct_graph`` above found (the non-final walk)."""
+    """output_contigs (debruijn.py:326-347) for the branch list ``construct_graph`` above returned: the non-final walk, or,
+    after ``construct_graph(final=True)``, every simple path (``walk_final``).  max_chars of the final walk: the default."""
+    if traversal.final_mode:
+        return PartContigs(traversal, traversal.walk_final())
     return PartContigs(traversal, traversal.walk_index(keep_skeleton=True))
 
 
-def traverse(g, k, threshold, dist=None):
-    """prune -> pull-out reads -> tips -> non-final walk over the graph in parts on ``g`` (every rank calls it).
-    -> dict(branch, pulled, read_flags, contigs)."""
+def traverse(g, k, threshold, dist=None, final=False):
+    """prune -> pull-out reads -> tips -> walk (final: every simple path, else the non-final one) over the graph in parts on
+    ``g`` (every rank calls it).  -> dict(branch, pulled, read_flags, contigs)."""
     t = PartTraversal(g, k, dist)
     branch = t.prune(threshold)
     flags = t.pull_out_reads()
     pulled = t.remove_tips()
-    contigs = t.walk_index()
+    contigs = t.walk_final() if final else t.walk_index()
     return {"branch": branch, "pulled": pulled, "read_flags": flags, "contigs": contigs, "tip_rounds": getattr(t, "tip_rounds", 0)}
