@@ -483,8 +483,9 @@ int dbg_part_write_contigs_fasta(dbg_t *h, const char *path, int append, const u
  *      or DBG_NO_NODE, starts below n_entries): DBG_E_ARG names what failed and no walk ran.  Then one walker per thread
  *      enumerates every simple path of every start in two passes (count, scan, write).  A walker holds a stack of
  *      n_branch + 1 levels of 24 bytes and n_branch bits -- only branch nodes need an on-path mark -- interleaved with the
- *      other walkers'; their number follows dbg_walk's rule (4 GiB of stacks, 2^16 at most).  Every walker counts its
- *      steps: above option "part_final_walk_steps" (dbg_set_option, default 2^24 per walker and pass -- a step measured 1.3 us, a refusal 22 s --, at least 1) the call
+ *      other walkers'; their number follows dbg_walk's rule (4 GiB of stacks, 2^16 at most), and walker w takes the
+ *      starts w, w + walkers, ...  Every walker counts its steps over all its starts -- a step is one trip of its loop: one
+ *      successor slot tried (used or empty) or one level popped, so 5 for every branch level it pushes --: above option "part_final_walk_steps" (dbg_set_option, default 2^24 per walker and pass -- a step measured 1.3 us, a refusal 22 s --, at least 1) the call
  *      stops with DBG_E_CAPACITY, keeps nothing and the handle stays usable.  max_chars (0 = 1 GiB) is checked after the
  *      counting pass like dbg_walk's: DBG_E_CAPACITY with valid sizes, nothing written.
  *      *n_contigs, *n_pieces (rows over all contigs) and *n_chars (sum of the contig lengths) are always set.

@@ -1,6 +1,7 @@
 // Host check of csrc/dbg_partfinal.h (tests/test_partfinal_host.py builds and runs it): the final-mode walker over the
 // contracted graph against a recursive node-by-node DFS written from debruijn.py:288-316 (branch_kmer == []), on hand-made
-// and random node-level graphs cut into parts; the validation predicate against each kind of broken row; the step budget.
+// and random node-level graphs cut into parts, walked with stride 1 and by three interleaved walkers at stride 3; the
+// validation predicate against each kind of broken row; the step budget.
 #include "dbg_partfinal.h"
 
 #include <algorithm>
@@ -181,20 +182,46 @@ struct Walked {
     std::vector<Contig> contigs;
     uint64_t n_pieces = 0, n_chars = 0, steps = 0;
 };
-static Walked walk(const Toy &t, const Contracted &c, uint64_t budget) {
+// With stride S, S walkers share one lv / bm allocation, interleaved as k_fw_walk lays them out (level d of walker v at
+// lv[d * S + v], word q at bm[q * S + v]), and start i goes to walker i % S with that walker's own budget.  Before every
+// start the other walkers' levels and words are filled with a pattern; the walker must leave them as they were.
+static const uint32_t PAT = 0xA5A5A5A5u;
+static const FwLevel PAT_LEVEL{PAT, PAT, 0xA5A5A5A5A5A5A5A5ull, 0xA5A5A5A5A5A5A5A5ull};
+struct Shared {
+    uint64_t stride;
+    std::vector<FwLevel> lv;
+    std::vector<uint32_t> bm;
+    Shared(const FwGraph &g, uint64_t s) : stride(s), lv((g.n_branch + 1) * s), bm(((g.n_branch + 31) / 32 + 1) * s, 0) {}
+    void arm(uint64_t v) {
+        std::fill(lv.begin(), lv.end(), PAT_LEVEL);
+        for (size_t q = 0; q < bm.size(); ++q) bm[q] = q % stride == v ? 0u : PAT;
+    }
+    void verify(uint64_t v, uint64_t i) const {
+        for (size_t q = 0; q < lv.size(); ++q)
+            if (q % stride != v)
+                EXPECT(lv[q].row == PAT && lv[q].state == PAT && lv[q].nodes == PAT_LEVEL.nodes && lv[q].score == PAT_LEVEL.score,
+                       "start %" PRIu64 " (walker %" PRIu64 " of %" PRIu64 ") wrote level slot %zu of a neighbour", i, v, stride, q);
+        for (size_t q = 0; q < bm.size(); ++q) {
+            if (q % stride == v) EXPECT(bm[q] == 0, "the bitmap is dirty after start %" PRIu64, i);
+            else EXPECT(bm[q] == PAT, "start %" PRIu64 " (walker %" PRIu64 " of %" PRIu64 ") wrote bitmap word %zu of a neighbour", i, v, stride, q);
+        }
+    }
+};
+static Walked walk(const Toy &t, const Contracted &c, uint64_t budget, uint64_t stride = 1) {
     Walked w;
     const FwGraph g = c.view();
-    std::vector<FwLevel> lv(g.n_branch + 1);
-    std::vector<uint32_t> bm((g.n_branch + 31) / 32 + 1, 0);
+    Shared sh(g, stride);
     std::vector<FwCount> per(g.n_starts);
     FwOut none{};
-    uint64_t steps = budget;
+    std::vector<uint64_t> steps(stride, budget);
     for (uint64_t i = 0; i < g.n_starts; ++i) {
+        const uint64_t v = i % stride;
         per[i] = FwCount{0, 0, 0};
-        if (!fw_walk_start(g, t.k, i, lv.data(), bm.data(), 1, 0, 0, 0, none, per[i], steps)) { w.ok = false; return w; }
-        for (uint32_t word : bm) EXPECT(word == 0, "the bitmap is dirty after start %" PRIu64, i);
+        sh.arm(v);
+        if (!fw_walk_start(g, t.k, i, sh.lv.data() + v, sh.bm.data() + v, stride, 0, 0, 0, none, per[i], steps[v])) { w.ok = false; return w; }
+        sh.verify(v, i);
     }
-    w.steps = budget - steps;
+    for (uint64_t v = 0; v < stride; ++v) w.steps += budget - steps[v];
     uint64_t nc = 0, np = 0;
     std::vector<uint64_t> cb(g.n_starts), pb(g.n_starts);
     for (uint64_t i = 0; i < g.n_starts; ++i) { cb[i] = nc; pb[i] = np; nc += per[i].contigs; np += per[i].pieces; w.n_chars += per[i].chars; }
@@ -202,10 +229,13 @@ static Walked walk(const Toy &t, const Contracted &c, uint64_t budget) {
     std::vector<uint32_t> so(nc + 1, 0xDEADu), seq(nc + 1, 0xDEADu), prow(np + 1, 0xDEADu);
     std::vector<uint64_t> len(nc + 1, 0), sc(nc + 1, 0), poff(nc + 1, 0);
     FwOut o{so.data(), seq.data(), len.data(), sc.data(), poff.data(), prow.data(), nc, np};
-    steps = budget;
+    steps.assign(stride, budget);
     for (uint64_t i = 0; i < g.n_starts; ++i) {
+        const uint64_t v = i % stride;
         FwCount again{0, 0, 0};
-        const bool ok = fw_walk_start(g, t.k, i, lv.data(), bm.data(), 1, 1, cb[i], pb[i], o, again, steps);
+        sh.arm(v);
+        const bool ok = fw_walk_start(g, t.k, i, sh.lv.data() + v, sh.bm.data() + v, stride, 1, cb[i], pb[i], o, again, steps[v]);
+        sh.verify(v, i);
         EXPECT(ok && again.contigs == per[i].contigs && again.pieces == per[i].pieces && again.chars == per[i].chars, "pass 1 differs from pass 0 at start %" PRIu64, i);
     }
     EXPECT(so[nc] == 0xDEADu && prow[np] == 0xDEADu, "pass 1 wrote behind its arrays");
@@ -242,12 +272,12 @@ static std::string show(const std::vector<Contig> &v) {
     return s;
 }
 
-static Walked check(const Toy &t, const char *what) {
+static Walked check(const Toy &t, const char *what, uint64_t stride = 1) {
     const Contracted c = contract(t);
     const FwGraph g = c.view();
     const uint64_t n_check = std::max<uint64_t>(std::max<uint64_t>(g.n_entries, g.n_branch * FW_FAN), g.n_starts);
     for (uint64_t i = 0; i < n_check; ++i) EXPECT(fw_fault_at(g, i) == FW_OK, "%s: the contraction fails validation at %" PRIu64, what, i);
-    const Walked w = walk(t, c, 1ull << 40);
+    const Walked w = walk(t, c, 1ull << 40, stride);
     const std::vector<Contig> ref = reference(t);
     EXPECT(w.ok && w.contigs == ref, "%s: walker %s reference %s", what, show(w.contigs).c_str(), show(ref).c_str());
     return w;
@@ -307,7 +337,7 @@ static void required_cases() {
 }
 
 static void random_cases() {
-    uint64_t with_branch = 0, with_pulled_prefix = 0, n_contigs = 0;
+    uint64_t with_branch = 0, with_pulled_prefix = 0, n_contigs = 0, strided_starts = 0;
     for (int round = 0; round < 4000; ++round) {
         Toy t;
         t.k = 2 + (int)(rnd() % 40);
@@ -333,6 +363,9 @@ static void random_cases() {
         for (int x = 0; x < n; ++x)
             if (indeg[x] == 0 || rnd() % 10 == 0) t.starts.push_back(x);
         const Walked w = check(t, "random");
+        const Walked w3 = check(t, "random, three interleaved walkers", 3);
+        EXPECT(w3.contigs == w.contigs && w3.steps == w.steps && w3.n_pieces == w.n_pieces, "stride 3 differs from stride 1");
+        strided_starts += t.starts.size() > 3;
         with_branch += branches > 0;
         n_contigs += w.contigs.size();
         for (size_t q = 1; q < w.contigs.size(); ++q) {
@@ -343,6 +376,28 @@ static void random_cases() {
     std::printf("random: %" PRIu64 " contigs, %" PRIu64 " graphs with branch nodes, %" PRIu64 " prefixes emitted before their extensions\n",
                 n_contigs, with_branch, with_pulled_prefix);
     EXPECT(with_branch > 2000 && n_contigs > 4000, "the random graphs are too tame");
+    std::printf("random: %" PRIu64 " graphs with more than three starts\n", strided_starts);
+    EXPECT(strided_starts > 1400, "only %" PRIu64 " graphs gave a walker of three a second start", strided_starts);
+}
+
+// The random graphs have at most 6 branch nodes: one bitmap word.  A comb of 70 branch nodes, each with a leaf and the next
+// branch node as successors and one arm back to the comb's first node, puts up to 70 levels on the stack and marks bits in
+// three words, by three interleaved walkers whose starts enter the comb at different depths.
+static void deep_comb() {
+    const int B = 70;
+    std::vector<E> edges;
+    for (int j = 0; j < B; ++j) {
+        edges.push_back({2 * j, j + 1 < B ? 2 * j + 2 : 2 * B, 3});
+        edges.push_back({2 * j, 2 * j + 1, 2});
+        if (j % 7 == 3) edges.push_back({2 * j, 0, 1});
+    }
+    const Toy t = make(2 * B + 1, edges, {0, 20, 80, 2, 66, 130, 1}, {5, 71});
+    const Walked one = check(t, "comb");
+    const Walked three = check(t, "comb, three interleaved walkers", 3);
+    EXPECT(three.contigs == one.contigs && three.steps == one.steps, "comb: stride 3 differs from stride 1");
+    size_t longest = 0;
+    for (const auto &ct : one.contigs) longest = std::max(longest, ct.nodes.size());
+    EXPECT(longest == (size_t)B + 1 && contract(t).branch_node.size() == (size_t)B, "comb: the longest path has %zu nodes", longest);
 }
 
 static int faults_of(const Contracted &c) {
@@ -391,6 +446,7 @@ static void check_budget() {
 int main() {
     required_cases();
     random_cases();
+    deep_comb();
     check_validation();
     check_budget();
     if (failures) { std::printf("%d failures\n", failures); return 1; }

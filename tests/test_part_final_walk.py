@@ -1,7 +1,8 @@
 """The final-mode contig walk over a graph in PARTS (dbg_part_final_walk, part_traversal.walk_final, construct_graph /
 output_contigs with final=True): against the vectors the REFERENCE produced with final = True (every DNA case at
 threshold >= 1, built in 1 and in 4 parts), against the single-graph final walk on 3 k reads over 30 kbp (index, every text,
-the FASTA file byte for byte; 4 parts, two-word keys, 2 ranks x 2 passes), and the library's refusals."""
+the FASTA file byte for byte; 4 parts, two-word keys, 2 ranks x 2 passes), on a read set of bubbles with 87 branch nodes
+(more than two words of the walker's bitmap) against both that walk and the oracle, and the library's refusals."""
 import json
 import os
 
@@ -101,33 +102,39 @@ def _reads(err, rank=0, ranks=1):
 _single = {}
 
 
+def walk_resident(set_reads, k, threshold, path):
+    """dbg_walk(final) on the resident graph: index in dict order, texts, the FASTA file's bytes (written to ``path``)."""
+    g = _dbg.Graph()
+    try:
+        set_reads(g)
+        g.build(k)
+        g.refine_edge_order()
+        g.prune(threshold)
+        g.remove_tips()
+        sizes = g.sizes()
+        g.walk(1, 1 << 30)
+        off, score, stamp, seq = g.export_contig_index()
+        order = np.lexsort((seq, stamp))     # starts in dict order, emission order within a start
+        toff, chars = g.export_contig_texts(order)
+        text = chars.tobytes()
+        texts = [text[int(toff[i]):int(toff[i + 1])] for i in range(order.size)]
+        g.write_contigs_fasta(path, indices=order[np.argsort(-score[order].astype(np.int64), kind="stable")], append=False, k_label=k)
+        with open(path, "rb") as fh:
+            fasta = fh.read()
+    finally:
+        g.close()
+    return {"stamp": stamp[order], "seq": seq[order], "length": (off[1:] - off[:-1])[order].astype(np.int64),
+            "score": score[order].astype(np.int64), "texts": texts, "fasta": fasta, "n_branch": sizes["n_branch"],
+            "n_pulled": sizes["n_pulled"]}
+
+
 def single(k, err, tmp):
-    """dbg_walk(final) on the resident graph, once per (k, err): index in dict order, texts, the FASTA file's bytes."""
+    """walk_resident, once per (k, err)"""
     if (k, err) not in _single:
         reads = _reads(err)
         assert np.array_equal(np.concatenate([_reads(err, r, 2) for r in range(2)]), reads)   # the ranks' reads are the one read set, cut
-        g = _dbg.Graph()
-        try:
-            g.set_reads(reads.reshape(-1), np.arange(0, reads.size + 1, L, dtype=np.uint64))
-            g.build(k)
-            g.refine_edge_order()
-            g.prune(THR)
-            g.remove_tips()
-            n_branch = g.sizes()["n_branch"]
-            g.walk(1, 1 << 30)
-            off, score, stamp, seq = g.export_contig_index()
-            order = np.lexsort((seq, stamp))     # starts in dict order, emission order within a start
-            toff, chars = g.export_contig_texts(order)
-            text = chars.tobytes()
-            texts = [text[int(toff[i]):int(toff[i + 1])] for i in range(order.size)]
-            path = os.path.join(tmp, f"single_{k}_{err}.fa")
-            g.write_contigs_fasta(path, indices=order[np.argsort(-score[order].astype(np.int64), kind="stable")], append=False, k_label=k)
-            with open(path, "rb") as fh:
-                fasta = fh.read()
-        finally:
-            g.close()
-        _single[(k, err)] = {"stamp": stamp[order], "seq": seq[order], "length": (off[1:] - off[:-1])[order].astype(np.int64),
-                             "score": score[order].astype(np.int64), "texts": texts, "fasta": fasta, "n_branch": n_branch}
+        _single[(k, err)] = walk_resident(lambda g: g.set_reads(reads.reshape(-1), np.arange(0, reads.size + 1, L, dtype=np.uint64)),
+                                          k, THR, os.path.join(tmp, f"single_{k}_{err}.fa"))
     return _single[(k, err)]
 
 
@@ -223,6 +230,98 @@ def test_stitch_in_small_blocks(monkeypatch):
         assert ctg[::-1] == ref["contigs"][::-1]
     finally:
         g.close()
+
+
+# ---- C2: more than 64 branch nodes: a read set of bubbles ---------------------------------------------------------------------
+# 40 random genomes of 200 bp, each as two haplotypes that differ at 2 SNPs 70 bp apart, and one of 600 bp with 7 SNPs 65 bp
+# apart; every haplotype is one whole read, given three times, and there is no error model.  Every SNP is a bubble whose arms
+# are k nodes long (longer than TIP_DEPTH, so no tip is pulled) and whose first node is a branch node: 40 * 2 + 7 = 87 of
+# them, 40 * 4 + 2^7 = 288 contigs, up to 7 branch nodes on a path (counted with the oracle at k = 21 and 40).  The on-path
+# bitmap of a walker has three words here; in every other case of this file it has one.
+BUBBLE_THR, BUBBLE_BRANCH, BUBBLE_CONTIGS = 2, 87, 288
+
+
+def bubble_reads():
+    import random
+    rng = random.Random(2024)
+    reads = []
+
+    def genome(n, snps):
+        a = [rng.choice("ACGT") for _ in range(n)]
+        b = list(a)
+        for x in snps:
+            b[x] = "ACGT"[("ACGT".index(a[x]) + 1 + rng.randrange(3)) % 4]
+        for hap in (a, b):
+            reads.extend(["".join(hap)] * 3)
+    for _ in range(40):
+        genome(200, (60, 130))
+    genome(600, tuple(70 + 65 * i for i in range(7)))
+    return reads
+
+
+_bubble = {}
+
+
+def bubble_want(k, tmp):
+    """once per k: walk_resident and the oracle's graph and contigs"""
+    if k not in _bubble:
+        reads = bubble_reads()
+        want = walk_resident(lambda g: _set_reads(g, reads), k, BUBBLE_THR, os.path.join(tmp, f"bubble_single_{k}.fa"))
+        og, _, obranch, opulled, oect = orc.construct_graph(reads, k, threshold=BUBBLE_THR, final=True, verbose=False)
+        want.update(oracle=orc.output_contigs(og, obranch, opulled, verbose=False), oracle_pulled=opulled, ect=oect,
+                    oracle_branch=sum(len(s) > 1 for s in og[1].values()))
+        _bubble[k] = want
+    return _bubble[k]
+
+
+@pytest.mark.parametrize("ranks,passes", [(1, 1), (1, 2), (1, 4), (2, 2)])
+@pytest.mark.parametrize("k", [21, 40])
+def test_bubbles_with_more_than_64_branch_nodes(k, ranks, passes, tmp_path_factory):
+    import inproc_dist
+    import multi_gpu
+    import part_traversal
+    tmp = str(tmp_path_factory.getbasetemp())
+    want = bubble_want(k, tmp)
+    assert want["oracle_branch"] == BUBBLE_BRANCH > 64 and want["oracle_pulled"] == [] and len(want["oracle"]) == BUBBLE_CONTIGS
+    assert want["n_branch"] == BUBBLE_BRANCH and want["n_pulled"] == 0
+    assert [t.decode("ascii") for t in want["texts"]] == want["oracle"]
+    assert want["score"].tolist() == [orc.get_score(want["ect"], c, k) for c in want["oracle"]]
+    assert int(want["seq"].max()) == 127                       # 2^7 paths from one start
+    all_reads = bubble_reads()
+    per = len(all_reads) // ranks
+    assert per * ranks == len(all_reads)
+
+    def one(dist, rank):
+        g = _dbg.Graph(device=0)
+        try:
+            _set_reads(g, all_reads[rank * per:(rank + 1) * per])
+            if dist is None:
+                g.build_multipass(k, passes)
+            else:
+                multi_gpu.sharded_build_multipass(g, k, dist, passes)
+            t, flags, branch, pulled = part_traversal.construct_graph(g, k, BUBBLE_THR, dist, final=True)
+            assert branch == [] and not flags.any()
+            assert t.branch["gid"].size == BUBBLE_BRANCH and pulled == []     # nothing pulled: the bubbles are whole
+            index = t.walk_final()                                             # what output_contigs wraps; it drops seq
+            ctg = part_traversal.PartContigs(t, index)
+            assert t.final_mode and t.final is not None
+            chars, off = ctg.packed()
+            text = chars.tobytes()
+            path = os.path.join(tmp, f"bubble_parts_{k}_{ranks}x{passes}.fa")
+            written = ctg.write_fasta(path, k, append=False)
+            return index, [text[int(off[i]):int(off[i + 1])] for i in range(len(ctg))], list(ctg), path, written
+        finally:
+            g.close()
+
+    for rank, (index, texts, strs, path, written) in enumerate([one(None, 0)] if ranks == 1 else inproc_dist.run_ranks(ranks, one)):
+        tag = f"rank {rank}"
+        for col in ("stamp", "seq", "length", "score"):
+            assert np.array_equal(index[col], want[col]), f"{tag}: {col}"
+        assert texts == want["texts"], tag
+        assert strs == want["oracle"], tag
+        assert written == len(want["fasta"]), tag
+    with open(path, "rb") as fh:
+        assert fh.read() == want["fasta"]
 
 
 # ---- D: refusals ------------------------------------------------------------------------------------------------------------

@@ -2,8 +2,11 @@
 function the kernel runs -- against a recursive node-by-node DFS written from debruijn.py:288-316, on hand-made cases (two
 pulled successors of one branch node, a successor chain that re-enters the path inside a segment, a branching start, a
 pulled start, a branch node with dead successors only, merging chains) and on 4000 random graphs of up to 40 nodes cut into
-1 to 4 parts and contracted by a host restatement of the entry and segment rules; the validation predicate against each
-kind of broken row; the step budget (tests/partfinal_host.cpp).  Compiled with the host compiler under AddressSanitizer and
+1 to 4 parts and contracted by a host restatement of the entry and segment rules -- each of them walked once with its own
+stack and bitmap and once by three walkers that share one allocation, interleaved at stride 3 as the kernel lays them out,
+with the neighbours' levels and words filled with a pattern that must survive --; a comb of 70 branch nodes (three bitmap
+words, 70 levels) walked the same two ways; the validation predicate against each kind of broken row; the step budget
+(tests/partfinal_host.cpp).  Compiled with the host compiler under AddressSanitizer and
 UBSan where it offers them, run as a stand-alone program; nothing is loaded into Python."""
 import os
 import shutil
