@@ -43,7 +43,7 @@ typedef struct dbg dbg_t;
 #define DBG_OK 0
 #define DBG_E_ARG (-1)      /* bad argument or call order */
 #define DBG_E_HIP (-2)      /* HIP runtime failure (text in dbg_last_error) */
-#define DBG_E_ALPHABET (-3) /* a read holds a byte outside "ACGT" */
+#define DBG_E_ALPHABET (-3) /* the reads hold more than 32 distinct bytes, or a byte outside "ACGT" in a call that takes ACGT reads only */
 #define DBG_E_CAPACITY (-4) /* hash table or an output limit was exceeded */
 #define DBG_E_NOMEM (-5)    /* host or device allocation failed */
 

@@ -9,6 +9,21 @@
 //   k_walk_*       contig walk / DFS + getScore               [debruijn.py:288-347, II:14-18]
 //
 // Integer/indexing work only: no MFMA.  Bound by HBM traffic of the hash table.
+//
+// The library is ONE translation unit, this file.  Two kinds of headers go into it:
+//   kernel headers (the includes below, dbg_partout.h further down, and what they include) hold kernels and plain C++ in
+//   namespace dbgk.  They know neither struct dbg nor the HIP runtime's host calls, and the host programs under tests/
+//   compile their plain-C++ parts with g++.
+//   section headers (dbg_hip_<topic>.h, and dbg_nextk.h at the end) are stretches of this translation unit, not
+//   self-contained: each relies on what stands in front of its include and opens with what it holds and what it needs.
+//     dbg_hip_handle.h     struct dbg, the arena and the names of its slots, ShardState, buf_ensure, HIPCHK / CHK, Timer
+//     dbg_hip_scan.h       exclusive_scan / reduce_sum and their functors; synthetic reads, checksum; read-start bitmap
+//     dbg_hip_table.h      kernels of the global-table build (a3 + a4)
+//     dbg_hip_partfinal.h  final-mode walk on a graph in parts
+//     dbg_nextk.h          dbg_build_from_walk(s)
+//   Everything else stands in this file between them, section by section under banner comments, in the order the
+//   sections rely on: traversal kernels, the ABI of the handle and its reads, build dispatch, the ABI of one graph, the
+//   query side, the LDS engines' host side, shards, multi-pass builds, graphs in parts, scores, contig output.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,627 +59,9 @@
 
 using namespace dbgk;
 
-// Slots of the arena h->ar_misc: one meaning each, in every build path of the super-k-mer engines
-enum MiscSlot {
-    MISC_SEGMENTS,      // segment table: what the extraction wrote, or the (bucket, sender) segments a shard received
-    MISC_L1_CHILDREN,   // children of multisplit level 1 (start, count)
-    MISC_MS_SCPRE,      // multisplit_level's scratch: super-chunk prefix,
-    MISC_MS_CMAT,       // ... count matrix (a pre-split extraction writes level 1's itself),
-    MISC_MS_OFFS,       // ... scanned offsets
-    MISC_BUCKETS,       // final buckets (start, count)
-    MISC_RANGES,        // SkRange per bucket and per hash sub-range
-    MISC_QUERY_SEGS,    // segments of the cross-bucket queries' owner / target split
-    MISC_ESTIMATE_SET,  // hash set of the distinct-k-mer estimate
-    MISC_SLOTS
-};
-
-#ifndef DBG_L1_WIDE_FROM
-#define DBG_L1_WIDE_FROM 20  // total bucket bits from which level 1 of the multisplit takes 10 bits instead of 9 (11..20)
-#endif
-#ifndef DBG_PS_WG_PER_CU
-#define DBG_PS_WG_PER_CU DBG_EXW_WAVES  // extraction workgroups per CU of a pre-split extraction
-#endif
-#ifndef DBG_EXTRACT_PRESPLIT
-#define DBG_EXTRACT_PRESPLIT 4  // default of option "extract_presplit" 
-#endif
-
-// ------------------------------------------------------------------------------------------
-// handle
-// ------------------------------------------------------------------------------------------
-struct dbg {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-
-    // reads
-    char *d_bases = nullptr;
-    bool own_bases = false;
-    uint64_t n_bytes = 0;
-    uint64_t *d_offsets = nullptr;
-    bool own_offsets = false;
-    uint64_t n_reads = 0;
-    uint32_t *d_startbits = nullptr;  // bit p set: a read starts at byte p (bit n_bytes = sentinel)
-    uint64_t startbits_words = 0;
-
-    // build
-    int k = 0;
-    Slot *d_tab = nullptr;
-    uint64_t cap = 0;
-    int cap_log2 = 0;
-    uint32_t *d_occ = nullptr;  // occupancy bitmap over slots
-    uint64_t *d_scalars = nullptr;  // [0] error flags [1] N_k [2] N_e [3..63] scratch [64..127] kernel descriptors
-    uint64_t n_kmer_inst = 0, n_edge_inst = 0;
-    uint64_t n_nodes = 0, n_edges = 0;
-    uint64_t *d_keys = nullptr, *d_stamps = nullptr;
-    uint64_t *d_keys_hi = nullptr;  // k > 31 only: bits 2k-1..64 of every node's k-mer (dbg_wide.h)
-    uint32_t *d_cnt = nullptr;
-    uint8_t *d_flags = nullptr;
-    uint8_t *d_order = nullptr;  // successor codes ranked by (count desc, ascii asc), 2 bits each
-    uint8_t *d_deg = nullptr;    // distinct successors (pre-pruning outdegree) -- feeds the CSR row scan
-    uint8_t *d_fsorder = nullptr; // successor codes in first-seen order (dbg_refine_edge_order)
-    bool order_exact = false;
-    uint32_t *d_succ = nullptr;
-    bool nodes_in_arena = false;  // node arrays borrowed from ar_node (super-k-mer engine)
-    bool csr_built = false;       // rowptr/col/ecnt already written by k_sk_count
-    uint64_t *d_rowptr = nullptr;
-    uint32_t *d_col = nullptr, *d_ecnt = nullptr;
-    // engine 0 writes ONE representation in the build: keys, stamps (32-bit while the reads stay below 2 GiB), one byte
-    // per node (indegree | present bases << 1) and the CSR with 32-bit row pointers.  The dense per-base views above
-    // (d_cnt, d_succ, d_order, 64-bit d_stamps / d_rowptr, plain d_flags) are derived by ensure_dense() on first use.
-    bool dense_pending = false;
-    uint32_t *d_rowptr32 = nullptr;
-    void *d_stamps_st = nullptr;
-    int stamps_st_bytes = 0;
-
-    // prune / tips
-    bool pruned = false, tipped = false;
-    uint64_t n_branch = 0, n_pulled = 0, tip_rounds = 0;
-    uint64_t *d_pull_rank = nullptr;
-
-    // pull reads
-    uint8_t *d_read_flags = nullptr;
-    uint64_t n_pull_reads = 0;
-    bool pull_reads_done = false;
-
-    // walk
-    uint64_t n_starts = 0, n_contigs = 0, contig_chars = 0;
-    bool starts_known = false;    // n_starts counted for the current graph
-    // engine 0, single GPU: the bucketed super-k-mer records of the last build (arena-owned, valid until the next build /
-    // extraction): dbg_refine_edge_order re-reads them bucket by bucket instead of streaming the reads against a global set
-    struct { const uint64_t *w0 = nullptr, *w1 = nullptr; const void *st = nullptr; int st_bytes = 0;
-             const uint64_t *b_start = nullptr, *b_cnt = nullptr; bool valid = false; } sk_src;
-    uint64_t *d_ctg_off = nullptr;
-    char *d_ctg_chars = nullptr;
-    uint64_t *d_ctg_score = nullptr, *d_ctg_stamp = nullptr;
-    uint32_t *d_ctg_seq = nullptr;
-    uint32_t *d_ctg_start = nullptr;  // list-ranking walk: start node of every contig (text on demand, dbg_export_contig_text)
-    uint32_t *d_lift = nullptr;       // binary-lifting tables of the last walk, built on the first text request
-    int lift_levels = 0;
-    bool walked = false;          // contig text materialised
-    bool walk_final = false;      // the last walk was a final-mode one (all simple paths, not chains)
-    bool walk_indexed = false;    // contig index (offsets, scores, start stamps) valid
-    bool walk_sizes_only = false; // the last walk (final-mode DFS) exceeded max_chars: counts valid, no index, no start nodes
-    uint64_t part_final_steps = dbgk::FW_DEFAULT_STEPS;  // option "part_final_walk_steps": steps a walker of dbg_part_final_walk may take in a pass (2^24: 22 s at the 1.3 us a step measured; the enumeration is exponential in the worst case)
-    uint64_t walk_jump_min = 1ull << 14;  // non-final walk: list ranking from this many nodes on (below: one thread per start)
-
-    // alphabet / node layout: 2 bits and 4 successors for DNA, 5 bits and 32 for the generic engine
-    int D = 4, sym_bits = 2, n_sym = 0;
-    bool alpha_known = false, is_dna = true;
-    uint8_t alphabet[32] = {0};       // generic: code -> byte (codes are assigned in byte order)
-    uint8_t *d_lut = nullptr;         // generic: byte -> code (256 entries)
-    char *d_alpha = nullptr;          // generic: code -> byte (32 entries, device)
-    uint32_t *d_keepmask = nullptr;   // generic: surviving successors per node
-    uint8_t *d_rank_mc = nullptr, *d_rank_fs = nullptr;  // generic: [n][32] successor codes by rank
-
-    // options (dbg_set_option)
-    int engine = 0;          // 0 = super-k-mer partitioned build, 1 = single global hash table
-    int bucket_bits = 0;     // 0 = auto (super-k-mer engine)
-    int lds_slots = 4096;    // LDS table slots per bucket workgroup (2048 or 4096)
-    int phase_limit = 0;     // ablation of k_sk_count (timing only; the build then fails on purpose)
-    int est_scale_pct = 100; // test hook: scales the distinct-k-mer estimate (a low one exercises the capacity retry)
-    int wide_engine = 1;     // k = 32..63: 1 = super-k-mer / LDS engine (dbg_wsk.h), 0 = global reference-keyed table (dbg_wide.h)
-    int count_kernel_u64 = 3; // option "count_kernel_u64": the count kernel of 64-bit stamps (shards, reads of 2 GiB and more): 3 = k_sk_count3 (one hint per slot; 12.2 ms on a 10 M-read shard), 1 = k_sk_count (13.4), 2 = k_sk_count2 (15.5: 320 staged records)
-    int stamp64 = 0;         // option "stamp64" 1: dbg_build keeps 64-bit stamps even for reads below 2 GiB (what reads of 2 GiB and more get by themselves; tests)
-    int resolve_sorted = 0;  // option "resolve_sorted" 1: cross-bucket queries grouped by the 512 level-1 groups of their target before k_succ_resolve.  Measured (tools/resolve_ab.py, 10 M reads): 3.09 ms with the grouping against 2.05 ms in the askers' order -- off
-    int resolve_direct = 1;  // option "resolve_direct" 1: the resolver of a single-GPU build takes a successor's node from the directory entry alone where dir_decide (dbg_dir.h) can name it, and reads no key for it; 0: every query reads and compares its key run.  Measured: DESIGN.md 3
-    int resolve_count = 0;   // option "resolve_count" 1 (tests): the resolvers' counting instantiation fills resolve_direct_hits / resolve_keyed
-    uint64_t resolve_direct_hits = 0, resolve_keyed = 0;  // queries answered without / with a key read, summed over the handle's resolver launches under "resolve_count" (dbg_get_counter)
-    int wcount_kernel = 2;   // 32 <= k <= 63, 32-bit stamps: 2 = k_wsk_count2 (one successor hint per slot, deferred lookups), 1 = k_wsk_count
-    int count_kernel = 2;    // k <= 31, 4096 slots: 2 = k_sk_count2 (successor hints, 16-bit counters; falls back to 1 on counter overflow), 1 = k_sk_count
-
-    // grow-only device arena of the super-k-mer engine: hipMalloc of tens of GB costs seconds,
-    // so buffers survive across dbg_build calls on the same handle
-    struct Buf {
-        void *p = nullptr;
-        uint64_t bytes = 0;
-    };
-    Buf ar_rec[2][3], ar_q[2][3], ar_node[8], ar_misc[MISC_SLOTS], ar_csr[4], ar_dir, ar_l2, ar_scan, ar_shard[6], ar_walk[3], ar_wide[6], ar_refine[4], ar_tips[4], ar_part[4][3] /* records of dbg_shard_extract_part, per part */;
-    int sk_T = 0, sk_l1 = 0, sk_l2 = 0, sk_nb2 = 0 /* scaled second level, 0 = power of two */, sk_cap = 0;
-    bool refine_streaming = false;  // option (tests): dbg_refine_edge_order always takes the pass over the reads
-    int target_distinct = 0;  // option: mean distinct k-mers per bucket the auto geometry aims at (0 = default)
-    int shard_stamp64 = 0;    // option: dbg_shard_extract hands out 64-bit rank-local stamps even below 2 GiB of reads (tests)
-    int extract_generic = 0;  // option: 1 = the window-minimum-through-LDS extraction kernels instead of the per-window register ones (A/B, tests)
-    int extract_presplit = DBG_EXTRACT_PRESPLIT;  // option: dbg_build's extraction pre-splits its records by this many top bits of the bucket hash (0: off)
-    uint64_t presplit_rehists = 0;  // builds whose level 1 took another width than the pre-split extraction counted for, so it ran its histogram pass (dbg_get_counter)
-    uint64_t presplit_fallbacks = 0;  // builds whose pre-split extraction overflowed a sub-segment and ran again without the split (dbg_get_counter)
-    uint64_t refine_crowded = 0, pull_crowded = 0;  // dbg_refine_edge_order / dbg_mark_pull_reads calls whose per-range kernel met a crowded range and fell back to the pass over the reads (dbg_get_counter)
-    uint64_t sk_n_ranges = 0, sk_n_buckets = 0;
-    SkGeom sk_geom{};            // hash -> bucket mapping of the last partitioned build (k_succ_resolve)
-    void *shard_state = nullptr;  // ShardState (multi-GPU builds)
-    void *multipass = nullptr;    // MultiPass (dbg_build_multipass): the parts of the graph, parked in HBM
-    bool dropping_parts = false;  // dbg_destroy / a build of another kind: nothing is parked
-    dbg *spare_part = nullptr;    // the part handle of the last ONE-pass sharded build: its arenas serve the next one (bench loops)
-    bool wide_owner = false;      // a part of a multi-pass build: successor ids are (owner byte, 32-bit local id), not tagged
-    bool borrowed_stream = false; // sub-handle of a multi-pass build: the stream belongs to the parent
-    bool arena_freed = false;     // an arena buffer went back to the memory pool since the last trim
-    std::vector<uint64_t> host_seg_cnt;  // sk_extract: records per extraction segment (host copy)
-    std::vector<uint64_t> host_scpre;    // multisplit_level: staging that must outlive an asynchronous upload
-    uint64_t shard_node_limit = 0;  // option (tests): lowers the 2^29 - 16 node ids a shard may hand out
-    bool partial_graph = false;   // the node table is one shard of several: successor ids point into other handles
-    // branch k-mer lookup (pull-out reads)
-    uint64_t *d_btab = nullptr;
-    uint64_t btab_cap = 0;
-    // graph of dbg_build_from_walk(s) (dbg_nextk.h): nk_reads contigs of nk_bytes characters are virtual reads in front of
-    // the real ones; their pull-out test needs, per block of contigs, the chain successors of the block's source graph,
-    // z(x) and the start of every contig
-    struct NkBlock {
-        uint64_t n_src = 0, n_reads = 0;  // nodes of the source graph, contigs of the block
-        uint32_t *next = nullptr, *z = nullptr, *start = nullptr;
-    };
-    bool nk_graph = false;
-    uint64_t nk_reads = 0, nk_bytes = 0;
-    std::vector<NkBlock> nk_blocks;
-    uint8_t *d_nk_read_flags = nullptr;
-
-    // query side (dbg_lookup.h).  dir_valid: ar_dir, the SkRange array, sk_geom and sk_cap are those of the build that made
-    // the CURRENT graph (a single-GPU dbg_build on one of the LDS engines) -- set there, cleared by everything that replaces
-    // or reshapes the graph or reuses ar_dir; never inferred from ar_dir.p
-    bool dir_valid = false;
-    int lookup_index = 0;     // option "lookup_index" 1 (tests): the sorted index even where the directory is valid
-    Buf ar_lookup[3];         // sorted index of the current graph: keys, ids, keys_hi (two-word keys) -- 12 or 20 B per node
-    bool lookup_built = false;
-    uint64_t lookup_index_builds = 0, lookup_dir_calls = 0, lookup_index_calls = 0;  // dbg_get_counter
-    // a part of a multi-pass build: ar_dir, the SkRange array, sk_geom and the node arrays are those the part finished its
-    // count with on the LDS engine (multipass_parts says so; like dir_valid never inferred from a pointer)
-    bool part_dir_ok = false;
-    uint64_t part_lookup_calls = 0;  // dbg_part_lookup_nodes[_device] / dbg_part_score_sequences calls that ran (dbg_get_counter)
-
-    dbg_stats_t stats{};
-    dbg_ingest_stats_t ingest{};  // the last FASTA ingest
-    dbg_contig_out_stats_t ctgout{};  // the last streamed contig output (dbg_ctgout.h)
-    uint64_t ctgout_chunk = 0;        // option "ctgout_chunk_bytes": window size where a call names none (0: CO_DEFAULT_CHUNK)
-};
-
-// What a sharded build leaves behind for the exchange of successors owned by other ranks.
-struct ShardState {
-    int n_shards = 0, my_shard = 0, shard_bits = 0, k = 0;
-    std::vector<uint64_t> q_start, q_cnt;   // remote queries grouped by owner (own group: count 0)
-    uint64_t n_remote = 0;
-    uint64_t n_kmer_inst_local = 0;          // k-mer instances of the reads this rank extracted
-    std::vector<uint64_t> l1_counts;         // records per level-1 bucket (512) of the last dbg_shard_extract
-    int rec_words = 1, rec_stamp_bytes = 4;  // what dbg_shard_extract handed out: words per record in d_w0, bytes per stamp
-};
-static ShardState &shard_of(dbg *h);
-static void multipass_free(dbg *h);
-static void drop_spare_part(dbg *h);
-
-// Arena buffers come from the device's stream-ordered memory pool (hipMallocAsync on the handle's stream) with the
-// pool told to keep what is freed: a hipMalloc / hipFree of several GB costs ~0.1 s each, and a multi-pass build
-// allocates, trims and frees a few hundred GB in pieces of similar sizes -- 14 s of allocator calls around 0.4 s of
-// kernels before this.  Everything a handle does is on its one stream, so stream order is program order.
-static int buf_ensure(dbg *h, dbg::Buf &b, uint64_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return DBG_OK;
-    if (b.p) { (void)hipFreeAsync(b.p, h->stream); h->arena_freed = true; }
-    b.p = nullptr;
-    b.bytes = 0;
-    static const bool trace = getenv("DBG_TRACE_ALLOC") != nullptr;  // diagnostic: arena allocations that take longer than 5 ms
-    const auto t_alloc = std::chrono::steady_clock::now();
-    hipError_t e = hipMallocAsync(&b.p, bytes, h->stream);
-    if (trace) {
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_alloc).count();
-        if (ms > 5.0) fprintf(stderr, "[dbg] hipMallocAsync(%.3f GB) took %.1f ms (buffer %p of handle %p)\n", bytes / 1e9, ms, (void *)&b, (void *)h);
-    }
-    if (e != hipSuccess) {
-        // the pool may be holding freed blocks of the wrong sizes: give them back to the device and try once more
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(h->stream);
-        hipMemPool_t pool;
-        if (hipDeviceGetDefaultMemPool(&pool, h->device) == hipSuccess) (void)hipMemPoolTrimTo(pool, 0);
-        e = hipMallocAsync(&b.p, bytes, h->stream);
-    }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        h->err = std::string("hipMallocAsync(") + std::to_string(bytes) + "): " + hipGetErrorString(e);
-        b.p = nullptr;
-        return DBG_E_NOMEM;
-    }
-    b.bytes = bytes;
-    return DBG_OK;
-}
-static void buf_free(dbg *h, dbg::Buf &b) {
-    if (b.p) { (void)hipFreeAsync(b.p, h->stream); h->arena_freed = true; }
-    b.p = nullptr;
-    b.bytes = 0;
-}
-// Blocks the pool kept for reuse go back to the device: called when a build is complete, so that what the library
-// holds is what it uses (other allocators of the process -- torch -- see the rest) and a later build does not find the
-// pool full of blocks of the wrong sizes.
-static void pool_trim(dbg *h) {
-    if (!h->arena_freed) return;
-    (void)hipStreamSynchronize(h->stream);
-    hipMemPool_t pool;
-    if (hipDeviceGetDefaultMemPool(&pool, h->device) == hipSuccess) (void)hipMemPoolTrimTo(pool, 0);
-    (void)hipGetLastError();
-    h->arena_freed = false;
-}
-
-#define HIPCHK(h, call)                                                                      \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                    \
-            return e_ == hipErrorOutOfMemory ? DBG_E_NOMEM : DBG_E_HIP;                      \
-        }                                                                                    \
-    } while (0)
-
-#define CHK(expr)                 \
-    do {                          \
-        int rc_ = (expr);         \
-        if (rc_ != DBG_OK) return rc_; \
-    } while (0)
-
-template <class T>
-static int dev_alloc(dbg *h, T **p, uint64_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    HIPCHK(h, hipMalloc((void **)p, count * sizeof(T)));
-    return DBG_OK;
-}
-template <class T>
-static void dev_free(T *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-static inline unsigned grid_for(uint64_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
-
-struct Timer {
-    hipEvent_t a = nullptr, b = nullptr;
-    hipStream_t s;
-    explicit Timer(hipStream_t st) : s(st) {
-        (void)hipEventCreate(&a);
-        (void)hipEventCreate(&b);
-        (void)hipEventRecord(a, s);
-    }
-    double stop() {
-        (void)hipEventRecord(b, s);
-        (void)hipEventSynchronize(b);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, a, b);
-        return ms;
-    }
-    ~Timer() {
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-    }
-};
-
-// ------------------------------------------------------------------------------------------
-// generic exclusive scan: out[i] = sum_{j<i} f(j); 256 threads x 16 items per block
-// ------------------------------------------------------------------------------------------
-constexpr int SCAN_ITEMS = 16;
-constexpr int SCAN_TILE = 256 * SCAN_ITEMS;
-
-template <class F>
-__global__ __launch_bounds__(256) void k_scan_reduce(uint64_t n, F f, uint64_t *partial) {
-    uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t s = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i)
-        if (base + i < n) s += f(base + i);
-    uint64_t tot;
-    (void)block_exscan_256(s, &tot);
-    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
-}
-
-// single block: partial[] -> exclusive prefix in place, grand total to *total
-__global__ __launch_bounds__(256) void k_scan_partials(uint64_t *partial, uint64_t nblk, uint64_t *total) {
-    uint64_t carry = 0;
-    for (uint64_t base = 0; base < nblk; base += 256) {
-        uint64_t i = base + threadIdx.x;
-        uint64_t v = i < nblk ? partial[i] : 0;
-        uint64_t tot;
-        uint64_t ex = block_exscan_256(v, &tot);
-        if (i < nblk) partial[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-
-template <class F, class OutT>
-__global__ __launch_bounds__(256) void k_scan_write(uint64_t n, F f, const uint64_t *partial, OutT *out) {
-    uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_ITEMS;
-    uint64_t v[SCAN_ITEMS];
-    uint64_t s = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        v[i] = (base + i < n) ? f(base + i) : 0;
-        s += v[i];
-    }
-    uint64_t tot;
-    uint64_t run = partial[blockIdx.x] + block_exscan_256(s, &tot);
-#pragma unroll
-    for (int i = 0; i < SCAN_ITEMS; ++i) {
-        if (base + i < n) out[base + i] = (OutT)run;
-        run += v[i];
-    }
-}
-
-// out must hold n entries; *d_total (device) receives the total; returns total on host too
-template <class F, class OutT>
-static int exclusive_scan(dbg *h, uint64_t n, F f, OutT *out, uint64_t *h_total) {
-    uint64_t nblk = (n + SCAN_TILE - 1) / SCAN_TILE;
-    if (nblk == 0) nblk = 1;
-    CHK(buf_ensure(h, h->ar_scan, (nblk + 1) * 8));
-    uint64_t *partial = (uint64_t *)h->ar_scan.p;
-    uint64_t *d_total = partial + nblk;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_reduce<F>), dim3((unsigned)nblk), dim3(256), 0, h->stream, n, f, partial);
-    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(256), 0, h->stream, partial, nblk, d_total);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_write<F, OutT>), dim3((unsigned)nblk), dim3(256), 0, h->stream, n, f,
-                       partial, out);
-    if (!h_total) return DBG_OK;  // the caller does not need the total on the host: no synchronisation
-    hipError_t e = hipMemcpyAsync(h_total, d_total, 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        h->err = std::string("exclusive_scan: ") + hipGetErrorString(e);
-        return DBG_E_HIP;
-    }
-    return DBG_OK;
-}
-
-template <class F>
-static int reduce_sum(dbg *h, uint64_t n, F f, uint64_t *h_total) {
-    uint64_t nblk = (n + SCAN_TILE - 1) / SCAN_TILE;
-    if (nblk == 0) nblk = 1;
-    CHK(buf_ensure(h, h->ar_scan, (nblk + 1) * 8));
-    uint64_t *partial = (uint64_t *)h->ar_scan.p;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_reduce<F>), dim3((unsigned)nblk), dim3(256), 0, h->stream, n, f, partial);
-    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(256), 0, h->stream, partial, nblk, partial + nblk);
-    hipError_t e = hipMemcpyAsync(h_total, partial + nblk, 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        h->err = std::string("reduce_sum: ") + hipGetErrorString(e);
-        return DBG_E_HIP;
-    }
-    return DBG_OK;
-}
-
-struct OccBytes32 {  // occupied slots among 32 one-byte flags (each 0 or 1)
-    const uint8_t *occ;
-    __device__ uint64_t operator()(uint64_t w) const {
-        const uint4 a = reinterpret_cast<const uint4 *>(occ)[2 * w], b = reinterpret_cast<const uint4 *>(occ)[2 * w + 1];
-        return __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w);
-    }
-};
-struct PopcWords {
-    const uint32_t *w;
-    __device__ uint64_t operator()(uint64_t i) const { return __popc(w[i]); }
-};
-struct DegOf {
-    const uint8_t *deg;
-    __device__ uint64_t operator()(uint64_t i) const { return deg[i]; }
-};
-struct U64At {
-    const uint64_t *p;
-    __device__ uint64_t operator()(uint64_t i) const { return p[i]; }
-};
-struct KmerInstances {  // k-mer instances of read i
-    const uint64_t *off;
-    uint64_t k;
-    __device__ uint64_t operator()(uint64_t i) const { const uint64_t len = off[i + 1] - off[i]; return len >= k ? len - k + 1 : 0; }
-};
-struct WRecLenAt {   // k-mers of wide record i
-    const uint64_t *w1;
-    __device__ uint64_t operator()(uint64_t i) const { return (uint64_t)wrec_len(w1[i]); }
-};
-struct WRecSuccAt {  // 1 if the last k-mer of wide record i has a successor
-    const uint64_t *w1;
-    __device__ uint64_t operator()(uint64_t i) const { return (uint64_t)wrec_has_succ(w1[i]); }
-};
-struct FlagSet {
-    const uint8_t *f;
-    uint8_t mask, want;
-    __device__ uint64_t operator()(uint64_t i) const { return (f[i] & mask) == want; }
-};
-
-// ------------------------------------------------------------------------------------------
-// synthetic reads (device twin of py-debruijn_amd/synth.py) + checksum
-// ------------------------------------------------------------------------------------------
-__device__ inline uint64_t synth_draw(uint64_t key, uint64_t ctr) { return mix64(key ^ (ctr * 0xD6E8FEB86659FD93ull)); }
-
-__global__ __launch_bounds__(256) void k_synth(char *bases, uint64_t *offsets, uint64_t kg, uint64_t ks, uint64_t ke,
-                                               uint64_t genome_len, uint64_t first_read, uint64_t n_reads,
-                                               uint32_t read_len, uint32_t err_thr) {
-    const uint64_t total = n_reads * read_len;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint64_t r = i / read_len, j = i - r * read_len, gr = first_read + r;
-        const uint64_t start = synth_draw(ks, gr) % (genome_len - read_len + 1);
-        uint32_t code = (uint32_t)(synth_draw(kg, start + j) & 3);
-        if (err_thr) {
-            const uint64_t e = synth_draw(ke, gr * read_len + j);
-            if ((uint32_t)(e & 0xFFFFFFu) < err_thr) code = (code + 1 + (uint32_t)((e >> 24) % 3)) & 3;
-        }
-        bases[i] = "ACGT"[code];
-        if (j == 0) offsets[r] = i;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) offsets[n_reads] = total;
-}
-
-__global__ __launch_bounds__(256) void k_checksum(const char *bases, uint64_t n, unsigned long long *out) {
-    uint64_t s = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        s += mix64((uint64_t)(uint8_t)bases[i] + 256ull * i);
-    s = wave_sum_u64(s);
-    if ((threadIdx.x & 63) == 0) atomicAdd(out, (unsigned long long)s);
-}
-
-// ------------------------------------------------------------------------------------------
-// read-start bitmap
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_startbits(const uint64_t *offsets, uint64_t n_reads, uint32_t *bits) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= n_reads) {
-        uint64_t p = offsets[i];
-        atomicOr(&bits[p >> 5], 1u << (p & 31));
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// a3 + a4: encode, hash insert, successor counters, first-occurrence stamp
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_table_init(Slot *tab, uint64_t cap) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cap) {
-        uint4 *p = reinterpret_cast<uint4 *>(tab + i);
-        p[0] = make_uint4(~0u, ~0u, ~0u, ~0u);
-        p[1] = make_uint4(0, 0, 0, 0);
-    }
-}
-
-__global__ __launch_bounds__(256) void k_count(const char *__restrict__ bases, uint64_t n_bytes,
-                                               const uint32_t *__restrict__ startbits, int k, Slot *tab,
-                                               uint64_t cap_mask, int hash_shift, uint32_t *occ,
-                                               unsigned long long *scalars) {
-    __shared__ TileLds t;
-    const uint64_t tile0 = (uint64_t)blockIdx.x * TILE;
-    const uint32_t bad = load_tile(t, bases, n_bytes, startbits, tile0);
-    if (bad) atomicOr(&scalars[0], STATUS_BAD_BASE);
-    __syncthreads();
-
-    const uint32_t mid_mask = (k >= 2) ? ((1u << (k - 1)) - 1u) : 0u;
-    uint64_t n_k = 0, n_e = 0;
-    for (int j = threadIdx.x; j < TILE; j += 256) {
-        const uint64_t p = tile0 + j;
-        if (p >= n_bytes) break;
-        const uint32_t sw = startwin32(t, j);
-        if ((sw >> 1) & mid_mask) continue;        // a read boundary inside the k-mer
-        const uint32_t s0 = sw & 1u;                // k-mer sits at position 0 of its read
-        const uint32_t sk = (sw >> k) & 1u;         // position p+k starts another read (or is the end)
-        if (sk && s0) continue;                     // read of length exactly k: contributes nothing [:126]
-        const uint64_t win = window32(t, j);
-        const uint64_t kmer = win >> (64 - 2 * k);
-        const uint32_t b = (uint32_t)(win >> (62 - 2 * k)) & 3u;
-        const uint64_t stamp = (p << 1) | (s0 ^ 1u);
-        n_k += 1;
-        n_e += sk ^ 1u;
-
-        uint64_t slot = kmer_hash(kmer) >> hash_shift;
-        bool found = false;
-        for (uint64_t probe = 0; probe <= cap_mask; ++probe) {
-            unsigned long long cur =
-                __hip_atomic_load(&tab[slot].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == EMPTY_KEY) {
-                cur = atomicCAS(&tab[slot].key, EMPTY_KEY, (unsigned long long)kmer);
-                if (cur == EMPTY_KEY) {
-                    atomicOr(&occ[slot >> 5], 1u << (slot & 31));
-                    cur = kmer;
-                }
-            }
-            if (cur == kmer) { found = true; break; }
-            slot = (slot + 1) & cap_mask;
-        }
-        if (!found) { atomicOr(&scalars[0], STATUS_TABLE_FULL); continue; }  // table full
-        if (!sk) atomicAdd(&tab[slot].cnt[b], 1u);
-        atomicMin(&tab[slot].stamp, (unsigned long long)stamp);
-    }
-    // one update per workgroup and counter: these are same-address atomics (serialised chip-wide, ~12 ns each)
-    uint64_t tot_k, tot_e;
-    (void)block_exscan_256(n_k, &tot_k);
-    (void)block_exscan_256(n_e, &tot_e);
-    if (threadIdx.x == 0) {
-        if (tot_k) atomicAdd(&scalars[1], (unsigned long long)tot_k);
-        if (tot_e) atomicAdd(&scalars[2], (unsigned long long)tot_e);
-    }
-}
-
-// occupied slots -> node arrays (table order); the slot's stamp field is re-used for the node id
-__global__ __launch_bounds__(256) void k_gather(Slot *tab, const uint32_t *occ, const uint32_t *word_rank,
-                                                uint64_t n_words, uint64_t *keys, uint64_t *stamps, uint32_t *cnt,
-                                                uint8_t *flags) {
-    uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= n_words) return;
-    uint32_t bits = occ[w];
-    uint32_t node = word_rank[w];
-    while (bits) {
-        const int b = __ffs(bits) - 1;
-        bits &= bits - 1;
-        Slot *s = tab + (w * 32 + b);
-        const uint4 lo = reinterpret_cast<const uint4 *>(s)[0];
-        const uint4 hi = reinterpret_cast<const uint4 *>(s)[1];
-        keys[node] = ((uint64_t)lo.y << 32) | lo.x;
-        const uint64_t st = ((uint64_t)lo.w << 32) | lo.z;
-        stamps[node] = st;
-        reinterpret_cast<uint4 *>(cnt)[node] = hi;
-        flags[node] = (uint8_t)(st & 1);
-        s->stamp = node;
-        ++node;
-    }
-}
-
-__device__ inline uint32_t tab_find(const Slot *tab, uint64_t cap_mask, int hash_shift, uint64_t key) {
-    uint64_t slot = kmer_hash(key) >> hash_shift;
-    for (uint64_t probe = 0; probe <= cap_mask; ++probe) {
-        const uint64_t cur = tab[slot].key;
-        if (cur == key) return (uint32_t)tab[slot].stamp;
-        if (cur == EMPTY_KEY) return NO_NODE;
-        slot = (slot + 1) & cap_mask;
-    }
-    return NO_NODE;
-}
-
-// successor ids (4-way) + successor rank order byte
-__global__ __launch_bounds__(256) void k_succ(const Slot *tab, uint64_t cap_mask, int hash_shift, int k, uint64_t n_nodes,
-                                              const uint64_t *keys, const uint32_t *cnt, uint32_t *succ,
-                                              uint8_t *order, uint8_t *deg) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_nodes) return;
-    const uint64_t kmask = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1);
-    const uint64_t key = keys[i];
-    const uint4 c4 = reinterpret_cast<const uint4 *>(cnt)[i];
-    const uint32_t c[4] = {c4.x, c4.y, c4.z, c4.w};
-    uint32_t s[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-        s[b] = c[b] ? tab_find(tab, cap_mask, hash_shift, ((key << 2) | (uint64_t)b) & kmask) : NO_NODE;
-    reinterpret_cast<uint4 *>(succ)[i] = make_uint4(s[0], s[1], s[2], s[3]);
-    deg[i] = (uint8_t)((c[0] != 0) + (c[1] != 0) + (c[2] != 0) + (c[3] != 0));
-    // rank codes by (count desc, ascii order asc): insertion sort of 4
-    uint32_t code[4] = {0, 1, 3, 2};  // ascii order A, C, G, T as codes
-#pragma unroll
-    for (int a = 1; a < 4; ++a) {
-#pragma unroll
-        for (int b = a; b > 0; --b) {
-            if (c[code[b]] > c[code[b - 1]]) {
-                uint32_t tmp = code[b]; code[b] = code[b - 1]; code[b - 1] = tmp;
-            }
-        }
-    }
-    order[i] = (uint8_t)(code[0] | (code[1] << 2) | (code[2] << 4) | (code[3] << 6));
-}
-
-__global__ __launch_bounds__(256) void k_csr_fill(uint64_t n_nodes, const uint64_t *rowptr, const uint32_t *cnt,
-                                                  const uint32_t *succ, uint32_t *col, uint32_t *ecnt) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_nodes) return;
-    const uint4 c4 = reinterpret_cast<const uint4 *>(cnt)[i];
-    const uint4 s4 = reinterpret_cast<const uint4 *>(succ)[i];
-    const uint32_t c[4] = {c4.x, c4.y, c4.z, c4.w}, s[4] = {s4.x, s4.y, s4.z, s4.w};
-    uint64_t o = rowptr[i];
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-        if (c[b]) { col[o] = s[b]; ecnt[o] = c[b]; ++o; }
-}
+#include "dbg_hip_handle.h"
+#include "dbg_hip_scan.h"
+#include "dbg_hip_table.h"
 
 // ------------------------------------------------------------------------------------------
 // a5 + a6: pruningEdges + branch flag
@@ -2180,16 +1577,16 @@ static int build_wsk(dbg *h, int k, bool *fallback);
 static int finish_graph(dbg *h) {
     if (!h->csr_built) {
         Timer t(h->stream);
-        CHK(buf_ensure(h, h->ar_csr[0], (h->n_nodes + 1) * 8));
-        h->d_rowptr = (uint64_t *)h->ar_csr[0].p;
+        CHK(buf_ensure(h, h->ar_csr[CSR_ROWPTR64], (h->n_nodes + 1) * 8));
+        h->d_rowptr = (uint64_t *)h->ar_csr[CSR_ROWPTR64].p;
         uint64_t total = 0;
         CHK(exclusive_scan(h, h->n_nodes, DegOf{h->d_deg}, h->d_rowptr, &total));
         h->n_edges = total;
         HIPCHK(h, hipMemcpyAsync(h->d_rowptr + h->n_nodes, &h->n_edges, 8, hipMemcpyHostToDevice, h->stream));
-        CHK(buf_ensure(h, h->ar_csr[1], total * 4));
-        CHK(buf_ensure(h, h->ar_csr[2], total * 4));
-        h->d_col = (uint32_t *)h->ar_csr[1].p;
-        h->d_ecnt = (uint32_t *)h->ar_csr[2].p;
+        CHK(buf_ensure(h, h->ar_csr[CSR_COL], total * 4));
+        CHK(buf_ensure(h, h->ar_csr[CSR_ECNT], total * 4));
+        h->d_col = (uint32_t *)h->ar_csr[CSR_COL].p;
+        h->d_ecnt = (uint32_t *)h->ar_csr[CSR_ECNT].p;
         if (h->n_nodes) {
             if (h->D == GEN_D)
                 hipLaunchKernelGGL(k_g_csr_fill, dim3(grid_for(h->n_nodes, 256)), dim3(256), 0, h->stream, h->n_nodes,
@@ -2213,17 +1610,17 @@ static int ensure_dense(dbg *h) {
     if (h->multipass) { h->err = kMultipassGraph; return DBG_E_ARG; }
     if (!h->dense_pending) return DBG_OK;
     const uint64_t n = h->n_nodes, cap = n ? n : 1;
-    CHK(buf_ensure(h, h->ar_node[2], cap * 16));
-    CHK(buf_ensure(h, h->ar_node[4], cap));
-    CHK(buf_ensure(h, h->ar_node[5], cap * 16));
-    CHK(buf_ensure(h, h->ar_csr[0], (cap + 1) * 8));
+    CHK(buf_ensure(h, h->ar_node[NODE_CNT], cap * 16));
+    CHK(buf_ensure(h, h->ar_node[NODE_ORDER], cap));
+    CHK(buf_ensure(h, h->ar_node[NODE_SUCC], cap * 16));
+    CHK(buf_ensure(h, h->ar_csr[CSR_ROWPTR64], (cap + 1) * 8));
     const bool widen = h->stamps_st_bytes == 4;
-    if (widen) CHK(buf_ensure(h, h->ar_node[1], cap * 8));
-    h->d_cnt = (uint32_t *)h->ar_node[2].p;
-    h->d_order = (uint8_t *)h->ar_node[4].p;
-    h->d_succ = (uint32_t *)h->ar_node[5].p;
-    h->d_rowptr = (uint64_t *)h->ar_csr[0].p;
-    if (widen) h->d_stamps = (uint64_t *)h->ar_node[1].p;
+    if (widen) CHK(buf_ensure(h, h->ar_node[NODE_STAMPS64], cap * 8));
+    h->d_cnt = (uint32_t *)h->ar_node[NODE_CNT].p;
+    h->d_order = (uint8_t *)h->ar_node[NODE_ORDER].p;
+    h->d_succ = (uint32_t *)h->ar_node[NODE_SUCC].p;
+    h->d_rowptr = (uint64_t *)h->ar_csr[CSR_ROWPTR64].p;
+    if (widen) h->d_stamps = (uint64_t *)h->ar_node[NODE_STAMPS64].p;
     if (n) {
         if (widen)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dense_from_csr<uint32_t>), dim3(grid_for(n, 256)), dim3(256), 0, h->stream, n,
@@ -2504,16 +1901,16 @@ static int build_wide_once(dbg *h, int k, uint64_t table_capacity_hint, bool pac
     uint64_t sc[4] = {0, 0, 0, 0};
     do {
         Timer t(h->stream);
-        if ((rc = buf_ensure(h, h->ar_wide[0], (pk_words + 3) * 8)) != DBG_OK) break;
-        if ((rc = buf_ensure(h, h->ar_wide[1], cap * sizeof(WSlot))) != DBG_OK) break;
-        if (!packed && (rc = buf_ensure(h, h->ar_wide[2], cap * 16)) != DBG_OK) break;
-        if ((rc = buf_ensure(h, h->ar_wide[3], cap)) != DBG_OK) break;
-        if ((rc = buf_ensure(h, h->ar_wide[4], n_occ * 4)) != DBG_OK) break;
-        pk = (uint64_t *)h->ar_wide[0].p;
-        tab = (WSlot *)h->ar_wide[1].p;
-        tcnt = packed ? nullptr : (uint32_t *)h->ar_wide[2].p;
-        occ = (uint8_t *)h->ar_wide[3].p;
-        word_rank = (uint32_t *)h->ar_wide[4].p;
+        if ((rc = buf_ensure(h, h->ar_wide[WIDE_PACKED], (pk_words + 3) * 8)) != DBG_OK) break;
+        if ((rc = buf_ensure(h, h->ar_wide[WIDE_TABLE], cap * sizeof(WSlot))) != DBG_OK) break;
+        if (!packed && (rc = buf_ensure(h, h->ar_wide[WIDE_TCNT], cap * 16)) != DBG_OK) break;
+        if ((rc = buf_ensure(h, h->ar_wide[WIDE_OCC], cap)) != DBG_OK) break;
+        if ((rc = buf_ensure(h, h->ar_wide[WIDE_WORD_RANK], n_occ * 4)) != DBG_OK) break;
+        pk = (uint64_t *)h->ar_wide[WIDE_PACKED].p;
+        tab = (WSlot *)h->ar_wide[WIDE_TABLE].p;
+        tcnt = packed ? nullptr : (uint32_t *)h->ar_wide[WIDE_TCNT].p;
+        occ = (uint8_t *)h->ar_wide[WIDE_OCC].p;
+        word_rank = (uint32_t *)h->ar_wide[WIDE_WORD_RANK].p;
         (void)hipMemsetAsync(pk + pk_words, 0, 3 * 8, h->stream);
         hipLaunchKernelGGL(k_wtab_init, dim3(grid_for(cap, 256)), dim3(256), 0, h->stream, tab, cap);
         if (tcnt) (void)hipMemsetAsync(tcnt, 0, cap * 16, h->stream);
@@ -2543,22 +1940,22 @@ static int build_wide_once(dbg *h, int k, uint64_t table_capacity_hint, bool pac
         if ((rc = exclusive_scan(h, n_occ, OccBytes32{occ}, word_rank, &total)) != DBG_OK) break;
         if (total >= 0xFFFFFFFFull) { h->err = "more than 2^32-1 nodes"; rc = DBG_E_CAPACITY; break; }
         h->n_nodes = total;
-        if ((rc = buf_ensure(h, h->ar_node[0], total * 8)) != DBG_OK) break;
-        if ((rc = buf_ensure(h, h->ar_node[1], total * 8)) != DBG_OK) break;
-        if ((rc = buf_ensure(h, h->ar_node[2], total * 16)) != DBG_OK) break;
-        if ((rc = buf_ensure(h, h->ar_node[3], total)) != DBG_OK) break;
-        if ((rc = buf_ensure(h, h->ar_node[4], total)) != DBG_OK) break;
-        if ((rc = buf_ensure(h, h->ar_node[5], total * 16)) != DBG_OK) break;
-        if ((rc = buf_ensure(h, h->ar_node[6], total)) != DBG_OK) break;
-        if ((rc = buf_ensure(h, h->ar_wide[5], total * 8)) != DBG_OK) break;
-        h->d_keys = (uint64_t *)h->ar_node[0].p;
-        h->d_stamps = (uint64_t *)h->ar_node[1].p;
-        h->d_cnt = (uint32_t *)h->ar_node[2].p;
-        h->d_flags = (uint8_t *)h->ar_node[3].p;
-        h->d_order = (uint8_t *)h->ar_node[4].p;
-        h->d_succ = (uint32_t *)h->ar_node[5].p;
-        h->d_deg = (uint8_t *)h->ar_node[6].p;
-        h->d_keys_hi = (uint64_t *)h->ar_wide[5].p;
+        if ((rc = buf_ensure(h, h->ar_node[NODE_KEYS], total * 8)) != DBG_OK) break;
+        if ((rc = buf_ensure(h, h->ar_node[NODE_STAMPS64], total * 8)) != DBG_OK) break;
+        if ((rc = buf_ensure(h, h->ar_node[NODE_CNT], total * 16)) != DBG_OK) break;
+        if ((rc = buf_ensure(h, h->ar_node[NODE_FLAGS], total)) != DBG_OK) break;
+        if ((rc = buf_ensure(h, h->ar_node[NODE_ORDER], total)) != DBG_OK) break;
+        if ((rc = buf_ensure(h, h->ar_node[NODE_SUCC], total * 16)) != DBG_OK) break;
+        if ((rc = buf_ensure(h, h->ar_node[NODE_DEG], total)) != DBG_OK) break;
+        if ((rc = buf_ensure(h, h->ar_wide[WIDE_KEYS_HI], total * 8)) != DBG_OK) break;
+        h->d_keys = (uint64_t *)h->ar_node[NODE_KEYS].p;
+        h->d_stamps = (uint64_t *)h->ar_node[NODE_STAMPS64].p;
+        h->d_cnt = (uint32_t *)h->ar_node[NODE_CNT].p;
+        h->d_flags = (uint8_t *)h->ar_node[NODE_FLAGS].p;
+        h->d_order = (uint8_t *)h->ar_node[NODE_ORDER].p;
+        h->d_succ = (uint32_t *)h->ar_node[NODE_SUCC].p;
+        h->d_deg = (uint8_t *)h->ar_node[NODE_DEG].p;
+        h->d_keys_hi = (uint64_t *)h->ar_wide[WIDE_KEYS_HI].p;
         h->nodes_in_arena = true;
         hipLaunchKernelGGL(k_wgather, dim3(grid_for(n_occ * 32, 256)), dim3(256), 0, h->stream, tab, tcnt, occ, word_rank, n_occ,
                            h->d_keys, h->d_keys_hi, h->d_stamps, h->d_cnt, h->d_flags, 1);
@@ -2813,15 +2210,15 @@ extern "C" int dbg_refine_edge_order(dbg_t *h) {
         int fbits = 20;
         while (fbits < 32 && (1ull << fbits) < n_multi * 16) ++fbits;
         // grow-only arena (a multi-k driver calls this once per k: ~700 MB of hipMalloc + hipFree each time otherwise)
-        int rc = buf_ensure(h, h->ar_refine[0], cap * 8);
-        if (rc == DBG_OK) rc = buf_ensure(h, h->ar_refine[1], cap * 4);
-        if (rc == DBG_OK) rc = buf_ensure(h, h->ar_refine[2], cap * 32);
-        if (rc == DBG_OK) rc = buf_ensure(h, h->ar_refine[3], (1ull << fbits) / 8);
+        int rc = buf_ensure(h, h->ar_refine[REFINE_SET_KEYS], cap * 8);
+        if (rc == DBG_OK) rc = buf_ensure(h, h->ar_refine[REFINE_SET_NODE], cap * 4);
+        if (rc == DBG_OK) rc = buf_ensure(h, h->ar_refine[REFINE_ESTAMP], cap * 32);
+        if (rc == DBG_OK) rc = buf_ensure(h, h->ar_refine[REFINE_FILTER], (1ull << fbits) / 8);
         if (rc == DBG_OK) {
-            set_keys = (unsigned long long *)h->ar_refine[0].p;
-            set_node = (uint32_t *)h->ar_refine[1].p;
-            estamp = (unsigned long long *)h->ar_refine[2].p;
-            filter = (uint32_t *)h->ar_refine[3].p;
+            set_keys = (unsigned long long *)h->ar_refine[REFINE_SET_KEYS].p;
+            set_node = (uint32_t *)h->ar_refine[REFINE_SET_NODE].p;
+            estamp = (unsigned long long *)h->ar_refine[REFINE_ESTAMP].p;
+            filter = (uint32_t *)h->ar_refine[REFINE_FILTER].p;
             (void)hipMemsetAsync(set_keys, 0xFF, cap * 8, h->stream);
             (void)hipMemsetAsync(estamp, 0xFF, cap * 32, h->stream);
             (void)hipMemsetAsync(filter, 0, (1ull << fbits) / 8, h->stream);
@@ -3045,17 +2442,17 @@ static int remove_tips_impl(dbg *h, const G &g) {
     h->tip_rounds = 0;
     h->n_pulled = 0;
     // grow-only arena: a hipFree + hipMalloc of the two n_nodes-sized arrays per call cost up to 150 ms at 3.6e8 nodes
-    CHK(buf_ensure(h, h->ar_tips[0], (h->n_nodes ? h->n_nodes : 1) * 8));
-    h->d_pull_rank = (uint64_t *)h->ar_tips[0].p;
+    CHK(buf_ensure(h, h->ar_tips[TIPS_PULL_RANK], (h->n_nodes ? h->n_nodes : 1) * 8));
+    h->d_pull_rank = (uint64_t *)h->ar_tips[TIPS_PULL_RANK].p;
     if (h->n_nodes)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fill<uint64_t>), dim3(grid_for(h->n_nodes, 256)), dim3(256), 0, h->stream,
                            h->d_pull_rank, h->n_nodes, ~0ull);
     if (h->n_branch) {
-        CHK(buf_ensure(h, h->ar_tips[1], h->n_branch * 4));
-        CHK(buf_ensure(h, h->ar_tips[2], h->n_branch * 4));
-        CHK(buf_ensure(h, h->ar_tips[3], h->n_nodes * 8));
-        uint32_t *pend[2] = {(uint32_t *)h->ar_tips[1].p, (uint32_t *)h->ar_tips[2].p};
-        unsigned long long *owner = (unsigned long long *)h->ar_tips[3].p;
+        CHK(buf_ensure(h, h->ar_tips[TIPS_PEND_A], h->n_branch * 4));
+        CHK(buf_ensure(h, h->ar_tips[TIPS_PEND_B], h->n_branch * 4));
+        CHK(buf_ensure(h, h->ar_tips[TIPS_OWNER], h->n_nodes * 8));
+        uint32_t *pend[2] = {(uint32_t *)h->ar_tips[TIPS_PEND_A].p, (uint32_t *)h->ar_tips[TIPS_PEND_B].p};
+        unsigned long long *owner = (unsigned long long *)h->ar_tips[TIPS_OWNER].p;
         unsigned long long *ctr = (unsigned long long *)(h->d_scalars + 24);
         HIPCHK(h, hipMemsetAsync(ctr, 0, 16, h->stream));
         uint64_t n_pending = 0;  // branch nodes, ascending id
@@ -3256,19 +2653,19 @@ static int walk_impl(dbg *h, const G &g, int final_mode, uint64_t max_chars) {
         if (use_jump) {
             if ((rc = dev_alloc(h, &per_score, ns)) != DBG_OK) break;
             // the one-step table, 16 B per node: kept in the arena (a fresh 6 GB hipMalloc costs ~0.2 s at the BASELINE size)
-            if ((rc = buf_ensure(h, h->ar_walk[0], h->n_nodes * sizeof(Jump))) != DBG_OK) break;
-            jump[0] = (Jump *)h->ar_walk[0].p;
+            if ((rc = buf_ensure(h, h->ar_walk[WALK_JUMP], h->n_nodes * sizeof(Jump))) != DBG_OK) break;
+            jump[0] = (Jump *)h->ar_walk[WALK_JUMP].p;
             const dim3 grid(grid_for(h->n_nodes, 256));
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_jump_init<G>), grid, dim3(256), 0, h->stream, h->n_nodes, g, jump[0]);
             // splitters (see k_jump_walk): their list, their walks into a table that is dense over the splitters,
             // then doubling over that table
-            if ((rc = buf_ensure(h, h->ar_walk[2], h->n_nodes * 4)) != DBG_OK) break;
-            uint32_t *slist = (uint32_t *)h->ar_walk[2].p;
+            if ((rc = buf_ensure(h, h->ar_walk[WALK_SPLITTERS], h->n_nodes * 4)) != DBG_OK) break;
+            uint32_t *slist = (uint32_t *)h->ar_walk[WALK_SPLITTERS].p;
             uint64_t n_split = 0;
             if ((rc = compact_ids(h, h->n_nodes, PredSplitter{jump[0]}, slist, &n_split)) != DBG_OK) break;
-            if ((rc = buf_ensure(h, h->ar_walk[1], (2 * n_split + 1) * sizeof(Jump) + (ns + 4) * 4)) != DBG_OK) break;
-            Jump *dense[2] = {(Jump *)h->ar_walk[1].p, (Jump *)h->ar_walk[1].p + n_split};
-            uint32_t *start_rank = (uint32_t *)((Jump *)h->ar_walk[1].p + 2 * n_split);
+            if ((rc = buf_ensure(h, h->ar_walk[WALK_DENSE], (2 * n_split + 1) * sizeof(Jump) + (ns + 4) * 4)) != DBG_OK) break;
+            Jump *dense[2] = {(Jump *)h->ar_walk[WALK_DENSE].p, (Jump *)h->ar_walk[WALK_DENSE].p + n_split};
+            uint32_t *start_rank = (uint32_t *)((Jump *)h->ar_walk[WALK_DENSE].p + 2 * n_split);
             const dim3 sgrid(grid_for(n_split, 256));
             if (n_split)
                 hipLaunchKernelGGL(k_jump_walk, sgrid, dim3(256), 0, h->stream, slist, n_split, jump[0], dense[0]);
@@ -3628,12 +3025,12 @@ static int lookup_index_ensure(dbg *h) {
     const uint64_t n = h->n_nodes;
     if (n > 0x7FFFFFFFull) { h->err = "too many nodes for one sort"; return DBG_E_CAPACITY; }
     const bool two = h->d_keys_hi != nullptr;
-    CHK(buf_ensure(h, h->ar_lookup[0], n * 8));
-    CHK(buf_ensure(h, h->ar_lookup[1], n * 4));
-    if (two) CHK(buf_ensure(h, h->ar_lookup[2], n * 8));
+    CHK(buf_ensure(h, h->ar_lookup[LOOKUP_KEYS], n * 8));
+    CHK(buf_ensure(h, h->ar_lookup[LOOKUP_IDS], n * 4));
+    if (two) CHK(buf_ensure(h, h->ar_lookup[LOOKUP_KEYS_HI], n * 8));
     if (n) {
-        uint64_t *lo_s = (uint64_t *)h->ar_lookup[0].p, *hi_s = (uint64_t *)h->ar_lookup[2].p, *hi_g = nullptr;
-        uint32_t *id_s = (uint32_t *)h->ar_lookup[1].p, *ids = nullptr, *ids1 = nullptr;
+        uint64_t *lo_s = (uint64_t *)h->ar_lookup[LOOKUP_KEYS].p, *hi_s = (uint64_t *)h->ar_lookup[LOOKUP_KEYS_HI].p, *hi_g = nullptr;
+        uint32_t *id_s = (uint32_t *)h->ar_lookup[LOOKUP_IDS].p, *ids = nullptr, *ids1 = nullptr;
         void *tmp = nullptr;
         int rc = DBG_OK;
         do {
@@ -3689,8 +3086,8 @@ static int with_finder(dbg *h, FN &&fn) {
     }
     CHK(lookup_index_ensure(h));
     ++h->lookup_index_calls;
-    return fn(LkIndexFinder{h->d_keys_hi ? (const uint64_t *)h->ar_lookup[2].p : nullptr, (const uint64_t *)h->ar_lookup[0].p,
-                            (const uint32_t *)h->ar_lookup[1].p, h->n_nodes});
+    return fn(LkIndexFinder{h->d_keys_hi ? (const uint64_t *)h->ar_lookup[LOOKUP_KEYS_HI].p : nullptr, (const uint64_t *)h->ar_lookup[LOOKUP_KEYS].p,
+                            (const uint32_t *)h->ar_lookup[LOOKUP_IDS].p, h->n_nodes});
 }
 
 extern "C" int dbg_lookup_nodes_device(dbg_t *h, const void *d_keys, const void *d_keys_hi, uint64_t n, void *d_ids) {
@@ -4000,12 +3397,12 @@ static int sk_extract(dbg *h, int k, uint64_t *w0[2], uint64_t *w1[2], ST *st[2]
         }
         const uint64_t rec_cap = seg_cap * n_seg;
         for (int set = 0; set < 2; ++set) {
-            CHK(buf_ensure(h, h->ar_rec[set][0], rec_cap * 8));
-            CHK(buf_ensure(h, h->ar_rec[set][1], rec_cap * 8));
-            CHK(buf_ensure(h, h->ar_rec[set][2], rec_cap * sizeof(ST)));
-            w0[set] = (uint64_t *)h->ar_rec[set][0].p;
-            w1[set] = (uint64_t *)h->ar_rec[set][1].p;
-            st[set] = (ST *)h->ar_rec[set][2].p;
+            CHK(buf_ensure(h, h->ar_rec[set][REC_W0], rec_cap * 8));
+            CHK(buf_ensure(h, h->ar_rec[set][REC_W1], rec_cap * 8));
+            CHK(buf_ensure(h, h->ar_rec[set][REC_ST], rec_cap * sizeof(ST)));
+            w0[set] = (uint64_t *)h->ar_rec[set][REC_W0].p;
+            w1[set] = (uint64_t *)h->ar_rec[set][REC_W1].p;
+            st[set] = (ST *)h->ar_rec[set][REC_ST].p;
         }
         for (uint64_t g = 0; g < n_seg; ++g) hseg[g] = g * seg_cap;
         HIPCHK(h, hipMemcpyAsync(seg_start, hseg.data(), (size_t)n_seg * 8, hipMemcpyHostToDevice, h->stream));
@@ -4259,10 +3656,10 @@ static int sk_partition(dbg *h, const SkPartitionParams<Est> &pp, const uint64_t
         where = 0;
         if (nb3 > 1) {  // third level: every level-2 child (of the groups this build owns) is split once more
             if (!w0[1]) {  // callers that start at level 2 bring one record set only
-                CHK(buf_ensure(h, h->ar_rec[1][0], (n_rec + 16) * 8));
-                CHK(buf_ensure(h, h->ar_rec[1][1], (n_rec + 16) * 8));
-                CHK(buf_ensure(h, h->ar_rec[1][2], (n_rec + 16) * sizeof(ST)));
-                w0[1] = (uint64_t *)h->ar_rec[1][0].p; w1[1] = (uint64_t *)h->ar_rec[1][1].p; st[1] = (ST *)h->ar_rec[1][2].p;
+                CHK(buf_ensure(h, h->ar_rec[SET_PONG][REC_W0], (n_rec + 16) * 8));
+                CHK(buf_ensure(h, h->ar_rec[SET_PONG][REC_W1], (n_rec + 16) * 8));
+                CHK(buf_ensure(h, h->ar_rec[SET_PONG][REC_ST], (n_rec + 16) * sizeof(ST)));
+                w0[1] = (uint64_t *)h->ar_rec[SET_PONG][REC_W0].p; w1[1] = (uint64_t *)h->ar_rec[SET_PONG][REC_W1].p; st[1] = (ST *)h->ar_rec[SET_PONG][REC_ST].p;
             }
             const uint64_t p_lo = pre ? b_lo * nb2 : 0, p_n = pre ? (uint64_t)bps * nb2 : n_l2;
             CHK((multisplit_level<ST, true>(h, l2_start + p_lo, l2_cnt + p_lo, (uint32_t)p_n, 1, n_rec, w0[0], w1[0], st[0], w0[1],
@@ -4294,7 +3691,7 @@ static int resolve_counts_in(dbg *h) {
 // ---- stages 2..: records given as segments of (in_w0, in_w1, in_st) -> node arrays + successors.
 // The ping-pong sets w0/w1/st (arena) must hold n_rec records; n_inst bounds the distinct k-mers.
 // shard_bits > 0: only buckets whose top shard_bits equal my_shard hold records (the caller made
-// sure); successors owned by other shards are left as remote queries in ar_shard[0..1].
+// sure); successors owned by other shards are left as remote queries in ar_shard[SHARD_Q_KEYS] / [SHARD_Q_COL].
 // host_cnt, pre, xs: see sk_partition
 template <class ST, int CAP, class STI = ST>
 static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, const uint64_t *seg_cnt, uint32_t n_seg,
@@ -4336,21 +3733,21 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
                                                         (h->est_scale_pct == 100 ? (1u << 20) : 1024u));
     uint64_t edge_cap = std::min<uint64_t>(edge_cap_max, node_cap + node_cap / 4 + 16);
     auto ensure_node_arrays = [&]() -> int {
-        CHK(buf_ensure(h, h->ar_node[0], node_cap * 8));
-        CHK(buf_ensure(h, h->ar_node[sizeof(ST) == 8 ? 1 : 7], node_cap * sizeof(ST)));
-        CHK(buf_ensure(h, h->ar_node[3], node_cap));
-        h->d_keys = (uint64_t *)h->ar_node[0].p;
-        h->d_stamps_st = h->ar_node[sizeof(ST) == 8 ? 1 : 7].p;
+        CHK(buf_ensure(h, h->ar_node[NODE_KEYS], node_cap * 8));
+        CHK(buf_ensure(h, h->ar_node[sizeof(ST) == 8 ? NODE_STAMPS64 : NODE_STAMPS32], node_cap * sizeof(ST)));
+        CHK(buf_ensure(h, h->ar_node[NODE_FLAGS], node_cap));
+        h->d_keys = (uint64_t *)h->ar_node[NODE_KEYS].p;
+        h->d_stamps_st = h->ar_node[sizeof(ST) == 8 ? NODE_STAMPS64 : NODE_STAMPS32].p;
         h->stamps_st_bytes = (int)sizeof(ST);
         h->d_stamps = sizeof(ST) == 8 ? (uint64_t *)h->d_stamps_st : nullptr;
-        h->d_flags = (uint8_t *)h->ar_node[3].p;
+        h->d_flags = (uint8_t *)h->ar_node[NODE_FLAGS].p;
         h->nodes_in_arena = true;
-        CHK(buf_ensure(h, h->ar_csr[3], (node_cap + 1) * 4));
-        CHK(buf_ensure(h, h->ar_csr[1], edge_cap * 4));
-        CHK(buf_ensure(h, h->ar_csr[2], edge_cap * 4));
-        h->d_rowptr32 = (uint32_t *)h->ar_csr[3].p;
-        h->d_col = (uint32_t *)h->ar_csr[1].p;
-        h->d_ecnt = (uint32_t *)h->ar_csr[2].p;
+        CHK(buf_ensure(h, h->ar_csr[CSR_ROWPTR32], (node_cap + 1) * 4));
+        CHK(buf_ensure(h, h->ar_csr[CSR_COL], edge_cap * 4));
+        CHK(buf_ensure(h, h->ar_csr[CSR_ECNT], edge_cap * 4));
+        h->d_rowptr32 = (uint32_t *)h->ar_csr[CSR_ROWPTR32].p;
+        h->d_col = (uint32_t *)h->ar_csr[CSR_COL].p;
+        h->d_ecnt = (uint32_t *)h->ar_csr[CSR_ECNT].p;
         return DBG_OK;
     };
     uint64_t q_cap = n_rec + 1024;
@@ -4374,12 +3771,12 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
     for (int attempt = 0; attempt < 3 + extra_attempts; ++attempt) {
         CHK(ensure_node_arrays());
         for (int set = 0; set < 2; ++set) {
-            CHK(buf_ensure(h, h->ar_q[set][0], q_cap * 8));
-            CHK(buf_ensure(h, h->ar_q[set][2], q_cap * 4));
-            if (shard_bits || h->resolve_sorted) CHK(buf_ensure(h, h->ar_q[set][1], q_cap * 8));
-            qk[set] = (uint64_t *)h->ar_q[set][0].p;
-            qm[set] = (uint64_t *)h->ar_q[set][1].p;
-            qc[set] = (uint32_t *)h->ar_q[set][2].p;
+            CHK(buf_ensure(h, h->ar_q[set][Q_KEY], q_cap * 8));
+            CHK(buf_ensure(h, h->ar_q[set][Q_COL], q_cap * 4));
+            if (shard_bits || h->resolve_sorted) CHK(buf_ensure(h, h->ar_q[set][Q_AUX], q_cap * 8));
+            qk[set] = (uint64_t *)h->ar_q[set][Q_KEY].p;
+            qm[set] = (uint64_t *)h->ar_q[set][Q_AUX].p;
+            qc[set] = (uint32_t *)h->ar_q[set][Q_COL].p;
             if (!shard_bits && !h->resolve_sorted) break;  // the second set is the output of the owner split / the target grouping
         }
         Timer t(h->stream);
@@ -4493,10 +3890,10 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
             HIPCHK(h, hipMemcpyAsync(sh.q_cnt.data(), o_cnt, (size_t)nsh * 8, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipStreamSynchronize(h->stream));
             // park keys and CSR positions (grouped by owner): the exchange reads them, the next build reuses ar_q
-            CHK(buf_ensure(h, h->ar_shard[0], n_q * 8));
-            CHK(buf_ensure(h, h->ar_shard[3], n_q * 4));
-            HIPCHK(h, hipMemcpyAsync(h->ar_shard[0].p, qk[1], n_q * 8, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHK(h, hipMemcpyAsync(h->ar_shard[3].p, qc[1], n_q * 4, hipMemcpyDeviceToDevice, h->stream));
+            CHK(buf_ensure(h, h->ar_shard[SHARD_Q_KEYS], n_q * 8));
+            CHK(buf_ensure(h, h->ar_shard[SHARD_Q_COL], n_q * 4));
+            HIPCHK(h, hipMemcpyAsync(h->ar_shard[0].p, qk[1], n_q * 8, hipMemcpyDeviceToDevice, h->stream));  // SHARD_Q_KEYS (the digit is part of HIPCHK's error text)
+            HIPCHK(h, hipMemcpyAsync(h->ar_shard[3].p, qc[1], n_q * 4, hipMemcpyDeviceToDevice, h->stream));  // SHARD_Q_COL
             root[0] = sh.q_start[my_shard];
             root[1] = sh.q_cnt[my_shard];
             sh.n_remote = n_q - root[1];
@@ -4571,8 +3968,8 @@ static int wsk_extract(dbg *h, int k, uint64_t **pk_out, uint64_t *w0[2], uint64
     unsigned long long *sc_dev = (unsigned long long *)h->d_scalars;
     uint64_t sc[8] = {0};
     const uint64_t pk_words = (h->n_bytes + 31) / 32;
-    CHK(buf_ensure(h, h->ar_wide[0], (pk_words + 8) * 8));
-    uint64_t *pk = (uint64_t *)h->ar_wide[0].p;
+    CHK(buf_ensure(h, h->ar_wide[WIDE_PACKED], (pk_words + 8) * 8));
+    uint64_t *pk = (uint64_t *)h->ar_wide[WIDE_PACKED].p;
     HIPCHK(h, hipMemsetAsync(pk + pk_words, 0, 8 * 8, h->stream));
     if (pk_words)
         hipLaunchKernelGGL(k_wpack, dim3(grid_for(pk_words, 256)), dim3(256), 0, h->stream, h->d_bases, h->n_bytes, pk_words, pk);
@@ -4594,12 +3991,12 @@ static int wsk_extract(dbg *h, int k, uint64_t **pk_out, uint64_t *w0[2], uint64
     for (int attempt = 0; attempt < 2; ++attempt) {
         const uint64_t rec_cap = seg_cap * n_wg;
         for (int set = 0; set < 2; ++set) {
-            CHK(buf_ensure(h, h->ar_rec[set][0], rec_cap * 8));
-            CHK(buf_ensure(h, h->ar_rec[set][1], rec_cap * 8));
-            CHK(buf_ensure(h, h->ar_rec[set][2], rec_cap * sizeof(ST)));
-            w0[set] = (uint64_t *)h->ar_rec[set][0].p;
-            w1[set] = (uint64_t *)h->ar_rec[set][1].p;
-            st[set] = (ST *)h->ar_rec[set][2].p;
+            CHK(buf_ensure(h, h->ar_rec[set][REC_W0], rec_cap * 8));
+            CHK(buf_ensure(h, h->ar_rec[set][REC_W1], rec_cap * 8));
+            CHK(buf_ensure(h, h->ar_rec[set][REC_ST], rec_cap * sizeof(ST)));
+            w0[set] = (uint64_t *)h->ar_rec[set][REC_W0].p;
+            w1[set] = (uint64_t *)h->ar_rec[set][REC_W1].p;
+            st[set] = (ST *)h->ar_rec[set][REC_ST].p;
         }
         for (uint32_t g = 0; g < n_wg; ++g) hseg[g] = (uint64_t)g * seg_cap;
         HIPCHK(h, hipMemcpyAsync(seg_start, hseg.data(), (size_t)n_wg * 8, hipMemcpyHostToDevice, h->stream));
@@ -4683,8 +4080,8 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
     const int where = P.where;
     const double est_distinct = P.est_distinct;
     // the records' bases, aligned, in bucket order (k_wsk_gather)
-    CHK(buf_ensure(h, h->ar_wide[2], (n_rec + 1) * 32));
-    uint4 *rec_b = (uint4 *)h->ar_wide[2].p;
+    CHK(buf_ensure(h, h->ar_wide[WIDE_REC_BASES], (n_rec + 1) * 32));
+    uint4 *rec_b = (uint4 *)h->ar_wide[WIDE_REC_BASES].p;
     {
         Timer t(h->stream);
         if (n_rec)
@@ -4724,27 +4121,27 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
     uint64_t *q_lo = nullptr, *q_hi = nullptr;
     uint32_t *q_col = nullptr;
     for (int attempt = 0; attempt < 3; ++attempt) {
-        CHK(buf_ensure(h, h->ar_node[0], node_cap * 8));
-        CHK(buf_ensure(h, h->ar_wide[5], node_cap * 8));
-        CHK(buf_ensure(h, h->ar_node[sizeof(ST) == 8 ? 1 : 7], node_cap * sizeof(ST)));
-        CHK(buf_ensure(h, h->ar_node[3], node_cap));
-        CHK(buf_ensure(h, h->ar_csr[3], (node_cap + 1) * 4));
-        CHK(buf_ensure(h, h->ar_csr[1], edge_cap * 4));
-        CHK(buf_ensure(h, h->ar_csr[2], edge_cap * 4));
-        CHK(buf_ensure(h, h->ar_q[0][0], q_cap * 8));
-        CHK(buf_ensure(h, h->ar_q[0][1], q_cap * 8));
-        CHK(buf_ensure(h, h->ar_q[0][2], q_cap * 4));
-        h->d_keys = (uint64_t *)h->ar_node[0].p;
-        h->d_keys_hi = (uint64_t *)h->ar_wide[5].p;
-        h->d_stamps_st = h->ar_node[sizeof(ST) == 8 ? 1 : 7].p;
+        CHK(buf_ensure(h, h->ar_node[NODE_KEYS], node_cap * 8));
+        CHK(buf_ensure(h, h->ar_wide[WIDE_KEYS_HI], node_cap * 8));
+        CHK(buf_ensure(h, h->ar_node[sizeof(ST) == 8 ? NODE_STAMPS64 : NODE_STAMPS32], node_cap * sizeof(ST)));
+        CHK(buf_ensure(h, h->ar_node[NODE_FLAGS], node_cap));
+        CHK(buf_ensure(h, h->ar_csr[CSR_ROWPTR32], (node_cap + 1) * 4));
+        CHK(buf_ensure(h, h->ar_csr[CSR_COL], edge_cap * 4));
+        CHK(buf_ensure(h, h->ar_csr[CSR_ECNT], edge_cap * 4));
+        CHK(buf_ensure(h, h->ar_q[SET_PING][Q_KEY], q_cap * 8));
+        CHK(buf_ensure(h, h->ar_q[SET_PING][Q_AUX], q_cap * 8));
+        CHK(buf_ensure(h, h->ar_q[SET_PING][Q_COL], q_cap * 4));
+        h->d_keys = (uint64_t *)h->ar_node[NODE_KEYS].p;
+        h->d_keys_hi = (uint64_t *)h->ar_wide[WIDE_KEYS_HI].p;
+        h->d_stamps_st = h->ar_node[sizeof(ST) == 8 ? NODE_STAMPS64 : NODE_STAMPS32].p;
         h->stamps_st_bytes = (int)sizeof(ST);
         h->d_stamps = sizeof(ST) == 8 ? (uint64_t *)h->d_stamps_st : nullptr;
-        h->d_flags = (uint8_t *)h->ar_node[3].p;
+        h->d_flags = (uint8_t *)h->ar_node[NODE_FLAGS].p;
         h->nodes_in_arena = true;
-        h->d_rowptr32 = (uint32_t *)h->ar_csr[3].p;
-        h->d_col = (uint32_t *)h->ar_csr[1].p;
-        h->d_ecnt = (uint32_t *)h->ar_csr[2].p;
-        q_lo = (uint64_t *)h->ar_q[0][0].p; q_hi = (uint64_t *)h->ar_q[0][1].p; q_col = (uint32_t *)h->ar_q[0][2].p;
+        h->d_rowptr32 = (uint32_t *)h->ar_csr[CSR_ROWPTR32].p;
+        h->d_col = (uint32_t *)h->ar_csr[CSR_COL].p;
+        h->d_ecnt = (uint32_t *)h->ar_csr[CSR_ECNT].p;
+        q_lo = (uint64_t *)h->ar_q[SET_PING][Q_KEY].p; q_hi = (uint64_t *)h->ar_q[SET_PING][Q_AUX].p; q_col = (uint32_t *)h->ar_q[SET_PING][Q_COL].p;
         Timer t(h->stream);
         HIPCHK(h, hipMemsetAsync(h->d_scalars, 0, 64 * 8, h->stream));
         HIPCHK(h, hipMemsetAsync(ranges, 0, n_buckets * sizeof(SkRange), h->stream));
@@ -4806,13 +4203,13 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
         const uint32_t *r_col = q_col;
         int stride = 1;
         if (shard_bits && n_q) {
-            CHK(buf_ensure(h, h->ar_shard[4], n_q * 8));
-            CHK(buf_ensure(h, h->ar_q[1][0], n_q * 8));
-            CHK(buf_ensure(h, h->ar_q[1][1], n_q * 8));
-            CHK(buf_ensure(h, h->ar_q[1][2], n_q * 4));
-            uint64_t *q_meta = (uint64_t *)h->ar_shard[4].p;
-            uint64_t *s_lo = (uint64_t *)h->ar_q[1][0].p, *s_meta = (uint64_t *)h->ar_q[1][1].p;
-            uint32_t *s_col = (uint32_t *)h->ar_q[1][2].p;
+            CHK(buf_ensure(h, h->ar_shard[SHARD_WQ_META], n_q * 8));
+            CHK(buf_ensure(h, h->ar_q[SET_PONG][Q_KEY], n_q * 8));
+            CHK(buf_ensure(h, h->ar_q[SET_PONG][Q_AUX], n_q * 8));
+            CHK(buf_ensure(h, h->ar_q[SET_PONG][Q_COL], n_q * 4));
+            uint64_t *q_meta = (uint64_t *)h->ar_shard[SHARD_WQ_META].p;
+            uint64_t *s_lo = (uint64_t *)h->ar_q[SET_PONG][Q_KEY].p, *s_meta = (uint64_t *)h->ar_q[SET_PONG][Q_AUX].p;
+            uint32_t *s_col = (uint32_t *)h->ar_q[SET_PONG][Q_COL].p;
             hipLaunchKernelGGL(k_wq_bucket, dim3(grid_for(n_q, 256)), dim3(256), 0, h->stream, q_lo, q_hi, q_meta, n_q, k, m);
             HIPCHK(h, hipGetLastError());
             CHK(buf_ensure(h, h->ar_misc[MISC_QUERY_SEGS], 512 * 16 + 16));
@@ -4829,19 +4226,19 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
             sh.q_cnt.assign(nsh, 0);
             HIPCHK(h, hipMemcpyAsync(sh.q_start.data(), o_start, (size_t)nsh * 8, hipMemcpyDeviceToHost, h->stream));
             HIPCHK(h, hipMemcpyAsync(sh.q_cnt.data(), o_cnt, (size_t)nsh * 8, hipMemcpyDeviceToHost, h->stream));
-            CHK(buf_ensure(h, h->ar_shard[0], n_q * 16));
-            CHK(buf_ensure(h, h->ar_shard[3], n_q * 4));
-            uint64_t *pairs = (uint64_t *)h->ar_shard[0].p;
+            CHK(buf_ensure(h, h->ar_shard[SHARD_Q_KEYS], n_q * 16));
+            CHK(buf_ensure(h, h->ar_shard[SHARD_Q_COL], n_q * 4));
+            uint64_t *pairs = (uint64_t *)h->ar_shard[SHARD_Q_KEYS].p;
             hipLaunchKernelGGL(k_wq_park, dim3(grid_for(n_q, 256)), dim3(256), 0, h->stream, n_q, s_lo, s_meta, q_hi, pairs);
             HIPCHK(h, hipGetLastError());
-            HIPCHK(h, hipMemcpyAsync(h->ar_shard[3].p, s_col, n_q * 4, hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(h, hipMemcpyAsync(h->ar_shard[3].p, s_col, n_q * 4, hipMemcpyDeviceToDevice, h->stream));  // SHARD_Q_COL (the digit is part of HIPCHK's error text)
             HIPCHK(h, hipStreamSynchronize(h->stream));
             const uint64_t mine_at = sh.q_start[my_shard], mine_n = sh.q_cnt[my_shard];
             sh.n_remote = n_q - mine_n;
             sh.q_cnt[my_shard] = 0;  // what is left in the lists is remote
             r_lo = pairs + 2 * mine_at;
             r_hi = r_lo + 1;
-            r_col = (const uint32_t *)h->ar_shard[3].p + mine_at;
+            r_col = (const uint32_t *)h->ar_shard[SHARD_Q_COL].p + mine_at;
             stride = 2;
             n_q = mine_n;
         }
@@ -5002,8 +4399,8 @@ static int shard_extract_wide(dbg *h, int k, int n_shards, uint64_t *send_counts
         if (d < n_shards) send_counts[d] = sc[48 + d];
         total += sc[48 + d];
     }
-    for (int a = 0; a < 3; ++a) CHK(buf_ensure(h, h->ar_rec[0][a], (total + 16) * 8));
-    uint64_t *lo = (uint64_t *)h->ar_rec[0][0].p, *hi = (uint64_t *)h->ar_rec[0][1].p, *st = (uint64_t *)h->ar_rec[0][2].p;
+    for (int a = 0; a < REC_COLS; ++a) CHK(buf_ensure(h, h->ar_rec[SET_PING][a], (total + 16) * 8));
+    uint64_t *lo = (uint64_t *)h->ar_rec[SET_PING][REC_W0].p, *hi = (uint64_t *)h->ar_rec[SET_PING][REC_W1].p, *st = (uint64_t *)h->ar_rec[SET_PING][REC_ST].p;
     HIPCHK(h, hipMemcpyAsync(cursor, offs, sizeof(offs), hipMemcpyHostToDevice, h->stream));
     if (tiles)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ws_extract<true>), dim3((unsigned)tiles), dim3(256), 0, h->stream, h->d_bases,
@@ -5033,13 +4430,13 @@ static int shard_build_wide(dbg *h, int k, int n_shards, int my_shard, const uin
     Timer t_total(h->stream);
     const uint64_t cap = std::max<uint64_t>(1024, ((uint64_t)((double)(n_rec + 1) / 0.7) + 1023) / 1024 * 1024);
     const uint64_t n_occ = cap / 32;
-    CHK(buf_ensure(h, h->ar_wide[1], cap * sizeof(WSlot)));
-    CHK(buf_ensure(h, h->ar_wide[2], cap * 16));
-    CHK(buf_ensure(h, h->ar_wide[3], cap));
-    CHK(buf_ensure(h, h->ar_wide[4], n_occ * 4));
-    WSlot *tab = (WSlot *)h->ar_wide[1].p;
-    uint32_t *tcnt = (uint32_t *)h->ar_wide[2].p, *word_rank = (uint32_t *)h->ar_wide[4].p;
-    uint8_t *occ = (uint8_t *)h->ar_wide[3].p;
+    CHK(buf_ensure(h, h->ar_wide[WIDE_TABLE], cap * sizeof(WSlot)));
+    CHK(buf_ensure(h, h->ar_wide[WIDE_TCNT], cap * 16));
+    CHK(buf_ensure(h, h->ar_wide[WIDE_OCC], cap));
+    CHK(buf_ensure(h, h->ar_wide[WIDE_WORD_RANK], n_occ * 4));
+    WSlot *tab = (WSlot *)h->ar_wide[WIDE_TABLE].p;
+    uint32_t *tcnt = (uint32_t *)h->ar_wide[WIDE_TCNT].p, *word_rank = (uint32_t *)h->ar_wide[WIDE_WORD_RANK].p;
+    uint8_t *occ = (uint8_t *)h->ar_wide[WIDE_OCC].p;
     HIPCHK(h, hipMemsetAsync(tab, 0xFF, cap * sizeof(WSlot), h->stream));
     HIPCHK(h, hipMemsetAsync(tcnt, 0, cap * 16, h->stream));
     HIPCHK(h, hipMemsetAsync(occ, 0, cap, h->stream));
@@ -5065,22 +4462,22 @@ static int shard_build_wide(dbg *h, int k, int n_shards, int my_shard, const uin
     CHK(exclusive_scan(h, n_occ, OccBytes32{occ}, word_rank, &total));
     if (total >= (1ull << 29) - 16) { h->err = "a shard holds at most 2^29 nodes"; return DBG_E_CAPACITY; }
     h->n_nodes = total;
-    CHK(buf_ensure(h, h->ar_node[0], total * 8));
-    CHK(buf_ensure(h, h->ar_node[1], total * 8));
-    CHK(buf_ensure(h, h->ar_node[2], total * 16));
-    CHK(buf_ensure(h, h->ar_node[3], total));
-    CHK(buf_ensure(h, h->ar_node[4], total));
-    CHK(buf_ensure(h, h->ar_node[5], total * 16));
-    CHK(buf_ensure(h, h->ar_node[6], total));
-    CHK(buf_ensure(h, h->ar_wide[5], total * 8));
-    h->d_keys = (uint64_t *)h->ar_node[0].p;
-    h->d_stamps = (uint64_t *)h->ar_node[1].p;
-    h->d_cnt = (uint32_t *)h->ar_node[2].p;
-    h->d_flags = (uint8_t *)h->ar_node[3].p;
-    h->d_order = (uint8_t *)h->ar_node[4].p;
-    h->d_succ = (uint32_t *)h->ar_node[5].p;
-    h->d_deg = (uint8_t *)h->ar_node[6].p;
-    h->d_keys_hi = (uint64_t *)h->ar_wide[5].p;
+    CHK(buf_ensure(h, h->ar_node[NODE_KEYS], total * 8));
+    CHK(buf_ensure(h, h->ar_node[NODE_STAMPS64], total * 8));
+    CHK(buf_ensure(h, h->ar_node[NODE_CNT], total * 16));
+    CHK(buf_ensure(h, h->ar_node[NODE_FLAGS], total));
+    CHK(buf_ensure(h, h->ar_node[NODE_ORDER], total));
+    CHK(buf_ensure(h, h->ar_node[NODE_SUCC], total * 16));
+    CHK(buf_ensure(h, h->ar_node[NODE_DEG], total));
+    CHK(buf_ensure(h, h->ar_wide[WIDE_KEYS_HI], total * 8));
+    h->d_keys = (uint64_t *)h->ar_node[NODE_KEYS].p;
+    h->d_stamps = (uint64_t *)h->ar_node[NODE_STAMPS64].p;
+    h->d_cnt = (uint32_t *)h->ar_node[NODE_CNT].p;
+    h->d_flags = (uint8_t *)h->ar_node[NODE_FLAGS].p;
+    h->d_order = (uint8_t *)h->ar_node[NODE_ORDER].p;
+    h->d_succ = (uint32_t *)h->ar_node[NODE_SUCC].p;
+    h->d_deg = (uint8_t *)h->ar_node[NODE_DEG].p;
+    h->d_keys_hi = (uint64_t *)h->ar_wide[WIDE_KEYS_HI].p;
     h->nodes_in_arena = true;
     hipLaunchKernelGGL(k_wgather, dim3(grid_for(n_occ * 32, 256)), dim3(256), 0, h->stream, tab, tcnt, occ, word_rank, n_occ,
                        h->d_keys, h->d_keys_hi, h->d_stamps, h->d_cnt, h->d_flags, 1);
@@ -5122,10 +4519,10 @@ static int shard_extract_wsk(dbg *h, int k, int n_shards, uint64_t *send_counts,
     // writes next to it -- into the unsplit stamps' array, which level 1 has read by then
     uint32_t *st_out = sizeof(ST) == 4 ? (uint32_t *)st[1] : (uint32_t *)st[0];
     if (n_parts > 1) {  // what travels (meta words, stamps; the gathered bases below) keeps buffers of its own per part
-        CHK(buf_ensure(h, h->ar_part[part][1], (n_rec + 16) * 8));
-        CHK(buf_ensure(h, h->ar_part[part][2], (n_rec + 16) * 4));
-        w1[1] = (uint64_t *)h->ar_part[part][1].p;
-        st_out = (uint32_t *)h->ar_part[part][2].p;
+        CHK(buf_ensure(h, h->ar_part[part][REC_W1], (n_rec + 16) * 8));
+        CHK(buf_ensure(h, h->ar_part[part][REC_ST], (n_rec + 16) * 4));
+        w1[1] = (uint64_t *)h->ar_part[part][REC_W1].p;
+        st_out = (uint32_t *)h->ar_part[part][REC_ST].p;
         if (sizeof(ST) == 4) st[1] = (ST *)st_out;  // (64-bit stamps stay in the record arena until the gather splits them)
     }
     const int nb1 = 512;
@@ -5137,7 +4534,7 @@ static int shard_extract_wsk(dbg *h, int k, int n_shards, uint64_t *send_counts,
                                     h->ar_misc[MISC_MS_OFFS], 0, nullptr, nullptr, h->host_seg_cnt.data())));
     std::vector<uint64_t> cnt(nb1);
     HIPCHK(h, hipMemcpyAsync(cnt.data(), c1_cnt, nb1 * 8, hipMemcpyDeviceToHost, h->stream));
-    dbg::Buf &b_rb = n_parts > 1 ? h->ar_part[part][0] : h->ar_wide[2];
+    dbg::Buf &b_rb = n_parts > 1 ? h->ar_part[part][REC_BASES] : h->ar_wide[WIDE_REC_BASES];
     CHK(buf_ensure(h, b_rb, (n_rec + 1) * 32));
     uint4 *rec_b = (uint4 *)b_rb.p;
     if constexpr (sizeof(ST) == 4) {
@@ -5185,15 +4582,15 @@ static int shard_build_wsk(dbg *h, int k, int n_shards, int my_shard, const uint
     free_build(h);
     uint64_t *w0[2], *w1[2], *st[2];
     for (int set = 0; set < 2; ++set) {
-        CHK(buf_ensure(h, h->ar_rec[set][0], (n_rec + 16) * 8));
-        CHK(buf_ensure(h, h->ar_rec[set][1], (n_rec + 16) * 8));
-        CHK(buf_ensure(h, h->ar_rec[set][2], (n_rec + 16) * 8));
-        w0[set] = (uint64_t *)h->ar_rec[set][0].p;
-        w1[set] = (uint64_t *)h->ar_rec[set][1].p;
-        st[set] = (uint64_t *)h->ar_rec[set][2].p;
+        CHK(buf_ensure(h, h->ar_rec[set][REC_W0], (n_rec + 16) * 8));
+        CHK(buf_ensure(h, h->ar_rec[set][REC_W1], (n_rec + 16) * 8));
+        CHK(buf_ensure(h, h->ar_rec[set][REC_ST], (n_rec + 16) * 8));
+        w0[set] = (uint64_t *)h->ar_rec[set][REC_W0].p;
+        w1[set] = (uint64_t *)h->ar_rec[set][REC_W1].p;
+        st[set] = (uint64_t *)h->ar_rec[set][REC_ST].p;
     }
-    CHK(buf_ensure(h, h->ar_shard[2], (n_rec + 16) * 8));
-    uint64_t *in_w0 = (uint64_t *)h->ar_shard[2].p;
+    CHK(buf_ensure(h, h->ar_shard[SHARD_RECV_COL], (n_rec + 16) * 8));
+    uint64_t *in_w0 = (uint64_t *)h->ar_shard[SHARD_RECV_COL].p;
     if (n_rec) hipLaunchKernelGGL(k_wsk_iota128, dim3(grid_for(n_rec, 256)), dim3(256), 0, h->stream, n_rec, in_w0);
     h->k = k;
     h->stats.n_records = n_rec;
@@ -5214,7 +4611,7 @@ static int shard_build_wsk(dbg *h, int k, int n_shards, int my_shard, const uint
     if (rc != DBG_OK) { const std::string keep = h->err; free_build(h); h->err = keep; return rc; }
     // successors owned by other shards: (lo, hi) pairs grouped by owner (two words per query)
     for (int d = 0; d < n_shards; ++d) { q_starts[d] = sh.q_start[d]; q_counts[d] = sh.q_cnt[d]; }
-    *d_q_keys = h->ar_shard[0].p;
+    *d_q_keys = h->ar_shard[SHARD_Q_KEYS].p;
     h->partial_graph = n_shards > 1;
     h->stats.ms_build_total = t_total.stop();
     return DBG_OK;
@@ -5239,12 +4636,12 @@ static int shard_extract_sk(dbg *h, int k, int n_shards, uint64_t *send_counts, 
     uint32_t n_seg = 0;
     CHK(sk_extract<ST>(h, k, w0, w1, st, &seg_start, &seg_cnt, &n_seg, &n_rec, part, n_parts));
     if (n_parts > 1) {  // the grouped records of every part keep buffers of their own: part p travels while part p + 1 is cut
-        CHK(buf_ensure(h, h->ar_part[part][0], (n_rec + 16) * 8));
-        CHK(buf_ensure(h, h->ar_part[part][1], (n_rec + 16) * 8));
-        CHK(buf_ensure(h, h->ar_part[part][2], (n_rec + 16) * sizeof(ST)));
-        w0[1] = (uint64_t *)h->ar_part[part][0].p;
-        w1[1] = (uint64_t *)h->ar_part[part][1].p;
-        st[1] = (ST *)h->ar_part[part][2].p;
+        CHK(buf_ensure(h, h->ar_part[part][REC_W0], (n_rec + 16) * 8));
+        CHK(buf_ensure(h, h->ar_part[part][REC_W1], (n_rec + 16) * 8));
+        CHK(buf_ensure(h, h->ar_part[part][REC_ST], (n_rec + 16) * sizeof(ST)));
+        w0[1] = (uint64_t *)h->ar_part[part][REC_W0].p;
+        w1[1] = (uint64_t *)h->ar_part[part][REC_W1].p;
+        st[1] = (ST *)h->ar_part[part][REC_ST].p;
     }
     // group by the 9 top bits of the bucket hash: owners are contiguous ranges of those 512 groups
     const int nb1 = 512;
@@ -5281,7 +4678,7 @@ extern "C" int dbg_shard_extract_part(dbg_t *h, int k, int n_shards, int part, i
                                       const void **d_w0, const void **d_w1, const void **d_st) {
     CHK(shard_args_ok(h, k, n_shards));
     if (!send_counts || !d_w0 || !d_w1 || !d_st || !h->d_offsets) { h->err = "bad argument / no reads"; return DBG_E_ARG; }
-    if (n_parts < 1 || n_parts > 4 || part < 0 || part >= n_parts) { h->err = "dbg_shard_extract_part: 1 <= n_parts <= 4, 0 <= part < n_parts"; return DBG_E_ARG; }
+    if (n_parts < 1 || n_parts > SHARD_EXTRACT_PARTS || part < 0 || part >= n_parts) { h->err = "dbg_shard_extract_part: 1 <= n_parts <= 4, 0 <= part < n_parts"; return DBG_E_ARG; }
     const bool st64 = h->n_bytes >= (1ull << 31) || h->shard_stamp64;
     HIPCHK(h, hipSetDevice(h->device));
     if (k > 31) {  // two-word k-mers: records by value (the LDS engine), 4-byte stamps on the wire (wider: dbg_wsk.h WREC_ST_HI)
@@ -5351,12 +4748,12 @@ extern "C" int dbg_shard_build(dbg_t *h, int k, int n_shards, int my_shard, cons
     // arena sets for 64-bit stamps
     uint64_t *w0[2], *w1[2], *st[2];
     for (int set = 0; set < 2; ++set) {
-        CHK(buf_ensure(h, h->ar_rec[set][0], (n_rec + 16) * 8));
-        CHK(buf_ensure(h, h->ar_rec[set][1], (n_rec + 16) * 8));
-        CHK(buf_ensure(h, h->ar_rec[set][2], (n_rec + 16) * 8));
-        w0[set] = (uint64_t *)h->ar_rec[set][0].p;
-        w1[set] = (uint64_t *)h->ar_rec[set][1].p;
-        st[set] = (uint64_t *)h->ar_rec[set][2].p;
+        CHK(buf_ensure(h, h->ar_rec[set][REC_W0], (n_rec + 16) * 8));
+        CHK(buf_ensure(h, h->ar_rec[set][REC_W1], (n_rec + 16) * 8));
+        CHK(buf_ensure(h, h->ar_rec[set][REC_ST], (n_rec + 16) * 8));
+        w0[set] = (uint64_t *)h->ar_rec[set][REC_W0].p;
+        w1[set] = (uint64_t *)h->ar_rec[set][REC_W1].p;
+        st[set] = (uint64_t *)h->ar_rec[set][REC_ST].p;
     }
     h->k = k;
     h->stats.n_records = n_rec;
@@ -5401,9 +4798,9 @@ extern "C" int dbg_shard_build(dbg_t *h, int k, int n_shards, int my_shard, cons
         CHK(buf_ensure(h, h->ar_misc[MISC_SEGMENTS], (uint64_t)n_shards * 16));
         uint64_t *seg_start = (uint64_t *)h->ar_misc[MISC_SEGMENTS].p, *seg_cnt = seg_start + n_shards;
         HIPCHK(h, hipMemcpyAsync(seg_start, seg.data(), seg.size() * 8, hipMemcpyHostToDevice, h->stream));
-        // the rebased stamps of the received records go to ar_shard[2]
-        CHK(buf_ensure(h, h->ar_shard[2], (n_rec + 16) * 8));
-        uint64_t *st64 = (uint64_t *)h->ar_shard[2].p;
+        // the rebased stamps of the received records go to ar_shard[SHARD_RECV_COL]
+        CHK(buf_ensure(h, h->ar_shard[SHARD_RECV_COL], (n_rec + 16) * 8));
+        uint64_t *st64 = (uint64_t *)h->ar_shard[SHARD_RECV_COL].p;
         HIPCHK(h, hipMemsetAsync(h->d_scalars + SC_L2_SUMS, 0, 16, h->stream));
         for (int r = 0; r < n_shards; ++r) {
             if (!recv_counts[r]) continue;
@@ -5427,7 +4824,7 @@ extern "C" int dbg_shard_build(dbg_t *h, int k, int n_shards, int my_shard, cons
     h->n_kmer_inst = n_inst;
     h->n_edge_inst = n_edge;
     for (int d = 0; d < n_shards; ++d) { q_starts[d] = sh.q_start[d]; q_counts[d] = sh.q_cnt[d]; }
-    *d_q_keys = h->ar_shard[0].p;
+    *d_q_keys = h->ar_shard[SHARD_Q_KEYS].p;
     h->partial_graph = n_shards > 1;
     h->stats.ms_build_total = t_total.stop();
     return DBG_OK;
@@ -5538,18 +4935,18 @@ extern "C" int dbg_import_graph(dbg_t *h, int k, int n_shards, const uint64_t *s
     // The big arrays are BORROWED, not copied (eight BASELINE-size shards are 140 GB of them: a second copy would
     // not fit): the caller keeps them alive and leaves them alone while this graph is in use.  Flags, rank bytes and
     // degrees are new (arena); successor ids are rewritten in place.
-    CHK(buf_ensure(h, h->ar_node[3], n));
-    CHK(buf_ensure(h, h->ar_node[4], n));
-    CHK(buf_ensure(h, h->ar_node[6], n));
+    CHK(buf_ensure(h, h->ar_node[NODE_FLAGS], n));
+    CHK(buf_ensure(h, h->ar_node[NODE_ORDER], n));
+    CHK(buf_ensure(h, h->ar_node[NODE_DEG], n));
     h->d_keys = (uint64_t *)d_keys;
     h->d_stamps = (uint64_t *)d_stamps;
     h->d_cnt = (uint32_t *)d_counts;
-    h->d_flags = (uint8_t *)h->ar_node[3].p;
-    h->d_order = (uint8_t *)h->ar_node[4].p;
-    h->d_deg = (uint8_t *)h->ar_node[6].p;
+    h->d_flags = (uint8_t *)h->ar_node[NODE_FLAGS].p;
+    h->d_order = (uint8_t *)h->ar_node[NODE_ORDER].p;
+    h->d_deg = (uint8_t *)h->ar_node[NODE_DEG].p;
     if (wide) {
-        CHK(buf_ensure(h, h->ar_node[5], n * 16));
-        h->d_succ = (uint32_t *)h->ar_node[5].p;
+        CHK(buf_ensure(h, h->ar_node[NODE_SUCC], n * 16));
+        h->d_succ = (uint32_t *)h->ar_node[NODE_SUCC].p;
     } else {
         h->d_succ = (uint32_t *)d_succ;
     }
@@ -5560,8 +4957,8 @@ extern "C" int dbg_import_graph(dbg_t *h, int k, int n_shards, const uint64_t *s
         // same successor kernel as the single-GPU build (it also writes the rank bytes and the degrees).
         h->d_keys_hi = (uint64_t *)d_keys_hi;
         const uint64_t cap = (2 * n + 1024) / 1024 * 1024;  // half full
-        CHK(buf_ensure(h, h->ar_wide[1], cap * sizeof(WSlot)));
-        WSlot *tab = (WSlot *)h->ar_wide[1].p;
+        CHK(buf_ensure(h, h->ar_wide[WIDE_TABLE], cap * sizeof(WSlot)));
+        WSlot *tab = (WSlot *)h->ar_wide[WIDE_TABLE].p;
         HIPCHK(h, hipMemsetAsync(tab, 0xFF, cap * sizeof(WSlot), h->stream));
         if (n) {
             hipLaunchKernelGGL(k_wnode_insert, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, n, h->d_keys, h->d_keys_hi, tab,
@@ -5606,7 +5003,7 @@ extern "C" int dbg_shard_apply(dbg_t *h, const void *d_answers) {
     Timer t(h->stream);
     HIPCHK(h, hipMemsetAsync(h->d_scalars, 0, 8, h->stream));
     // local successor ids already carry this shard's tag (k_sk_count / k_succ_resolve wrote them tagged)
-    const uint32_t *qcol = (const uint32_t *)h->ar_shard[3].p;
+    const uint32_t *qcol = (const uint32_t *)h->ar_shard[SHARD_Q_COL].p;
     for (int d = 0; d < sh.n_shards; ++d) {
         if (d == sh.my_shard || !sh.q_cnt[d]) continue;
         if (!d_answers) { h->err = "answers missing"; return DBG_E_ARG; }
@@ -5673,29 +5070,29 @@ static int buf_shrink(dbg *h, dbg::Buf &b, uint64_t bytes) {
 
 static int part_compact(dbg *sub, uint64_t n_dir_entries) {
     const uint64_t n = sub->n_nodes, ne = sub->n_edges;
-    const int st_slot = sub->stamps_st_bytes == 8 ? 1 : 7;
-    CHK(buf_shrink(sub, sub->ar_node[0], n * 8));
+    const int st_slot = sub->stamps_st_bytes == 8 ? NODE_STAMPS64 : NODE_STAMPS32;
+    CHK(buf_shrink(sub, sub->ar_node[NODE_KEYS], n * 8));
     if (sub->k > 31) {  // two-word k-mers: the high key words stay, the gathered record bases go
-        CHK(buf_shrink(sub, sub->ar_wide[5], n * 8));
-        sub->d_keys_hi = (uint64_t *)sub->ar_wide[5].p;
-        for (int i : {0, 1, 2, 3, 4}) buf_free(sub, sub->ar_wide[i]);
-        buf_free(sub, sub->ar_shard[4]);
+        CHK(buf_shrink(sub, sub->ar_wide[WIDE_KEYS_HI], n * 8));
+        sub->d_keys_hi = (uint64_t *)sub->ar_wide[WIDE_KEYS_HI].p;
+        for (int i : {WIDE_PACKED, WIDE_TABLE, WIDE_REC_BASES, WIDE_OCC, WIDE_WORD_RANK}) buf_free(sub, sub->ar_wide[i]);
+        buf_free(sub, sub->ar_shard[SHARD_WQ_META]);
     }
     CHK(buf_shrink(sub, sub->ar_node[st_slot], n * (uint64_t)sub->stamps_st_bytes));
-    CHK(buf_shrink(sub, sub->ar_node[3], n));
-    CHK(buf_shrink(sub, sub->ar_csr[3], (n + 1) * 4));
-    CHK(buf_shrink(sub, sub->ar_csr[1], ne * 4));
-    CHK(buf_shrink(sub, sub->ar_csr[2], ne * 4));
+    CHK(buf_shrink(sub, sub->ar_node[NODE_FLAGS], n));
+    CHK(buf_shrink(sub, sub->ar_csr[CSR_ROWPTR32], (n + 1) * 4));
+    CHK(buf_shrink(sub, sub->ar_csr[CSR_COL], ne * 4));
+    CHK(buf_shrink(sub, sub->ar_csr[CSR_ECNT], ne * 4));
     sub->dir_valid = false;  // a part's directory serves dbg_part_answer and the part queries (part_dir_ok), never dbg_lookup_nodes
     CHK(buf_shrink(sub, sub->ar_dir, n_dir_entries * sizeof(SkDirEnt)));
     CHK(buf_shrink(sub, sub->ar_misc[MISC_RANGES], sub->sk_n_ranges * sizeof(SkRange)));
-    sub->d_keys = (uint64_t *)sub->ar_node[0].p;
+    sub->d_keys = (uint64_t *)sub->ar_node[NODE_KEYS].p;
     sub->d_stamps_st = sub->ar_node[st_slot].p;
     if (sub->stamps_st_bytes == 8) sub->d_stamps = (uint64_t *)sub->d_stamps_st;
-    sub->d_flags = (uint8_t *)sub->ar_node[3].p;
-    sub->d_rowptr32 = (uint32_t *)sub->ar_csr[3].p;
-    sub->d_col = (uint32_t *)sub->ar_csr[1].p;
-    sub->d_ecnt = (uint32_t *)sub->ar_csr[2].p;
+    sub->d_flags = (uint8_t *)sub->ar_node[NODE_FLAGS].p;
+    sub->d_rowptr32 = (uint32_t *)sub->ar_csr[CSR_ROWPTR32].p;
+    sub->d_col = (uint32_t *)sub->ar_csr[CSR_COL].p;
+    sub->d_ecnt = (uint32_t *)sub->ar_csr[CSR_ECNT].p;
     for (auto &lvl : sub->ar_rec) for (auto &b : lvl) buf_free(sub, b);
     for (auto &lvl : sub->ar_q) for (auto &b : lvl) buf_free(sub, b);
     for (int i = 0; i < MISC_SLOTS; ++i)
@@ -5823,10 +5220,10 @@ static int multipass_parts(dbg *h, int k, int n_virtual, int v_first, int n_pass
         // level-2 output of this pass (one set: the presplit path writes set 0 only); freed again below
         uint64_t *pw0[2] = {nullptr, nullptr}, *pw1[2] = {nullptr, nullptr};
         ST *pst[2] = {nullptr, nullptr};
-        CHK(buf_ensure(sub, sub->ar_rec[0][0], (n_rec_p + 16) * 8));
-        CHK(buf_ensure(sub, sub->ar_rec[0][1], (n_rec_p + 16) * 8));
-        CHK(buf_ensure(sub, sub->ar_rec[0][2], (n_rec_p + 16) * sizeof(ST)));
-        pw0[0] = (uint64_t *)sub->ar_rec[0][0].p; pw1[0] = (uint64_t *)sub->ar_rec[0][1].p; pst[0] = (ST *)sub->ar_rec[0][2].p;
+        CHK(buf_ensure(sub, sub->ar_rec[SET_PING][REC_W0], (n_rec_p + 16) * 8));
+        CHK(buf_ensure(sub, sub->ar_rec[SET_PING][REC_W1], (n_rec_p + 16) * 8));
+        CHK(buf_ensure(sub, sub->ar_rec[SET_PING][REC_ST], (n_rec_p + 16) * sizeof(ST)));
+        pw0[0] = (uint64_t *)sub->ar_rec[SET_PING][REC_W0].p; pw1[0] = (uint64_t *)sub->ar_rec[SET_PING][REC_W1].p; pst[0] = (ST *)sub->ar_rec[SET_PING][REC_ST].p;
         ShardState &sh = shard_of(sub);
         sh.n_shards = n_virtual; sh.my_shard = v_first + p; sh.shard_bits = shard_bits; sh.k = k; sh.n_remote = 0;
         sh.q_start.assign(n_virtual, 0);
@@ -5870,14 +5267,14 @@ static int multipass_parts(dbg *h, int k, int n_virtual, int v_first, int n_pass
             ShardState &sh = shard_of(mp->part[p]);
             for (int q = 0; q < n_passes; ++q) if (q != p) max_q = std::max(max_q, sh.q_cnt[v_first + q]);
         }
-        CHK(buf_ensure(h, h->ar_shard[2], (max_q + 16) * 4));
-        uint32_t *ans = (uint32_t *)h->ar_shard[2].p;
+        CHK(buf_ensure(h, h->ar_shard[SHARD_PART_ANSWERS], (max_q + 16) * 4));
+        uint32_t *ans = (uint32_t *)h->ar_shard[SHARD_PART_ANSWERS].p;
         HIPCHK(h, hipMemsetAsync(h->d_scalars, 0, 8, h->stream));
         for (int p = 0; p < n_passes; ++p) {
             dbg *sub = mp->part[p];
             ShardState &sh = shard_of(sub);
-            const uint64_t *keys = (const uint64_t *)sub->ar_shard[0].p;
-            const uint32_t *qcol = (const uint32_t *)sub->ar_shard[3].p;
+            const uint64_t *keys = (const uint64_t *)sub->ar_shard[SHARD_Q_KEYS].p;
+            const uint32_t *qcol = (const uint32_t *)sub->ar_shard[SHARD_Q_COL].p;
             const uint64_t qw = pk ? 2 : 1;  // two-word k-mers: a query is a (lo, hi) pair
             for (int q = 0; q < n_passes; ++q) {
                 const int vq = v_first + q;
@@ -5889,8 +5286,8 @@ static int multipass_parts(dbg *h, int k, int n_virtual, int v_first, int n_pass
                                    ans, sh.q_cnt[vq], (uint8_t)vq, sub->d_col, mp->col_owner[p], (unsigned long long *)h->d_scalars);
             }
             if (n_virtual == n_passes) {  // nothing is owned elsewhere: the query lists are done with
-                buf_free(sub, sub->ar_shard[0]);
-                buf_free(sub, sub->ar_shard[3]);
+                buf_free(sub, sub->ar_shard[SHARD_Q_KEYS]);
+                buf_free(sub, sub->ar_shard[SHARD_Q_COL]);
             }
         }
         HIPCHK(h, hipGetLastError());
@@ -5927,11 +5324,11 @@ static int build_multipass_t(dbg *h, int k, int n_passes) {
         HIPCHK(h, hipMemcpyAsync(cnt.data(), c1_cnt, nb1 * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(start.data(), c1_start, nb1 * 8, hipMemcpyDeviceToHost, h->stream));
         h->stats.ms_partition = t.stop();
-        for (auto &b : h->ar_rec[0]) buf_free(h, b);  // the unsplit records; the split ones (set 1) stay parked for the passes
+        for (auto &b : h->ar_rec[SET_PING]) buf_free(h, b);  // the unsplit records; the split ones (set 1) stay parked for the passes
     }
     const uint64_t off0 = start[0], add0 = 0;
     int rc = multipass_parts<ST, ST>(h, k, n_passes, 0, n_passes, 1, cnt.data(), &off0, &add0, w0[1], w1[1], st[1]);
-    for (auto &b : h->ar_rec[1]) buf_free(h, b);  // every pass has read its slice of the parked records
+    for (auto &b : h->ar_rec[SET_PONG]) buf_free(h, b);  // every pass has read its slice of the parked records
     return rc;
 }
 
@@ -5954,12 +5351,12 @@ static int build_multipass_wsk(dbg *h, int k, int n_passes) {
         HIPCHK(h, hipMemcpyAsync(cnt.data(), c1_cnt, nb1 * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipMemcpyAsync(start.data(), c1_start, nb1 * 8, hipMemcpyDeviceToHost, h->stream));
         h->stats.ms_partition = t.stop();
-        for (auto &b : h->ar_rec[0]) buf_free(h, b);
+        for (auto &b : h->ar_rec[SET_PING]) buf_free(h, b);
     }
     const uint64_t off0 = start[0], add0 = 0;
     int rc = multipass_parts<ST, ST>(h, k, n_passes, 0, n_passes, 1, cnt.data(), &off0, &add0, w0[1], w1[1], st[1], pk);
-    for (auto &b : h->ar_rec[1]) buf_free(h, b);
-    buf_free(h, h->ar_wide[0]);
+    for (auto &b : h->ar_rec[SET_PONG]) buf_free(h, b);
+    buf_free(h, h->ar_wide[WIDE_PACKED]);
     return rc;
 }
 
@@ -6052,8 +5449,8 @@ extern "C" int dbg_shard_build_multipass_from(dbg_t *h, int k, int n_shards, int
     Timer t_total(h->stream);
     int rc;
     if (k > 31) {  // d_w0 holds the received bases, four words per record: the receiver's "packed reads", record i at position 128 i
-        CHK(buf_ensure(h, h->ar_shard[2], (n_rec + 16) * 8));
-        uint64_t *pos = (uint64_t *)h->ar_shard[2].p;
+        CHK(buf_ensure(h, h->ar_shard[SHARD_RECV_COL], (n_rec + 16) * 8));
+        uint64_t *pos = (uint64_t *)h->ar_shard[SHARD_RECV_COL].p;
         if (n_rec) hipLaunchKernelGGL(k_wsk_iota128, dim3(grid_for(n_rec, 256)), dim3(256), 0, h->stream, n_rec, pos);
         HIPCHK(h, hipGetLastError());
         rc = multipass_parts<uint64_t, uint32_t>(h, k, n_shards * n_passes, my_shard * n_passes, n_passes, n_senders, sender_bucket_counts,
@@ -6093,7 +5490,7 @@ extern "C" int dbg_part_queries(dbg_t *h, int part, uint64_t *q_starts, uint64_t
         q_starts[v] = v < (int)sh.q_start.size() ? sh.q_start[v] : 0;
         q_counts[v] = (mine || v >= (int)sh.q_cnt.size()) ? 0 : sh.q_cnt[v];
     }
-    *d_q_keys = sub->ar_shard[0].p;
+    *d_q_keys = sub->ar_shard[SHARD_Q_KEYS].p;
     return DBG_OK;
 }
 
@@ -6116,9 +5513,9 @@ extern "C" int dbg_part_apply(dbg_t *h, int part, int owner, const void *d_answe
     if (owner < 0 || owner >= mp->n_virtual || owner >= (int)sh.q_cnt.size()) { h->err = "no such owner"; return DBG_E_ARG; }
     const uint64_t n = sh.q_cnt[owner];
     if (!n) return DBG_OK;
-    if (!d_answers || !sub->ar_shard[3].p) { h->err = "no answers / the part's queries are gone (dbg_multipass_finish ran)"; return DBG_E_ARG; }
+    if (!d_answers || !sub->ar_shard[SHARD_Q_COL].p) { h->err = "no answers / the part's queries are gone (dbg_multipass_finish ran)"; return DBG_E_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
-    const uint32_t *qcol = (const uint32_t *)sub->ar_shard[3].p;
+    const uint32_t *qcol = (const uint32_t *)sub->ar_shard[SHARD_Q_COL].p;
     hipLaunchKernelGGL(k_apply_part, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, qcol + sh.q_start[owner],
                        (const uint32_t *)d_answers, n, (uint8_t)owner, sub->d_col, mp->col_owner[part],
                        (unsigned long long *)h->d_scalars);
@@ -6134,7 +5531,7 @@ extern "C" int dbg_multipass_finish(dbg_t *h) {
     uint64_t sc0 = 0;
     HIPCHK(h, hipMemcpyAsync(&sc0, h->d_scalars, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (dbg *sub : mp->part) { buf_free(sub, sub->ar_shard[0]); buf_free(sub, sub->ar_shard[3]); }
+    for (dbg *sub : mp->part) { buf_free(sub, sub->ar_shard[SHARD_Q_KEYS]); buf_free(sub, sub->ar_shard[SHARD_Q_COL]); }
     h->arena_freed = true;
     if (mp->n_passes > 1) pool_trim(h);
     if (sc0 & STATUS_REMOTE_UNRESOLVED) { h->err = "a successor owned by another rank came back unresolved"; return DBG_E_HIP; }
@@ -7771,181 +7168,5 @@ extern "C" int dbg_part_write_contigs_fasta(dbg_t *h, const char *path, int appe
     return rc;
 }
 
-// ==========================================================================================
-// Final-mode walk over a graph in parts (dbg_partfinal.h): every simple path of the contracted graph the caller built
-// from the ranked skeleton and the branch list.  One walker per thread, two passes like walk_impl: count per start,
-// scan, write.  The walkers of a wave interleave their stacks and bitmaps (level d of walker w at d * n_walkers + w).
-// ==========================================================================================
-struct PartFinal {
-    uint64_t n_contigs = 0, n_pieces = 0, n_chars = 0;
-    bool written = false;  // pass 1 ran: the arrays below hold the index (false: sizes only, the text exceeded max_chars)
-    uint32_t *start_ord = nullptr, *seq = nullptr, *piece_row = nullptr;
-    uint64_t *length = nullptr, *score = nullptr, *piece_off = nullptr;
-};
-
-static void part_final_free(MultiPass *mp) {
-    PartFinal *f = mp->fin;
-    if (!f) return;
-    dev_free(f->start_ord); dev_free(f->seq); dev_free(f->piece_row); dev_free(f->length); dev_free(f->score); dev_free(f->piece_off);
-    delete f;
-    mp->fin = nullptr;
-}
-
-__global__ __launch_bounds__(256) void k_fw_check(FwGraph g, uint64_t n, unsigned long long *err) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int f = fw_fault_at(g, i);
-    if (f) atomicOr(err, (unsigned long long)f);
-}
-
-// Walker w takes the starts w, w + n_walkers, ...; `budget` steps in all.  *status bit 0: a walker ran out of steps.
-__global__ __launch_bounds__(64) void k_fw_walk(FwGraph g, int k, int pass, uint64_t n_walkers, FwLevel *lv, uint32_t *bm, uint64_t budget,
-                                                uint64_t *per_ctg, uint64_t *per_piece, uint64_t *per_chr, const uint64_t *base_ctg,
-                                                const uint64_t *base_piece, FwOut o, unsigned long long *status) {
-    const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= n_walkers) return;
-    uint64_t steps = budget;
-    for (uint64_t i = w; i < g.n_starts; i += n_walkers) {
-        FwCount c{0, 0, 0};
-        if (!fw_walk_start(g, k, i, lv + w, bm + w, n_walkers, pass, pass ? base_ctg[i] : 0, pass ? base_piece[i] : 0, o, c, steps)) {
-            atomicOr(status, 1ull);
-            return;
-        }
-        if (pass == 0) { per_ctg[i] = c.contigs; per_piece[i] = c.pieces; per_chr[i] = c.chars; }
-    }
-}
-
-static std::string fw_fault_text(uint64_t f) {
-    std::string s;
-    auto add = [&](uint64_t bit, const char *what) { if (f & bit) s += std::string(s.empty() ? "" : "; ") + what; };
-    add(FW_BAD_KIND, "a kind is not one of the five");
-    add(FW_BAD_BRANCH, "a row that ends at a branch node names a branch row that is not below n_branch");
-    add(FW_BAD_SUCC, "a successor row of the branch table is neither below n_entries nor DBG_NO_NODE");
-    add(FW_BAD_START, "a start is not below n_entries");
-    return s;
-}
-
-extern "C" int dbg_part_final_walk(dbg_t *h, const dbg_final_skeleton_t *s, uint64_t max_chars, uint64_t *n_contigs, uint64_t *n_pieces,
-                                   uint64_t *n_chars) {
-    if (!h) return DBG_E_ARG;
-    if (n_contigs) *n_contigs = 0;
-    if (n_pieces) *n_pieces = 0;
-    if (n_chars) *n_chars = 0;
-    MultiPass *mp = (MultiPass *)h->multipass;
-    if (!mp || !h->k) { h->err = kNoParts; return DBG_E_ARG; }
-    part_final_free(mp);  // the result of an earlier walk goes, whatever becomes of this one
-    if (!s) { h->err = "dbg_part_final_walk: null skeleton"; return DBG_E_ARG; }
-    if (!max_chars) max_chars = 1ull << 30;
-    PartFinal *res = new PartFinal();
-    mp->fin = res;
-    if (!s->n_starts || !s->n_entries) { res->written = true; return DBG_OK; }
-    if (s->n_entries >= 0xFFFFFFFFull || s->n_branch >= 0xFFFFFFFFull || s->n_starts >= 0xFFFFFFFFull) {
-        h->err = "dbg_part_final_walk: more than 2^32 - 2 entries, branch nodes or starts";
-        part_final_free(mp);
-        return DBG_E_ARG;
-    }
-    if (!s->d_kind || !s->d_append || !s->d_score || !s->d_branch || !s->d_starts || (s->n_branch && (!s->d_succ_row || !s->d_succ_count))) {
-        h->err = "dbg_part_final_walk: null column";
-        part_final_free(mp);
-        return DBG_E_ARG;
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    const FwGraph g{(const uint8_t *)s->d_kind, (const uint64_t *)s->d_append, (const uint64_t *)s->d_score, (const uint32_t *)s->d_branch,
-                    (const uint32_t *)s->d_succ_row, (const uint32_t *)s->d_succ_count, (const uint32_t *)s->d_starts,
-                    s->n_entries, s->n_branch, s->n_starts};
-    const uint64_t ns = g.n_starts;
-    uint64_t *per[3] = {nullptr, nullptr, nullptr}, *base[2] = {nullptr, nullptr};
-    unsigned long long *status = nullptr;
-    FwLevel *lv = nullptr;
-    uint32_t *bm = nullptr;
-    auto body = [&]() -> int {
-        CHK(dev_alloc(h, &status, 1));
-        HIPCHK(h, hipMemsetAsync(status, 0, 8, h->stream));
-        // nothing below follows an index before this kernel has passed all of them
-        const uint64_t n_check = std::max(std::max(g.n_entries, g.n_branch * FW_FAN), ns);
-        hipLaunchKernelGGL(k_fw_check, dim3(grid_for(n_check, 256)), dim3(256), 0, h->stream, g, n_check, status);
-        HIPCHK(h, hipGetLastError());
-        uint64_t f = 0;
-        HIPCHK(h, hipMemcpyAsync(&f, status, 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (f) { h->err = "dbg_part_final_walk: " + fw_fault_text(f) + " (no walk ran)"; return DBG_E_ARG; }
-        for (auto &p : per) { CHK(dev_alloc(h, &p, ns)); HIPCHK(h, hipMemsetAsync(p, 0, ns * 8, h->stream)); }
-        for (auto &p : base) CHK(dev_alloc(h, &p, ns));
-        // walkers: the rule of walk_impl -- 4 GiB of stacks, 2^16 walkers at most
-        const uint64_t levels = g.n_branch + 1, bm_words = (g.n_branch + 31) / 32;
-        const uint64_t per_walker = levels * sizeof(FwLevel) + bm_words * 4;
-        uint64_t n_walkers = std::min<uint64_t>(ns, std::max<uint64_t>(1, (4ull << 30) / per_walker));
-        n_walkers = std::min<uint64_t>(n_walkers, 1u << 16);
-        CHK(dev_alloc(h, &lv, n_walkers * levels));
-        CHK(dev_alloc(h, &bm, n_walkers * bm_words));
-        HIPCHK(h, hipMemsetAsync(bm, 0, std::max<uint64_t>(n_walkers * bm_words, 1) * 4, h->stream));
-        FwOut o{};
-        auto launch = [&](int pass) {
-            hipLaunchKernelGGL(k_fw_walk, dim3(grid_for(n_walkers, 64)), dim3(64), 0, h->stream, g, h->k, pass, n_walkers, lv, bm,
-                               h->part_final_steps, per[0], per[1], per[2], base[0], base[1], o, status);
-        };
-        launch(0);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(&f, status, 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (f) {
-            h->err = "dbg_part_final_walk: a walker took more than " + std::to_string(h->part_final_steps) +
-                     " steps (option \"part_final_walk_steps\" raises the budget)";
-            return DBG_E_CAPACITY;
-        }
-        uint64_t n_ctg = 0, n_pc = 0, n_chr = 0;
-        CHK(exclusive_scan(h, ns, U64At{per[0]}, base[0], &n_ctg));
-        CHK(exclusive_scan(h, ns, U64At{per[1]}, base[1], &n_pc));
-        CHK(reduce_sum(h, ns, U64At{per[2]}, &n_chr));
-        res->n_contigs = n_ctg; res->n_pieces = n_pc; res->n_chars = n_chr;
-        if (n_contigs) *n_contigs = n_ctg;
-        if (n_pieces) *n_pieces = n_pc;
-        if (n_chars) *n_chars = n_chr;
-        if (n_ctg >= 0xFFFFFFFFull) { h->err = "dbg_part_final_walk: more than 2^32 - 2 contigs"; return DBG_E_CAPACITY; }
-        if (n_chr > max_chars) {
-            h->err = "dbg_part_final_walk: contig text exceeds max_chars (sizes are valid, nothing was written)";
-            return DBG_E_CAPACITY;
-        }
-        CHK(dev_alloc(h, &res->start_ord, n_ctg)); CHK(dev_alloc(h, &res->seq, n_ctg)); CHK(dev_alloc(h, &res->length, n_ctg));
-        CHK(dev_alloc(h, &res->score, n_ctg)); CHK(dev_alloc(h, &res->piece_off, n_ctg + 1)); CHK(dev_alloc(h, &res->piece_row, n_pc));
-        HIPCHK(h, hipMemcpyAsync(res->piece_off + n_ctg, &res->n_pieces, 8, hipMemcpyHostToDevice, h->stream));
-        o = FwOut{res->start_ord, res->seq, res->length, res->score, res->piece_off, res->piece_row, n_ctg, n_pc};
-        launch(1);  // the same walk: the bitmaps are clean again and the budget holds as it did
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        res->written = true;
-        return DBG_OK;
-    };
-    const int rc = body();
-    (void)hipStreamSynchronize(h->stream);
-    for (auto &p : per) dev_free(p);
-    for (auto &p : base) dev_free(p);
-    dev_free(status); dev_free(lv); dev_free(bm);
-    // a text above max_chars keeps its sizes (dbg_part_final_export then refuses); every other failure keeps nothing
-    if (rc != DBG_OK && !(rc == DBG_E_CAPACITY && res->n_chars > max_chars)) part_final_free(mp);
-    return rc;
-}
-
-extern "C" int dbg_part_final_export(dbg_t *h, uint32_t *start_ordinal, uint32_t *seq, uint64_t *length, uint64_t *score,
-                                     uint64_t *piece_off, uint32_t *piece_row) {
-    if (!h) return DBG_E_ARG;
-    MultiPass *mp = (MultiPass *)h->multipass;
-    if (!mp || !h->k) { h->err = kNoParts; return DBG_E_ARG; }
-    const PartFinal *f = mp->fin;
-    if (!f) { h->err = "dbg_part_final_export: dbg_part_final_walk must run first on this graph"; return DBG_E_ARG; }
-    if (!f->written) { h->err = "dbg_part_final_export: the last final walk kept its sizes only (text larger than max_chars)"; return DBG_E_ARG; }
-    const uint64_t n = f->n_contigs;
-    if (piece_off && !n) piece_off[0] = 0;
-    if (!n) return DBG_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (start_ordinal) HIPCHK(h, hipMemcpyAsync(start_ordinal, f->start_ord, n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (seq) HIPCHK(h, hipMemcpyAsync(seq, f->seq, n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (length) HIPCHK(h, hipMemcpyAsync(length, f->length, n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (score) HIPCHK(h, hipMemcpyAsync(score, f->score, n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (piece_off) HIPCHK(h, hipMemcpyAsync(piece_off, f->piece_off, (n + 1) * 8, hipMemcpyDeviceToHost, h->stream));
-    if (piece_row && f->n_pieces) HIPCHK(h, hipMemcpyAsync(piece_row, f->piece_row, f->n_pieces * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return DBG_OK;
-}
-
+#include "dbg_hip_partfinal.h"
 #include "dbg_nextk.h"  // dbg_build_from_walk: the next k's graph from the last walk
