@@ -369,6 +369,15 @@ int dbg_get_stats(dbg_t *h, dbg_stats_t *out);
  * "lookup_dir_calls" / "lookup_index_calls": dbg_lookup_nodes[_device] / dbg_score_sequences calls answered through the
  *   build's directory / through the sorted index; "lookup_index_builds": sorts that built such an index (one per graph).
  * "part_lookup_calls": dbg_part_lookup_nodes[_device] / dbg_part_score_sequences calls that ran a kernel.
+ * "count_events" and the other "count_*" counters describe the last build that ran an LDS count kernel (engine 0), not the
+ *   handle's life; a multi-pass parent or a shard built in parts reports the OR / the sums over its parts.  "count_events": OR
+ *   over the count launches of the rare paths a kernel took: 1 a bucket started in hash sub-ranges, 2 a table overflowed on a
+ *   whole bucket and the bucket was split, 4 a table overflowed inside a sub-range, 8 a wave's list of pending edges overflowed
+ *   (second-generation kernel, k <= 31), 16 a pass had more cross-range successors than its staging holds, 32 a wave deferred
+ *   more successor lookups than its list holds (third-generation kernel, second two-word kernel).
+ * "count_extra_ranges": sub-range passes of the last count launch (each adds a range and a directory block behind the buckets').
+ * "count_retries_query_cap" / "count_retries_node_cap" / "count_retries_counter16": count launches repeated because the query
+ *   list / the node and edge arrays sized from the estimate were too small / a 16-bit successor counter overflowed.
  * DBG_E_ARG for an unknown name. */
 int dbg_get_counter(dbg_t *h, const char *name, uint64_t *out);
 

@@ -99,9 +99,11 @@ class WalkBlock(C.Structure):
 # after reading keys -- filled only under option "resolve_count" 1 (tests), by a counting instantiation of the resolver
 # lookup_*: which way the query calls found their nodes (the build's directory / the sorted index) and how often such an
 # index was built
+# count_*: the rare paths the LDS count kernels took in the last build (EV_* below), its sub-range passes and repeated launches
 COUNTERS = ("extract_presplit_fallbacks", "extract_presplit_rehists", "resolve_direct_hits", "resolve_keyed",
             "refine_crowded", "pull_crowded", "lookup_index_builds", "lookup_dir_calls", "lookup_index_calls",
-            "part_lookup_calls")
+            "part_lookup_calls", "count_events", "count_extra_ranges", "count_retries_query_cap", "count_retries_node_cap",
+            "count_retries_counter16")
 
 
 class DbgError(RuntimeError):

@@ -29,6 +29,23 @@ enum Status : unsigned long long {
     STATUS_INCONSISTENT = 2048,     // a count kernel's two totals of a bucket disagree
 };
 
+// Event bits of word SC_COUNT_EVENTS of the scalar block: which of their rare paths the LDS count kernels (k_sk_count,
+// k_sk_count2, k_sk_count3, k_wsk_count, k_wsk_count2) took during one launch.  One thread raises its bit with one atomicOr
+// INSIDE the rare branch; the path of an ordinary bucket holds nothing of this.  The host ORs the word over the attempts of a
+// build (counter "count_events"); the tests built for these paths (tests/test_count_paths.py) prove with it that they ran.
+// The sites differ in small ways (`bit > 1` or cur_mask, a 32-bit OR on the low half, before or after the barrier): each is the
+// form that left VGPRs, SGPR spills and scratch of every instantiation as they were (tools/kernel_resources.sh); at 127 of 128
+// registers k_wsk_count2 tolerates two such atomics in its write phase, not three.
+constexpr int SC_COUNT_EVENTS = 7;  // words 0 (status), 4 (node | edge cursor), 5 (queries), 6 (extra ranges) are the kernels' own
+enum CountEvent : unsigned long long {
+    EV_PRESPLIT = 1,      // a bucket started in 2..16 hash sub-ranges (r_n > split_recs)
+    EV_SPLIT_ROOT = 2,    // a table overflowed on a bucket counted whole: two sub-ranges pushed
+    EV_SPLIT_PART = 4,    // a table overflowed inside a sub-range: split again
+    EV_PEND_OVER = 8,     // k_sk_count2: a wave listed more than PSEG pending edges, every (slot, base) word is scanned
+    EV_QUERY_SPILL = 16,  // a pass produced more queries than the LDS staging holds
+    EV_DEFER_SPILL = 32,  // k_sk_count3 / k_wsk_count2: a wave deferred more than DSEG edges, the rest are looked up in place
+};
+
 // One hash slot: 32 bytes, so the key probe, the stamp min and the successor
 // counter add of one record touch a single 128-byte line.
 struct __attribute__((aligned(32))) Slot {

@@ -2811,6 +2811,11 @@ extern "C" int dbg_get_counter(dbg_t *h, const char *name, uint64_t *out) {
     if (n == "lookup_dir_calls") { *out = h->lookup_dir_calls; return DBG_OK; }
     if (n == "lookup_index_calls") { *out = h->lookup_index_calls; return DBG_OK; }
     if (n == "part_lookup_calls") { *out = h->part_lookup_calls; return DBG_OK; }
+    if (n == "count_events") { *out = h->count_paths.events; return DBG_OK; }
+    if (n == "count_extra_ranges") { *out = h->count_paths.extra_ranges; return DBG_OK; }
+    if (n == "count_retries_query_cap") { *out = h->count_paths.retries_query_cap; return DBG_OK; }
+    if (n == "count_retries_node_cap") { *out = h->count_paths.retries_node_cap; return DBG_OK; }
+    if (n == "count_retries_counter16") { *out = h->count_paths.retries_counter16; return DBG_OK; }
     h->err = "unknown counter: " + n;
     return DBG_E_ARG;
 }
@@ -3768,6 +3773,7 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
     // "count_kernel" 3 runs it for 32-bit stamps too (A/B: tools/sweep.py)
     const bool use_count3 = use_count2 && ((sizeof(ST) == 8 && h->count_kernel_u64 == 3) || h->count_kernel == 3);
     int extra_attempts = 0;
+    h->count_paths = {};
     for (int attempt = 0; attempt < 3 + extra_attempts; ++attempt) {
         CHK(ensure_node_arrays());
         for (int set = 0; set < 2; ++set) {
@@ -3830,6 +3836,8 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
         if (use_count2 && n_rec) HIPCHK(h, hipMemcpyAsync(&q2, h->d_scalars + SK2_QUERY_CURSOR, 8, hipMemcpyDeviceToHost, h->stream));
         h->stats.ms_count = t.stop();
         if (use_count2 && n_rec) sc[5] = q2;  // k_sk_count2 keeps its query cursor on a cache line of its own
+        h->count_paths.events |= sc[SC_COUNT_EVENTS];
+        h->count_paths.extra_ranges = sc[6];
         if (h->phase_limit) { h->err = "ablation run (phase_limit set): timing only"; return DBG_E_ARG; }
         // buckets that had to be split by hash sub-range turn in-bucket successors into queries:
         // the usual bound (one query per record) no longer holds, retry with the safe one
@@ -3841,13 +3849,15 @@ static int sk_count_from_segments(dbg *h, int k, const uint64_t *seg_start, cons
             use_count2 = false;  // an edge seen more than 65 535 times: the kernel with 32-bit counters
             ++extra_attempts;
             again = true;
+            ++h->count_paths.retries_counter16;
         }
         if ((sc[0] & STATUS_NODE_EDGE_CAP) && (node_cap < node_cap_max || edge_cap < edge_cap_max) && !node_capacity_hint) {
             node_cap = node_cap_max;  // the estimate was low
             edge_cap = edge_cap_max;
             again = true;
+            ++h->count_paths.retries_node_cap;
         }
-        if ((sc[0] & STATUS_QUERY_CAP) && q_cap < n_edge_inst + 1024) { q_cap = n_edge_inst + 1024; again = true; }
+        if ((sc[0] & STATUS_QUERY_CAP) && q_cap < n_edge_inst + 1024) { q_cap = n_edge_inst + 1024; again = true; ++h->count_paths.retries_query_cap; }
         if (!again || attempt == 2 + extra_attempts) break;
     }
     if (sc[0] & STATUS_BUCKET_TOO_BIG) { h->err = "a bucket could not be split to fit the LDS table"; return DBG_E_CAPACITY; }
@@ -4120,6 +4130,7 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
     SkDirEnt *dirs = (SkDirEnt *)h->ar_dir.p;
     uint64_t *q_lo = nullptr, *q_hi = nullptr;
     uint32_t *q_col = nullptr;
+    h->count_paths = {};
     for (int attempt = 0; attempt < 3; ++attempt) {
         CHK(buf_ensure(h, h->ar_node[NODE_KEYS], node_cap * 8));
         CHK(buf_ensure(h, h->ar_wide[WIDE_KEYS_HI], node_cap * 8));
@@ -4171,10 +4182,12 @@ static int wsk_count(dbg *h, int k, const uint64_t *pk, const uint64_t *seg_star
         h->stats.count_launches = n_rec ? (uint64_t)(attempt + 1) : 0;
         HIPCHK(h, hipMemcpyAsync(sc, h->d_scalars, 64, hipMemcpyDeviceToHost, h->stream));
         h->stats.ms_count = t.stop();
+        h->count_paths.events |= sc[SC_COUNT_EVENTS];
+        h->count_paths.extra_ranges = sc[6];
         if (sc[0] & (STATUS_BUCKET_TOO_BIG | STATUS_RANGE_CAP | STATUS_COUNTER16 | STATUS_INCONSISTENT)) break;
         bool again = false;
-        if ((sc[0] & STATUS_NODE_EDGE_CAP) && (node_cap < node_cap_max || edge_cap < edge_cap_max)) { node_cap = node_cap_max; edge_cap = edge_cap_max; again = true; }
-        if ((sc[0] & STATUS_QUERY_CAP) && q_cap < n_edge_inst + 1024) { q_cap = n_edge_inst + 1024; again = true; }
+        if ((sc[0] & STATUS_NODE_EDGE_CAP) && (node_cap < node_cap_max || edge_cap < edge_cap_max)) { node_cap = node_cap_max; edge_cap = edge_cap_max; again = true; ++h->count_paths.retries_node_cap; }
+        if ((sc[0] & STATUS_QUERY_CAP) && q_cap < n_edge_inst + 1024) { q_cap = n_edge_inst + 1024; again = true; ++h->count_paths.retries_query_cap; }
         if (!again || attempt == 2) break;
     }
     if (sc[0] & STATUS_CLAIM_STUCK) { h->err = "two-word count kernel: an LDS slot claim never completed"; return DBG_E_HIP; }
@@ -5183,6 +5196,7 @@ static int multipass_parts(dbg *h, int k, int n_virtual, int v_first, int n_pass
     const int w = k - sk_m_for_k(k) + 1;
     double ms_count = 0, ms_part = h->stats.ms_partition, ms_succ = 0;
     uint64_t n_buckets = 0, n_queries = 0;
+    h->count_paths = {};
     std::vector<uint64_t> p_cnt((size_t)n_senders * bps), p_off(n_senders);
     for (int p = 0; p < n_passes; ++p) {
         dbg *sub = nullptr;
@@ -5257,6 +5271,11 @@ static int multipass_parts(dbg *h, int k, int n_virtual, int v_first, int n_pass
         ms_count += sub->stats.ms_count; ms_part += sub->stats.ms_partition; ms_succ += sub->stats.ms_succ;
         n_buckets += sub->stats.n_buckets >> shard_bits; n_queries += sub->stats.n_queries;
         h->stats.count_launches += sub->stats.count_launches;
+        h->count_paths.events |= sub->count_paths.events;
+        h->count_paths.extra_ranges += sub->count_paths.extra_ranges;
+        h->count_paths.retries_query_cap += sub->count_paths.retries_query_cap;
+        h->count_paths.retries_node_cap += sub->count_paths.retries_node_cap;
+        h->count_paths.retries_counter16 += sub->count_paths.retries_counter16;
     }
     // ---- successors owned by another part of this handle: the asker's queries are grouped by owner (ShardState), the
     //      owner's directory answers them

@@ -248,6 +248,10 @@ struct dbg {
     int shard_stamp64 = 0;    // option: dbg_shard_extract hands out 64-bit rank-local stamps even below 2 GiB of reads (tests)
     int extract_generic = 0;  // option: 1 = the window-minimum-through-LDS extraction kernels instead of the per-window register ones (A/B, tests)
     int extract_presplit = DBG_EXTRACT_PRESPLIT;  // option: dbg_build's extraction pre-splits its records by this many top bits of the bucket hash (0: off)
+    // What the LDS count kernels of the last build did beyond the ordinary pass (dbg_get_counter "count_*"): the event bits
+    // (CountEvent, dbg_device.h) OR-ed over the count launches, the sub-range passes of the last launch and the launches that
+    // were repeated, by reason.  A multi-pass parent or a shard holds the OR / the sums of its parts.
+    struct CountPaths { uint64_t events = 0, extra_ranges = 0, retries_query_cap = 0, retries_node_cap = 0, retries_counter16 = 0; } count_paths;
     uint64_t presplit_rehists = 0;  // builds whose level 1 took another width than the pre-split extraction counted for, so it ran its histogram pass (dbg_get_counter)
     uint64_t presplit_fallbacks = 0;  // builds whose pre-split extraction overflowed a sub-segment and ran again without the split (dbg_get_counter)
     uint64_t refine_crowded = 0, pull_crowded = 0;  // dbg_refine_edge_order / dbg_mark_pull_reads calls whose per-range kernel met a crowded range and fell back to the pass over the reads (dbg_get_counter)

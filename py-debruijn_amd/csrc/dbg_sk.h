@@ -935,6 +935,7 @@ __global__ __launch_bounds__((CntCfg<ST, CAP>::NT)) void k_sk_count(const uint64
             uint32_t parts = 2;
             while (parts < 16 && (uint64_t)parts * split_recs < r_n) parts <<= 1;
             if (threadIdx.x < parts) { s.stk_mask[threadIdx.x] = parts - 1; s.stk_val[threadIdx.x] = threadIdx.x; }
+            if (threadIdx.x == 0) atomicOr(&fresh_args(outp)->scalars[SC_COUNT_EVENTS], EV_PRESPLIT);
             stk_n = parts;
             root = false;
             __syncthreads();
@@ -1067,6 +1068,7 @@ __global__ __launch_bounds__((CntCfg<ST, CAP>::NT)) void k_sk_count(const uint64
                 if (threadIdx.x == 0) {
                     s.stk_mask[stk_n] = cur_mask | bit; s.stk_val[stk_n] = cur_val;
                     s.stk_mask[stk_n + 1] = cur_mask | bit; s.stk_val[stk_n + 1] = cur_val | bit;
+                    atomicOr(&fresh_args(outp)->scalars[SC_COUNT_EVENTS], bit > 1 ? EV_SPLIT_PART : EV_SPLIT_ROOT);
                 }
                 stk_n += 2;
                 __syncthreads();  // entries visible to every thread's pop
@@ -1278,6 +1280,7 @@ __global__ __launch_bounds__((CntCfg<ST, CAP>::NT)) void k_sk_count(const uint64
                     oq.q_col[qbase + i] = (uint32_t)(ebase + s.q_meta[i]);
                 }
                 if (nq > (uint32_t)CNT_QBUF) {  // rare: queries that did not fit the staging, straight from the registers
+                    if (threadIdx.x == 0) atomicOr(&oq.scalars[SC_COUNT_EVENTS], EV_QUERY_SPILL);
 #pragma unroll
                     for (int u = 0; u < NPT; ++u) {
                         const uint32_t li = threadIdx.x + u * CNT_NT;

@@ -192,6 +192,7 @@ __global__ __launch_bounds__(1024) void k_sk_count2(const SkCount2Args *__restri
         }
         if (fl_nq > (uint32_t)QS) {  // rare: queries beyond the staging go out one by one, key and row re-read from the node arrays
             const uint64_t kmask = (1ull << (2 * k)) - 1;
+            if (threadIdx.x == 0) atomicOr(&oq.scalars[SC_COUNT_EVENTS], EV_QUERY_SPILL);
 #pragma unroll
             for (int u = 0; u < NPT; ++u) {
                 const uint32_t mine = (fl_unst >> (u * 4)) & 15u;
@@ -231,6 +232,7 @@ __global__ __launch_bounds__(1024) void k_sk_count2(const SkCount2Args *__restri
             uint32_t parts = 2;
             while (parts < 16 && (uint64_t)parts * split_recs < r_n) parts <<= 1;
             if (threadIdx.x < parts) { s.stk_mask[threadIdx.x] = parts - 1; s.stk_val[threadIdx.x] = threadIdx.x; }
+            if (threadIdx.x == 0) atomicOr(&fresh_args2(argp)->out.scalars[SC_COUNT_EVENTS], EV_PRESPLIT);
             stk_n = parts;
             root = false;
             __syncthreads();
@@ -481,7 +483,7 @@ __global__ __launch_bounds__(1024) void k_sk_count2(const SkCount2Args *__restri
             }
             if (lane == 0) {
                 s.pend_cnt[wave] = (uint16_t)min(pcur, (uint32_t)PSEG);
-                if (pcur > (uint32_t)PSEG) s.pend_over = 1;
+                if (pcur > (uint32_t)PSEG) { s.pend_over = 1; atomicOr(&fresh_args2(argp)->out.scalars[SC_COUNT_EVENTS], EV_PEND_OVER); }
             }
             CNT_TICK(4);
             __syncthreads();
@@ -506,6 +508,7 @@ __global__ __launch_bounds__(1024) void k_sk_count2(const SkCount2Args *__restri
                 }
                 stk_n += 2;
                 __syncthreads();
+                if (threadIdx.x == 0) atomicOr(&fresh_args2(argp)->out.scalars[SC_COUNT_EVENTS], bit > 1 ? EV_SPLIT_PART : EV_SPLIT_ROOT);
                 continue;
             }
             // ---- the insert counted the bucket's nodes and edges: reserve node ids and CSR rows now; the pending lookups and

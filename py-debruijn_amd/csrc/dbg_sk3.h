@@ -157,6 +157,7 @@ __global__ __launch_bounds__(1024) void k_sk_count3(const SkCount2Args *__restri
                 asm volatile("" : "+v"(td));
                 s.stk_mask[td] = parts - 1;
                 s.stk_val[td] = td;
+                if (td == 0) atomicOr(&fresh_args2(argp)->out.scalars[SC_COUNT_EVENTS], EV_PRESPLIT);
             }
             stk_n = parts;
             root = false;
@@ -325,6 +326,7 @@ __global__ __launch_bounds__(1024) void k_sk_count3(const SkCount2Args *__restri
                 if (threadIdx.x == 0) {
                     s.stk_mask[stk_n] = cur_mask | bit; s.stk_val[stk_n] = cur_val;
                     s.stk_mask[stk_n + 1] = cur_mask | bit; s.stk_val[stk_n + 1] = cur_val | bit;
+                    atomicOr(&fresh_args2(argp)->out.scalars[SC_COUNT_EVENTS], cur_mask ? EV_SPLIT_PART : EV_SPLIT_ROOT);
                 }
                 stk_n += 2;
                 __syncthreads();
@@ -365,6 +367,7 @@ __global__ __launch_bounds__(1024) void k_sk_count3(const SkCount2Args *__restri
                     s.qs_key[qi] = sk;
                     s.qs_col[qi] = (uint32_t)e;
                 } else {
+                    if (qi == (uint32_t)QBUF) atomicOr(&ow.scalars[SC_COUNT_EVENTS], EV_QUERY_SPILL);
                     const unsigned long long g = atomicAdd(&ow.scalars[SK2_QUERY_CURSOR], 1ull);
                     if (g >= ow.q_cap || g >= 0xFFFFFFF0ull) { atomicOr(&ow.scalars[0], STATUS_QUERY_CAP); return; }
                     ow.q_key[g] = sk;
@@ -432,6 +435,7 @@ __global__ __launch_bounds__(1024) void k_sk_count3(const SkCount2Args *__restri
                             dseg[2 * at] = (uint16_t)((i << 2) | b);
                             dseg[2 * at + 1] = (uint16_t)er;
                         } else {
+                            if (at == (uint32_t)DSEG) atomicOr(&ow.scalars[SC_COUNT_EVENTS], EV_DEFER_SPILL);
                             resolve(i, b, ebase + er);
                         }
                         ++at;
@@ -470,7 +474,10 @@ __global__ __launch_bounds__(1024) void k_sk_count3(const SkCount2Args *__restri
                     const unsigned long long md = __ballot(direct);
                     if (md) {
                         unsigned long long g0 = 0;
-                        if (lane == 0) g0 = atomicAdd(&ow.scalars[SK2_QUERY_CURSOR], (unsigned long long)__popcll(md));
+                        if (lane == 0) {
+                            g0 = atomicAdd(&ow.scalars[SK2_QUERY_CURSOR], (unsigned long long)__popcll(md));
+                            atomicOr(&ow.scalars[SC_COUNT_EVENTS], EV_QUERY_SPILL);
+                        }
                         g0 = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(g0 >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)g0);
                         const unsigned long long g = g0 + lanes_below(md);
                         if (direct) {

@@ -646,6 +646,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count(const uint64_t *__restric
             while (parts < 16 && (uint64_t)parts * split_recs < r_n) parts <<= 1;
             __syncthreads();
             if (threadIdx.x < parts) { s.stk_mask[threadIdx.x] = parts - 1; s.stk_val[threadIdx.x] = threadIdx.x; }
+            if (threadIdx.x == 0) atomicOr(&wfresh_args(outp)->scalars[SC_COUNT_EVENTS], EV_PRESPLIT);
             stk_n = parts;
             root = false;
             __syncthreads();
@@ -814,6 +815,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count(const uint64_t *__restric
                 if (threadIdx.x == 0) {
                     s.stk_mask[stk_n] = cur_mask | bit; s.stk_val[stk_n] = cur_val;
                     s.stk_mask[stk_n + 1] = cur_mask | bit; s.stk_val[stk_n + 1] = cur_val | bit;
+                    atomicOr(&wfresh_args(outp)->scalars[SC_COUNT_EVENTS], bit > 1 ? EV_SPLIT_PART : EV_SPLIT_ROOT);
                 }
                 stk_n += 2;
                 __syncthreads();
@@ -1016,6 +1018,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count(const uint64_t *__restric
                     oq.q_col[qbase + i] = (uint32_t)(ebase + s.q_off[i]);
                 }
                 if (nq > (uint32_t)WCNT_QBUF) {  // rare: queries that did not fit the staging, straight from the registers
+                    if (threadIdx.x == 0) atomicOr(&oq.scalars[SC_COUNT_EVENTS], EV_QUERY_SPILL);
 #pragma unroll
                     for (int u = 0; u < NPT; ++u) {
                         const uint32_t li = threadIdx.x + u * WCNT_NT;

@@ -171,6 +171,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
                 asm volatile("" : "+v"(td));  // (see the directory write below)
                 s.stk_mask[td] = parts - 1;
                 s.stk_val[td] = td;
+                if (td == 0) atomicOr(&wfresh_args(outp)->scalars[SC_COUNT_EVENTS], EV_PRESPLIT);
             }
             stk_n = parts;
             root = false;
@@ -390,6 +391,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
                 if (threadIdx.x == 0) {
                     s.stk_mask[stk_n] = cur_mask | bit; s.stk_val[stk_n] = cur_val;
                     s.stk_mask[stk_n + 1] = cur_mask | bit; s.stk_val[stk_n + 1] = cur_val | bit;
+                    atomicOr(&wfresh_args(outp)->scalars[SC_COUNT_EVENTS], cur_mask ? EV_SPLIT_PART : EV_SPLIT_ROOT);
                 }
                 stk_n += 2;
                 __syncthreads();
@@ -435,7 +437,8 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
                     s.q_lo[qi] = sk.lo;
                     s.q_hi[qi] = sk.hi;
                     s.q_col[qi] = (uint32_t)e;
-                } else {  // rare: past the staging, one by one
+                } else {  // rare: past the staging, one by one (no event bit of its own: the deferred lookups below raise
+                          // EV_QUERY_SPILL with their first miss after this one)
                     const unsigned long long g = atomicAdd(&ow.scalars[5], 1ull);
                     if (g >= ow.q_cap || g >= 0xFFFFFFF0ull) { atomicOr(&ow.scalars[0], STATUS_QUERY_CAP); return; }
                     ow.q_lo[g] = sk.lo;
@@ -506,6 +509,7 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
                             dseg[2 * at] = (uint16_t)((i << 2) | b);
                             dseg[2 * at + 1] = (uint16_t)er;
                         } else {
+                            if (at == (uint32_t)DSEG) atomicOr((unsigned int *)&ow.scalars[SC_COUNT_EVENTS], (unsigned int)EV_DEFER_SPILL);
                             resolve(i, b, ebase + er);
                         }
                         ++at;
@@ -548,7 +552,10 @@ __global__ __launch_bounds__(WCNT_NT) void k_wsk_count2(const uint64_t *__restri
                     const unsigned long long md = __ballot(direct);
                     if (md) {
                         unsigned long long g0 = 0;
-                        if (lane == 0) g0 = atomicAdd(&ow.scalars[5], (unsigned long long)__popcll(md));
+                        if (lane == 0) {
+                            g0 = atomicAdd(&ow.scalars[5], (unsigned long long)__popcll(md));
+                            atomicOr((unsigned int *)&ow.scalars[SC_COUNT_EVENTS], (unsigned int)EV_QUERY_SPILL);
+                        }
                         g0 = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(g0 >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)g0);
                         const unsigned long long g = g0 + lanes_below(md);
                         if (direct) {

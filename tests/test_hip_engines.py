@@ -54,7 +54,9 @@ def build(reads2d, k, **opts):
     dict(engine=0, bucket_bits=12, lds_slots=2048),
     dict(engine=0, bucket_bits=18),
     dict(engine=0, bucket_bits=22),                  # three multisplit levels: 10 + 10 + 2 bits, all 22 of the bucket hash
-    dict(engine=0, bucket_bits=1, lds_slots=2048),   # forces LDS overflow splits
+    dict(engine=0, bucket_bits=1, lds_slots=2048),   # k_sk_count alone (2 048 slots keep k_sk_count2 out): two tables for ~10^5 k-mers
+                                                     # overflow and split from k = 13 on, not at k = 5 (4^5 k-mers); the other
+                                                     # kernels' splits and spills: test_count_paths, proven by their event bits
     dict(engine=0, stamp64=1),                       # 64-bit stamps (reads of 2 GiB and more, shards)
     dict(engine=0, stamp64=1, bucket_bits=3),
     dict(engine=0, stamp64=1, count_kernel_u64=1),   # ... on k_sk_count (lookups after the insert)
@@ -375,8 +377,10 @@ def test_resolver_with_queries_grouped_by_target(k, opts):
 @pytest.mark.parametrize("opts", [dict(), dict(bucket_bits=9), dict(bucket_bits=3), dict(bucket_bits=14)])
 def test_both_count_kernels_write_the_same_graph(opts):
     """k_sk_count (lookups after the insert) and k_sk_count2 (successor hints, pending list) on the same reads and geometry:
-    the same nodes, counts, flags and successors (compared in dict order) and the same cross-bucket query count.  bucket_bits = 3: eight buckets, every table overflows into hash
-    sub-ranges, so in-record successors land in other ranges (pending lookups that miss, queries beyond the LDS staging)."""
+    the same nodes, counts, flags and successors (compared in dict order) and the same cross-bucket query count.  bucket_bits = 3: eight buckets for
+    more than 8 x 4 096 distinct k-mers, so tables overflow and are counted in hash sub-ranges, where in-record successors land in
+    other ranges.  Whether the pending list or the query staging overflow on the way is not looked at here: test_count_paths
+    proves those paths, kernel by kernel, with the event bits."""
     reads = synth.reads_ascii(17, 80000, 8000, 100, 0.01)
     out = []
     for ck in (1, 2):
