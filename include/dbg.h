@@ -28,6 +28,12 @@
  *     generic path: up to 32 distinct bytes, codes in byte order (dbg_get_alphabet), 32 successor
  *     slots per node, k <= 63 (5 bits per character in one word up to k = 11, tables keyed by
  *     reference into the reads above); DBG_E_ALPHABET for more symbols.  k >= 64 is DBG_E_ARG, as on every path.
+ *   - that is the default and stays it: 'N' is a character, and k-mers that hold it are nodes.  dbg_split_reads is the
+ *     other choice: it replaces the resident reads by their pieces,
+ *       pieces(reads, fold) = [m for r in reads for m in re.findall(b"[ACGT]+", fold_acgt(r) if fold else r)]
+ *     where fold_acgt maps the four bytes a c g t to A C G T and nothing else.  Every other byte (>= 0x80 included) is
+ *     a cut; a read with no base (the empty read too) gives no piece; two reads never merge; no k-mer window spans a
+ *     cut.  The graph of the pieces is the reference run on that list, and it takes the 2-bit path.
  */
 #ifndef DBG_H
 #define DBG_H
@@ -49,7 +55,7 @@ typedef struct dbg dbg_t;
 
 #define DBG_ABI_VERSION 6 /* not raised for dbg_build_from_walks, nor for the query calls (dbg_lookup_nodes[_device],
                             * dbg_gather_nodes, dbg_score_sequences, dbg_part_lookup_nodes[_device],
-                            * dbg_part_score_sequences): they only add symbols, every earlier call and struct is
+                            * dbg_part_score_sequences), nor for dbg_split_reads / dbg_read_origins: they only add symbols, every earlier call and struct is
                             * unchanged, and tests/test_fasta_stream.py pins this number; a binding that needs a new
                             * call fails at symbol lookup on an older library */
 
@@ -209,6 +215,32 @@ int dbg_take_reads(dbg_t *h, const uint64_t *indices, uint64_t n, uint64_t *out_
                    uint64_t *n_chars);
 /* device pointers of the current read set (bases: n_bytes chars; offsets: u64[n_reads + 1]); valid until the reads change */
 int dbg_reads_device(dbg_t *h, const void **d_bases, uint64_t *n_bytes, const void **d_offsets, uint64_t *n_reads);
+/* Cuts the resident reads at every byte that is not A/C/G/T (the contract is in the header comment above) in one pass
+ * on the device, whichever call set them.  Like dbg_set_reads it drops any graph, walk and parts of the handle.
+ * DBG_SPLIT_FOLD_CASE folds a c g t to upper case first; any other flag bit is DBG_E_ARG.
+ * A read set with nothing to cut, to fold or to drop stays as it is (changed == 0): the same device pointers, no
+ * allocation, one read of the bases.  Folding alone happens in place where the handle owns the bases (changed == 1, the
+ * pointers stay).  Otherwise the pieces go to new buffers of exactly their size, the old ones are freed if the handle
+ * owns them, and dbg_get_sizes, dbg_copy_reads, dbg_take_reads, dbg_reads_device and dbg_export_pull_reads speak of
+ * the pieces from then on.  Buffers lent through dbg_set_reads_device are never written: a lent read set that has to
+ * change is replaced by buffers the handle owns. */
+#define DBG_SPLIT_FOLD_CASE 1u
+typedef struct dbg_split_stats {
+    uint64_t n_reads_in, n_bytes_in;
+    uint64_t n_reads_out, n_bytes_out; /* the pieces and their bases */
+    uint64_t n_cut_bytes;              /* n_bytes_in - n_bytes_out */
+    uint64_t n_folded_bytes;           /* kept bytes the fold changed */
+    uint64_t n_reads_changed;          /* reads that lose at least one byte */
+    uint64_t n_reads_emptied;          /* reads left without a piece (the empty reads among them) */
+    uint64_t changed;                  /* 0: the read set is the one that was there */
+    uint64_t peak_extra_device_bytes;  /* most device memory the call held beside the read set it found: new bases,
+                                        * offsets, origins (8 B + 16 B per piece) and 16 B per 64 KiB block of scan scratch */
+} dbg_split_stats_t;
+int dbg_split_reads(dbg_t *h, uint32_t flags, dbg_split_stats_t *out /* may be NULL */);
+/* Where piece j of the last dbg_split_reads came from: read_index[j] = the read (as numbered before the call), pos[j] =
+ * its first byte's position in that read; [n_reads] each, either may be NULL.  After a call that changed nothing: (j, 0).
+ * DBG_E_ARG before a dbg_split_reads on the current read set: every dbg_set_reads* forgets the origins. */
+int dbg_read_origins(dbg_t *h, uint64_t *read_index, uint64_t *pos);
 
 /* ---- a3 + a4: get_graph_from_reads (debruijn.py:98-147) + edge-count table (:213-222)
  *      -> node table, 4-way successor edges, CSR ------------------------------------ */

@@ -42,6 +42,7 @@ SYMBOLS = (
     "dbg_export_contig_texts", "dbg_write_contigs_fasta", "dbg_contig_output_stats",
     "dbg_part_set_skeleton", "dbg_part_contig_window", "dbg_part_export_contig_texts", "dbg_part_write_contigs_fasta",
     "dbg_part_final_walk", "dbg_part_final_export",
+    "dbg_split_reads", "dbg_read_origins",
 )
 
 
@@ -88,6 +89,23 @@ class ContigOutStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class SplitStats(C.Structure):
+    """dbg_split_stats_t: what the last dbg_split_reads did"""
+    _fields_ = [(n, C.c_uint64) for n in (
+        "n_reads_in", "n_bytes_in", "n_reads_out", "n_bytes_out", "n_cut_bytes", "n_folded_bytes", "n_reads_changed",
+        "n_reads_emptied", "changed", "peak_extra_device_bytes")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+SPLIT_FOLD_CASE = 1
+# granularities of the split kernels (csrc/dbg_readsplit.h: RS_WORD_BYTES, RS_BLOCK_BYTES, RS_ROUND_BYTES); tests aim at them
+SPLIT_WORD_BYTES = 64
+SPLIT_BLOCK_BYTES = 256 * 4 * SPLIT_WORD_BYTES
+SPLIT_ROUND_BYTES = 256 * SPLIT_BLOCK_BYTES
 
 
 class WalkBlock(C.Structure):
@@ -230,6 +248,8 @@ def load_library():
         "dbg_part_write_contigs_fasta": (C.c_int, [H, C.c_char_p, C.c_int, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, u64p]),
         "dbg_part_final_walk": (C.c_int, [H, C.POINTER(FinalSkeleton), C.c_uint64, u64p, u64p, u64p]),
         "dbg_part_final_export": (C.c_int, [H, vp, vp, vp, vp, vp, vp]),
+        "dbg_split_reads": (C.c_int, [H, C.c_uint32, C.POINTER(SplitStats)]),
+        "dbg_read_origins": (C.c_int, [H, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -358,6 +378,24 @@ class Graph:
         o = np.empty(s["n_reads"] + 1, dtype=np.uint64)
         self._chk(self._lib.dbg_copy_reads(self._h, _ptr(b), _ptr(o)))
         return b, o
+
+    def split_reads(self, fold_case=False):
+        """Cuts the resident reads at every byte that is not A/C/G/T (``fold_case``: a c g t count as A C G T and are
+        folded) -> the call's statistics.  The reads are then the pieces; ``changed == 0``: nothing had to move."""
+        out = SplitStats()
+        self.generation += 1
+        self._chk(self._lib.dbg_split_reads(self._h, SPLIT_FOLD_CASE if fold_case else 0, C.byref(out)))
+        if out.n_reads_out != out.n_reads_in or out.n_bytes_out != out.n_bytes_in:
+            self._keep = []  # lent buffers were replaced by the handle's own
+        return out.as_dict()
+
+    def read_origins(self):
+        """-> (read_index, pos) uint64 [n_reads]: the read each piece of the last ``split_reads`` came from and the
+        position of its first byte there."""
+        n = self.sizes()["n_reads"]
+        r, p = np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64)
+        self._chk(self._lib.dbg_read_origins(self._h, _ptr(r), _ptr(p)))
+        return r, p
 
     # ---- pipeline
     def build(self, k, table_capacity_hint=0):

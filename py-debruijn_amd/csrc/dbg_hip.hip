@@ -53,6 +53,7 @@
 #include "dbg_support.h"
 #include "dbg_wsk.h"
 #include "dbg_fasta.h"
+#include "dbg_readsplit.h"
 #include "dbg_lookup.h"
 #include "dbg_ctgout.h"
 #include "dbg_partfinal.h"
@@ -1026,6 +1027,8 @@ static void free_reads(dbg *h) {
     dev_free(h->d_lut); dev_free(h->d_alpha);
     h->alpha_known = false;
     h->n_bytes = h->n_reads = 0;
+    dev_free(h->d_org_read); dev_free(h->d_org_pos);
+    h->split_done = false;
 }
 
 extern "C" int dbg_abi_version(void) { return DBG_ABI_VERSION; }
@@ -1509,6 +1512,114 @@ extern "C" int dbg_copy_reads(dbg_t *h, char *bases, uint64_t *offsets) {
     if (bases && h->n_bytes) HIPCHK(h, hipMemcpyAsync(bases, h->d_bases, h->n_bytes, hipMemcpyDeviceToHost, h->stream));
     if (offsets && h->d_offsets)
         HIPCHK(h, hipMemcpyAsync(offsets, h->d_offsets, (h->n_reads + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return DBG_OK;
+}
+
+// ---- the resident reads cut at the bytes that are not bases (kernels: dbg_readsplit.h)
+extern "C" int dbg_split_reads(dbg_t *h, uint32_t flags, dbg_split_stats_t *out) {
+    if (!h) return DBG_E_ARG;
+    if (flags & ~DBG_SPLIT_FOLD_CASE) { h->err = "dbg_split_reads: unknown flag bits"; return DBG_E_ARG; }
+    if (!h->d_offsets) { h->err = "no reads set"; return DBG_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    free_build(h);
+    dev_free(h->d_org_read); dev_free(h->d_org_pos);
+    h->split_done = false;
+    const int fold = (flags & DBG_SPLIT_FOLD_CASE) ? 1 : 0;
+    const uint64_t n = h->n_bytes, n_reads = h->n_reads;
+    const uint64_t n_words = (n + RS_WORD_BYTES - 1) / RS_WORD_BYTES;
+    dbg_split_stats_t s{};
+    s.n_reads_in = s.n_reads_out = n_reads;
+    s.n_bytes_in = s.n_bytes_out = n;
+    RsTotals *d_tot = (RsTotals *)(h->d_scalars + 16);
+    RsTotals t{};
+    HIPCHK(h, hipMemsetAsync(d_tot, 0, sizeof(RsTotals), h->stream));
+    if (n_words) {
+        const unsigned grid = (unsigned)std::min<uint64_t>((n_words + 255) / 256, 8192);
+        hipLaunchKernelGGL(k_rs_count, dim3(grid), dim3(256), 0, h->stream, h->d_bases, n, h->d_startbits, fold, d_tot);
+        HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, hipMemcpyAsync(&t, d_tot, sizeof(RsTotals), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    const uint64_t n_kept = t.kept, n_pieces = t.starts;
+    s.n_cut_bytes = n - n_kept;
+    s.n_folded_bytes = t.folded;
+    auto alphabet_changed = [&]() { dev_free(h->d_lut); dev_free(h->d_alpha); h->alpha_known = false; };
+    if (s.n_cut_bytes == 0 && n_pieces == n_reads && (t.folded == 0 || h->own_bases)) {
+        // every read is one piece, whole: the read set stays where it is
+        if (t.folded) {
+            hipLaunchKernelGGL(k_rs_fold, dim3(grid_for((n + 15) / 16, 256)), dim3(256), 0, h->stream, h->d_bases, n);
+            HIPCHK(h, hipGetLastError());
+            HIPCHK(h, hipStreamSynchronize(h->stream));
+            alphabet_changed();
+            s.changed = 1;
+        }
+        h->split_done = true;
+        if (out) *out = s;
+        return DBG_OK;
+    }
+    // exact-size outputs next to the old read set
+    char *nb = nullptr;
+    uint64_t *noff = nullptr, *org_read = nullptr, *org_pos = nullptr;
+    auto fail = [&](int rc) { dev_free(nb); dev_free(noff); dev_free(org_read); dev_free(org_pos); return rc; };
+    const uint64_t nblk = (n + RS_BLOCK_BYTES - 1) / RS_BLOCK_BYTES;
+    int rc = dev_alloc(h, &nb, n_kept + 64);
+    if (rc == DBG_OK) rc = dev_alloc(h, &noff, n_pieces + 1);
+    if (rc == DBG_OK) rc = dev_alloc(h, &org_read, n_pieces);
+    if (rc == DBG_OK) rc = dev_alloc(h, &org_pos, n_pieces);
+    if (rc == DBG_OK) rc = buf_ensure(h, h->ar_scan, 2 * nblk * 8);
+    if (rc != DBG_OK) return fail(rc);
+    s.peak_extra_device_bytes = (n_kept + 64) + (n_pieces + 1) * 8 + std::max<uint64_t>(n_pieces, 1) * 16 + 2 * nblk * 8;
+    uint64_t *blk_kept = (uint64_t *)h->ar_scan.p, *blk_starts = blk_kept + nblk;
+    hipError_t e = hipMemsetAsync(nb + n_kept, 0, 64, h->stream);
+    if (e == hipSuccess && !nblk) e = hipMemsetAsync(noff, 0, 8, h->stream);
+    if (e == hipSuccess && nblk) {
+        hipLaunchKernelGGL(k_rs_blocks, dim3((unsigned)nblk), dim3(256), 0, h->stream, h->d_bases, n, h->d_startbits, fold,
+                           blk_kept, blk_starts);
+        hipLaunchKernelGGL(k_rs_carry, dim3(1), dim3(256), 0, h->stream, blk_kept, blk_starts, nblk);
+        hipLaunchKernelGGL(k_rs_write, dim3((unsigned)nblk), dim3(256), 0, h->stream, h->d_bases, n, h->d_startbits, fold,
+                           h->d_offsets, n_reads, blk_kept, blk_starts, nb, n_kept, noff, org_read, org_pos, n_pieces);
+        if (n_pieces)
+            hipLaunchKernelGGL(k_rs_read_stats, dim3(grid_for(n_pieces, 256)), dim3(256), 0, h->stream, h->d_offsets, noff,
+                               org_read, org_pos, n_pieces, d_tot);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&t, d_tot, sizeof(RsTotals), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { h->err = std::string("dbg_split_reads: ") + hipGetErrorString(e); return fail(DBG_E_HIP); }
+    s.n_reads_out = n_pieces;
+    s.n_bytes_out = n_kept;
+    s.n_reads_changed = t.nonempty_reads - t.intact;
+    s.n_reads_emptied = n_reads - t.with_piece;
+    s.changed = 1;
+    // swap: a borrowed buffer is let go unwritten, an owned one is freed
+    if (h->own_bases) dev_free(h->d_bases);
+    if (h->own_offsets) dev_free(h->d_offsets);
+    h->d_bases = nb; h->own_bases = true;
+    h->d_offsets = noff; h->own_offsets = true;
+    h->n_bytes = n_kept;
+    h->n_reads = n_pieces;
+    h->d_org_read = org_read;
+    h->d_org_pos = org_pos;
+    h->split_done = true;
+    alphabet_changed();
+    if (out) *out = s;
+    return make_startbits(h);
+}
+
+extern "C" int dbg_read_origins(dbg_t *h, uint64_t *read_index, uint64_t *pos) {
+    if (!h) return DBG_E_ARG;
+    if (!h->split_done) { h->err = "dbg_read_origins: dbg_split_reads has not run on the current read set"; return DBG_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->d_org_read) {  // nothing was cut: piece i is read i
+        for (uint64_t i = 0; i < h->n_reads; ++i) {
+            if (read_index) read_index[i] = i;
+            if (pos) pos[i] = 0;
+        }
+        return DBG_OK;
+    }
+    if (read_index && h->n_reads) HIPCHK(h, hipMemcpyAsync(read_index, h->d_org_read, h->n_reads * 8, hipMemcpyDeviceToHost, h->stream));
+    if (pos && h->n_reads) HIPCHK(h, hipMemcpyAsync(pos, h->d_org_pos, h->n_reads * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DBG_OK;
 }

@@ -148,6 +148,9 @@ struct dbg {
     uint64_t n_reads = 0;
     uint32_t *d_startbits = nullptr;  // bit p set: a read starts at byte p (bit n_bytes = sentinel)
     uint64_t startbits_words = 0;
+    // dbg_split_reads ran on the current read set; the origins of its pieces (both null: the identity, nothing was cut)
+    bool split_done = false;
+    uint64_t *d_org_read = nullptr, *d_org_pos = nullptr;
 
     // build
     int k = 0;

@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import bisect
 import os
+import re
 from collections.abc import ItemsView, Mapping, Sequence
 
 import numpy as np
@@ -75,17 +76,31 @@ class DeviceReads:
     reads of the whole file for every b.  chunk_bytes: size of the staging chunks of the streamed ingest (0: library
     default).  Either argument, or a file of ``STREAM_MIN_BYTES`` or more, takes the streamed ingest
     (``dbg_set_reads_fasta_file``); smaller files go over in one image.
+
+    non_acgt="keep" (default): every byte of a read is a character, as in the reference.  "split": after the ingest the
+    reads are cut at every byte that is not A/C/G/T (``acgt_pieces``; ``fold_case``: a c g t are folded to upper case
+    first) and the object lists the pieces; ``split_stats`` holds what the pass did, ``origins()`` where each piece came from.
     """
 
-    def __init__(self, fname, byte_range=None, chunk_bytes=None):
+    def __init__(self, fname, byte_range=None, chunk_bytes=None, non_acgt="keep", fold_case=False):
+        if non_acgt not in ("keep", "split"):
+            raise ValueError(f"non_acgt must be 'keep' or 'split', not {non_acgt!r}")
         self._graph = _dbg.Graph()
         if byte_range is None and chunk_bytes is None and os.path.getsize(fname) < STREAM_MIN_BYTES:
             self._graph.set_reads_fasta(fname)
         else:
             begin, end = (0, None) if byte_range is None else byte_range
             self._graph.set_reads_fasta_file(fname, begin, end, chunk_bytes or 0)
+        self.split_stats = self._graph.split_reads(fold_case=fold_case) if non_acgt == "split" else None
         self._n = self._graph.sizes()["n_reads"]
         self._host = None
+
+    def origins(self):
+        """non_acgt="split": (read_index, pos) uint64 arrays -- the read of the file (the line, headers not counted;
+        within the byte range) every piece came from and the position of its first byte in it."""
+        if self.split_stats is None:
+            raise ValueError("origins() needs non_acgt='split'")
+        return self._graph.read_origins()
 
     def _pull(self):
         if self._host is None:
@@ -125,9 +140,28 @@ class DeviceReads:
         return [text[int(a):int(b)] for a, b in zip(off[:-1], off[1:])]
 
 
-def read_reads_device(fname, byte_range=None, chunk_bytes=None):
-    """``read_reads`` (debruijn.py:22-32) without leaving the GPU; see DeviceReads (byte ranges, streamed ingest)."""
-    return DeviceReads(fname, byte_range, chunk_bytes)
+def read_reads_device(fname, byte_range=None, chunk_bytes=None, non_acgt="keep", fold_case=False):
+    """``read_reads`` (debruijn.py:22-32) without leaving the GPU; see DeviceReads (byte ranges, streamed ingest, the
+    split at bytes that are not bases)."""
+    return DeviceReads(fname, byte_range, chunk_bytes, non_acgt, fold_case)
+
+
+_ACGT_RUNS = re.compile(b"[ACGT]+")
+_FOLD_ACGT = bytes.maketrans(b"acgt", b"ACGT")
+
+
+def acgt_pieces(reads, fold_case=False):
+    """What ``split_reads`` / ``non_acgt="split"`` computes, in plain Python: the maximal runs of A/C/G/T of every read,
+    in order (``fold_case``: a c g t count as A C G T and come out folded).  Every other byte is a cut, a read without
+    a base gives nothing, two reads never merge.  str reads (one byte per character, latin-1) give str pieces."""
+    out = []
+    for r in reads:
+        text = isinstance(r, str)
+        b = r.encode("latin-1") if text else bytes(r)
+        if fold_case:
+            b = b.translate(_FOLD_ACGT)
+        out.extend(m.decode("latin-1") if text else m for m in _ACGT_RUNS.findall(b))
+    return out
 
 
 class _Vertices(dict):

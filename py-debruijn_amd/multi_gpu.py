@@ -120,7 +120,7 @@ def stamp_bases(dist, n_bytes, device):
     return bases
 
 
-def set_reads_fasta_shard(g, path, dist, chunk_bytes=0):
+def set_reads_fasta_shard(g, path, dist, chunk_bytes=0, non_acgt="keep", fold_case=False):
     """Sets this rank's share of the FASTA file at ``path`` as the reads of handle ``g`` (the input of sharded_build).
 
     Rank r of w takes the lines that start in bytes [r*S//w, (r+1)*S//w) of the S-byte file (a line that starts in
@@ -128,10 +128,18 @@ def set_reads_fasta_shard(g, path, dist, chunk_bytes=0):
     default): no rank reads or holds more than its slice and one line.  Every line belongs to exactly one rank, so the
     ranks' reads concatenated in rank order are the file's reads in file order, and the stamp bases of sharded_build
     (the byte offset of every rank's reads in that concatenation, as in ``stamp_bases``) give every node the global
-    stamp a single handle ingesting the whole file would give it.  Returns ``g``."""
+    stamp a single handle ingesting the whole file would give it.  Returns ``g``.
+
+    non_acgt="split": each rank then cuts its own lines at the bytes that are not A/C/G/T (``Graph.split_reads``,
+    ``fold_case`` as there) before any size is exchanged.  A piece never leaves its line, so the ranks' pieces in rank
+    order are the pieces of the whole file, and the same holds for the stamps."""
+    if non_acgt not in ("keep", "split"):
+        raise ValueError(f"non_acgt must be 'keep' or 'split', not {non_acgt!r}")
     w, r = dist.get_world_size(), dist.get_rank()
     size = os.path.getsize(path)
     g.set_reads_fasta_file(path, r * size // w, (r + 1) * size // w, chunk_bytes)
+    if non_acgt == "split":
+        g.split_reads(fold_case=fold_case)
     return g
 
 
