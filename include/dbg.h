@@ -199,6 +199,37 @@ int dbg_set_reads_fasta(dbg_t *h, const char *text, uint64_t n_text);
  * past the end of the file gives an empty read set. */
 int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t begin, uint64_t end, uint64_t chunk_bytes);
 int dbg_fasta_ingest_stats(dbg_t *h, dbg_ingest_stats_t *out);
+/* Reads of the FASTQ records whose header line's FIRST byte lies in [begin, end) of the file at `path` (end = UINT64_MAX:
+ * to EOF), streamed and parsed like dbg_set_reads_fasta_file (same arguments, same errors, any chunk_bytes from 1 up; it
+ * fills dbg_ingest_stats_t too, bytes_read being the bytes of the owned records).  Read i is the sequence line of record i,
+ * rstrip'ed; a record that starts inside the range is read to its end, even past `end`.
+ * The format is strict four-line FASTQ over universal-newline lines: trailing lines of the file that are empty after rstrip
+ * are ignored; the others come in groups of four: a header that begins with '@', the sequence (it must not begin with '@'
+ * or '+'; it may be empty), a separator that begins with '+', and a quality line of exactly the sequence's length after
+ * rstrip.  Only the file's last record may lack its quality line, and only if its read is empty.  Anything else is a
+ * malformed file: DBG_E_ARG, dbg_last_error names the 0-based record within the range and the kind (header, sequence
+ * start, separator, length mismatch, truncated record, quality byte), and the handle is left with no reads.
+ * The record start at or after a position is the first line start p >= position with t[p] == '@' whose second-next line
+ * begins with '+' (0 for position 0); on every file the whole-file parse accepts these are the true header lines, so the
+ * reads of [0, b) followed by those of [b, size) are the reads of the file for every b.
+ * min_quality q in 0..93 (more: DBG_E_ARG), Phred+33: with q > 0 base j of a read becomes the byte 'N' where
+ * qual[j] - 33 < q, whatever it was, and a quality byte outside 33..126 is malformed; lengths do not change, so
+ * dbg_split_reads afterwards cuts there and its origins count positions of the unmasked read.  With 0 the mask is off and
+ * quality bytes are never stored.  Device memory: the bases (half the owned bytes; twice that while a mask holds the
+ * qualities), the offsets and ~1.75 chunks of parse state. */
+int dbg_set_reads_fastq_file(dbg_t *h, const char *path, uint64_t begin, uint64_t end, uint64_t chunk_bytes, uint32_t min_quality);
+/* what the last dbg_set_reads_fastq_file did, beside dbg_ingest_stats_t */
+typedef struct dbg_fastq_stats {
+    uint64_t n_records;          /* records owned = reads */
+    uint64_t masked_bases;       /* bases the quality mask turned into 'N' (counted whatever the base was) */
+    uint64_t quality_bytes_held; /* size of the quality buffer while the mask needed it (0 with the mask off) */
+    uint64_t peak_device_bytes;  /* as in dbg_ingest_stats_t, the quality buffer included */
+    uint64_t min_quality;
+    uint64_t first_byte;         /* file position of the first owned record's header */
+    uint64_t end_byte;           /* file position after the last owned record (trailing white space of the file left out) */
+    double ms_mask;              /* device time of the mask pass */
+} dbg_fastq_stats_t;
+int dbg_fastq_ingest_stats(dbg_t *h, dbg_fastq_stats_t *out);
 /* Zero-copy: device pointers the caller keeps alive (16-byte aligned bases, u64 offsets[n_reads+1]). */
 int dbg_set_reads_device(dbg_t *h, const void *d_bases, uint64_t n_bytes, const void *d_offsets, uint64_t n_reads);
 /* Generate reads [first_read, first_read+n_reads) of the synthetic set on the device

@@ -2,8 +2,8 @@
 """Drop-in for the reference's ``II_assembleFromReads.py`` on the MI355X path.
 
 Same CLI (``-froot``), same ``{froot}/setting.json`` keys (score_cut, k_lowerlimit,
-k_upperlimit, threshold, source -- II_assembleFromReads.py:32-38; optionally non_acgt and
-fold_case, see ``debruijn.DeviceReads``), same stdout lines and
+k_upperlimit, threshold, source -- II_assembleFromReads.py:32-38; optionally non_acgt,
+fold_case, reads_format and min_quality, see ``debruijn.DeviceReads``), same stdout lines and
 the same append-mode FASTA output ``{froot}/{froot}.fasta`` with records
 ``>SEQUENCE_{i}_{k}mer`` (II_assembleFromReads.py:65-69).  Input is the FASTA surface the
 reference keeps commented out at II_assembleFromReads.py:53:
@@ -81,7 +81,11 @@ if __name__ == '__main__':
     threshold = setting['threshold']
     # II_assembleFromReads.py:53 with the FASTA parsed on the GPU (read_reads semantics, no Python string per read)
     # optional keys: "non_acgt": "split" cuts the reads at every byte that is not A/C/G/T, "fold_case" folds a c g t first
-    split = {key: setting[key] for key in ('non_acgt', 'fold_case') if key in setting}
-    sequences = read_reads_device(f'{froot}/input_reads.fasta', **split)
+    # "reads_format": "fastq" reads {froot}/input_reads.fastq instead; "min_quality": q turns bases below Phred q into N
+    split = {key: setting[key] for key in ('non_acgt', 'fold_case', 'min_quality') if key in setting}
+    reads_format = setting.get('reads_format', 'fasta')
+    if reads_format not in ('fasta', 'fastq'):
+        raise ValueError(f"setting.json: reads_format must be 'fasta' or 'fastq', not {reads_format!r}")
+    sequences = read_reads_device(f'{froot}/input_reads.{reads_format}', format=reads_format, **split)
     print(len(sequences))
     assemble(sequences, k_lowerlimit, k_upperlimit, threshold, out_path=f'{froot}/{froot}.fasta')

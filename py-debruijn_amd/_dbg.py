@@ -22,7 +22,8 @@ ABI_VERSION = 6
 # symbols declared in include/dbg.h; tests check that the library exports every one of them
 SYMBOLS = (
     "dbg_create", "dbg_destroy", "dbg_last_error", "dbg_abi_version", "dbg_set_option", "dbg_set_reads", "dbg_set_reads_fasta",
-    "dbg_set_reads_fasta_file", "dbg_fasta_ingest_stats", "dbg_set_reads_device",
+    "dbg_set_reads_fasta_file", "dbg_fasta_ingest_stats", "dbg_set_reads_fastq_file", "dbg_fastq_ingest_stats",
+    "dbg_set_reads_device",
     "dbg_synth_reads", "dbg_reads_checksum", "dbg_copy_reads", "dbg_reads_device", "dbg_build", "dbg_refine_edge_order", "dbg_export_orders",
     "dbg_get_alphabet", "dbg_export_keepmask", "dbg_export_dict_order",
     "dbg_prune", "dbg_remove_tips",
@@ -77,6 +78,16 @@ class IngestStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "bytes_read", "chunks", "chunk_bytes", "peak_device_bytes", "n_reads", "n_bases")] + [
         (n, C.c_double) for n in ("ms_total", "ms_io_wait", "ms_h2d", "ms_parse")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class FastqStats(C.Structure):
+    """dbg_fastq_stats_t: what the last dbg_set_reads_fastq_file did, beside IngestStats"""
+    _fields_ = [(n, C.c_uint64) for n in (
+        "n_records", "masked_bases", "quality_bytes_held", "peak_device_bytes", "min_quality", "first_byte", "end_byte")] + [
+        ("ms_mask", C.c_double)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -166,6 +177,8 @@ def load_library():
         "dbg_set_reads_fasta": (C.c_int, [H, vp, C.c_uint64]),
         "dbg_set_reads_fasta_file": (C.c_int, [H, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64]),
         "dbg_fasta_ingest_stats": (C.c_int, [H, C.POINTER(IngestStats)]),
+        "dbg_set_reads_fastq_file": (C.c_int, [H, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]),
+        "dbg_fastq_ingest_stats": (C.c_int, [H, C.POINTER(FastqStats)]),
         "dbg_set_reads_device": (C.c_int, [H, vp, C.c_uint64, vp, C.c_uint64]),
         "dbg_synth_reads": (C.c_int, [H, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]),
         "dbg_reads_checksum": (C.c_int, [H, u64p]),
@@ -343,6 +356,24 @@ class Graph:
         """What the last FASTA ingest did: bytes read, chunks, peak device bytes, ms in file reads / H2D / parse."""
         out = IngestStats()
         self._chk(self._lib.dbg_fasta_ingest_stats(self._h, C.byref(out)))
+        return out.as_dict()
+
+    def set_reads_fastq_file(self, path, begin=0, end=None, chunk_bytes=0, min_quality=0):
+        """Streams the FASTQ records of ``path`` whose header line starts in bytes [begin, end) (end None: to the end of
+        the file) like ``set_reads_fasta_file``; read i is the sequence of record i.  ``min_quality`` q in 1..93
+        (Phred+33): base j becomes ``N`` where ``qual[j] - 33 < q``; 0: quality bytes are never stored.  A malformed
+        file raises DbgError (DBG_E_ARG) naming record and kind and leaves the handle without reads."""
+        end = (1 << 64) - 1 if end is None else int(end)
+        if not 0 <= int(min_quality) < (1 << 32):
+            raise ValueError(f"min_quality must be 0..93, not {min_quality!r}")
+        self.generation += 1
+        self._chk(self._lib.dbg_set_reads_fastq_file(self._h, os.fsencode(path), int(begin), end, int(chunk_bytes),
+                                                     int(min_quality)))
+
+    def fastq_stats(self):
+        """What the last FASTQ ingest did beside ``ingest_stats()``: records, masked bases, quality bytes held, peak."""
+        out = FastqStats()
+        self._chk(self._lib.dbg_fastq_ingest_stats(self._h, C.byref(out)))
         return out.as_dict()
 
     def set_reads_device(self, bases_ptr, n_bytes, offsets_ptr, n_reads, keepalive=()):

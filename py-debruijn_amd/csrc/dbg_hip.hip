@@ -54,6 +54,7 @@
 #include "dbg_wsk.h"
 #include "dbg_fasta.h"
 #include "dbg_readsplit.h"
+#include "dbg_fastq.h"
 #include "dbg_lookup.h"
 #include "dbg_ctgout.h"
 #include "dbg_partfinal.h"
@@ -1453,6 +1454,297 @@ extern "C" int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t beg
 extern "C" int dbg_fasta_ingest_stats(dbg_t *h, dbg_ingest_stats_t *out) {
     if (!h || !out) return DBG_E_ARG;
     *out = h->ingest;
+    return DBG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// chunked FASTQ ingest from a file (kernels and the plain-C++ searches: dbg_fastq.h).  The staging machinery is the FASTA
+// stream's: two pinned buffers, the host reads chunk i+1 while chunk i is copied and parsed, the stream state stays on the
+// device (double-buffered: a chunk can run again after a buffer has grown), one host wait per chunk.  The host knows the
+// owned bytes [first record start, next range's first record start) before the first chunk, so no chunk looks for its end.
+// ------------------------------------------------------------------------------------------
+namespace {
+struct FastqStream : FastaStream {
+    struct HostView {
+        FqState st;
+        uint64_t flags, err;
+    };
+    HostView *fq_hv = nullptr;  // pinned: the state after the last chunk
+    uint32_t *d_wq = nullptr, *d_ls = nullptr, *d_lidx = nullptr, *d_blk_ls = nullptr;
+    FqState *d_fq_state = nullptr;
+    FqChunk *d_fq_chunk = nullptr;
+    uint64_t *d_err = nullptr;  // [0] the least (record, kind) of a malformed file [1] masked bases
+    char *qual = nullptr;       // quality bytes at the places of their bases (mask on), bases_cap + 64 bytes
+
+    explicit FastqStream(dbg *hh) : FastaStream(hh) {}
+    ~FastqStream() {
+        (void)hipStreamSynchronize(h->stream);
+        if (fq_hv) (void)hipHostFree(fq_hv);
+        dev_free(d_wq); dev_free(d_ls); dev_free(d_lidx); dev_free(d_blk_ls); dev_free(d_fq_state); dev_free(d_fq_chunk);
+        dev_free(d_err); dev_free(qual);
+    }
+};
+}  // namespace
+
+static int fastq_parse_chunk(FastqStream &fs, uint64_t n, int si) {
+    dbg *h = fs.h;
+    const uint64_t words = (n + 31) / 32, nblk = (words + FS_WPB - 1) / FS_WPB;
+    const FqState *in = fs.d_fq_state + si;
+    hipLaunchKernelGGL(k_fq_blocks, dim3((unsigned)nblk), dim3(256), 0, h->stream, fs.d_text, n, in, fs.d_blk_ls, fs.d_blk);
+    hipLaunchKernelGGL(k_fq_carry, dim3(1), dim3(256), 0, h->stream, fs.d_blk_ls, fs.d_blk, nblk, in, fs.d_fq_chunk);
+    hipLaunchKernelGGL(k_fq_count, dim3((unsigned)nblk), dim3(256), 0, h->stream, fs.d_text, n, in, (const uint32_t *)fs.d_blk_ls,
+                       (const uint8_t *)fs.d_blk, fs.d_wr, fs.d_wq, fs.d_ls, fs.d_lidx, fs.d_fq_chunk);
+    CHK(exclusive_scan(h, words, FqPopcPair{fs.d_wr, fs.d_wq}, fs.d_rank, (uint64_t *)nullptr));
+    const uint64_t *total = (const uint64_t *)h->ar_scan.p + std::max<uint64_t>((words + SCAN_TILE - 1) / SCAN_TILE, 1);
+    hipLaunchKernelGGL(k_fq_write, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, fs.d_text, n, in,
+                       (const FqChunk *)fs.d_fq_chunk, (const uint32_t *)fs.d_wr, (const uint32_t *)fs.d_wq,
+                       (const uint32_t *)fs.d_ls, (const uint32_t *)fs.d_lidx, (const uint64_t *)fs.d_rank, fs.bases, fs.qual,
+                       fs.bases_cap, fs.offsets, fs.off_cap, fs.d_flags, (unsigned long long *)fs.d_err);
+    hipLaunchKernelGGL(k_fq_finish, dim3(1), dim3(64), 0, h->stream, fs.d_text, n, in, (const FqChunk *)fs.d_fq_chunk, total,
+                       fs.d_fq_state + (si ^ 1));
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(&fs.fq_hv->st, fs.d_fq_state + (si ^ 1), sizeof(FqState), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&fs.fq_hv->flags, fs.d_flags, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&fs.fq_hv->err, fs.d_err, 8, hipMemcpyDeviceToHost, h->stream));
+    return DBG_OK;
+}
+
+// the file without its trailing white space: *out = position after the last non-space byte (0: there is none)
+static int fastq_trimmed_size(int fd, uint64_t size, uint64_t *out) {
+    std::vector<uint8_t> win(1 << 16);
+    uint64_t hi = size;
+    while (hi) {
+        const uint64_t lo = hi > win.size() ? hi - win.size() : 0;
+        if (pread_full(fd, (char *)win.data(), hi - lo, lo) != (int64_t)(hi - lo)) return -1;
+        const uint64_t keep = fq_trim(win.data(), hi - lo);
+        if (keep) { *out = lo + keep; return 0; }
+        hi = lo;
+    }
+    *out = 0;
+    return 0;
+}
+
+// the record start at or after `from` in the file that ends at `size` (its trailing white space trimmed): `size` if none
+static int fastq_record_start(int fd, uint64_t from, uint64_t size, uint64_t *out) {
+    *out = std::min(from, size);
+    if (from == 0 || from >= size) return 0;  // the file begins with a record
+    std::vector<uint8_t> win(1 << 16);
+    if (pread_full(fd, (char *)win.data(), 1, from - 1) != 1) return -1;
+    FqStartScan scan(win[0]);
+    for (uint64_t pos = from; pos < size; pos += win.size()) {
+        const uint64_t len = std::min<uint64_t>(win.size(), size - pos);
+        if (pread_full(fd, (char *)win.data(), len, pos) != (int64_t)len) return -1;
+        if (scan.feed(win.data(), len, pos)) { *out = scan.found; return 0; }
+    }
+    *out = size;
+    return 0;
+}
+
+extern "C" int dbg_set_reads_fastq_file(dbg_t *h, const char *path, uint64_t begin, uint64_t end, uint64_t chunk_bytes,
+                                        uint32_t min_quality) {
+    if (!h) return DBG_E_ARG;
+    using clk = std::chrono::steady_clock;
+    const auto t_call = clk::now();
+    if (!path) { h->err = "set_reads_fastq_file: no path"; return DBG_E_ARG; }
+    if (begin > end) {
+        h->err = "set_reads_fastq_file: begin " + std::to_string(begin) + " > end " + std::to_string(end);
+        return DBG_E_ARG;
+    }
+    if (min_quality > 93) { h->err = "set_reads_fastq_file: min_quality " + std::to_string(min_quality) + " > 93"; return DBG_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    FastqStream fs(h);
+    fs.fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fs.fd < 0) { h->err = std::string(path) + ": " + strerror(errno); return DBG_E_ARG; }
+    struct stat sb;
+    if (fstat(fs.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { h->err = std::string(path) + ": not a readable regular file"; return DBG_E_ARG; }
+    uint64_t size = 0, start = 0, stop = 0;
+    if (fastq_trimmed_size(fs.fd, (uint64_t)sb.st_size, &size) != 0 || fastq_record_start(fs.fd, begin, size, &start) != 0 ||
+        fastq_record_start(fs.fd, end, size, &stop) != 0) {
+        h->err = std::string(path) + ": read failed: " + strerror(errno);
+        return DBG_E_ARG;
+    }
+    const uint64_t chunk = chunk_bytes ? std::min(chunk_bytes, FS_MAX_CHUNK) : FS_DEFAULT_CHUNK;
+    free_build(h);
+    free_reads(h);
+    h->ingest = dbg_ingest_stats_t{};
+    h->ingest.chunk_bytes = chunk;
+    h->fastq = dbg_fastq_stats_t{};
+    h->fastq.min_quality = min_quality;
+    h->fastq.first_byte = start;
+    h->fastq.end_byte = stop;
+
+    // staging and parse state for chunks of up to `stage` bytes
+    const uint64_t range = stop - start;
+    fs.stage = std::max<uint64_t>(std::min(chunk, range), 1);
+    fs.words_cap = (fs.stage + 31) / 32;
+    fs.nblk_cap = (fs.words_cap + FS_WPB - 1) / FS_WPB;
+    for (auto &p : fs.pin) HIPCHK(h, hipHostMalloc((void **)&p, fs.stage, hipHostMallocDefault));
+    HIPCHK(h, hipHostMalloc((void **)&fs.fq_hv, sizeof(FastqStream::HostView), hipHostMallocDefault));
+    for (auto *e : {&fs.ev_copy[0], &fs.ev_copy[1], &fs.ev_t0, &fs.ev_done}) HIPCHK(h, hipEventCreate(e));
+    CHK(fs.alloc(&fs.d_text, fs.stage + 64));
+    CHK(fs.alloc(&fs.d_wr, fs.words_cap));
+    CHK(fs.alloc(&fs.d_wq, fs.words_cap));
+    CHK(fs.alloc(&fs.d_ls, fs.words_cap));
+    CHK(fs.alloc(&fs.d_lidx, fs.words_cap));
+    CHK(fs.alloc(&fs.d_rank, fs.words_cap));
+    CHK(fs.alloc(&fs.d_blk, fs.nblk_cap));
+    CHK(fs.alloc(&fs.d_blk_ls, fs.nblk_cap));
+    CHK(fs.alloc(&fs.d_fq_state, 2));
+    CHK(fs.alloc(&fs.d_fq_chunk, 1));
+    CHK(fs.alloc(&fs.d_flags, 1));
+    CHK(fs.alloc(&fs.d_err, 2));
+    fs.cur += (std::max<uint64_t>((fs.words_cap + SCAN_TILE - 1) / SCAN_TILE, 1) + 1) * 8;  // scan partials (handle arena)
+    fs.peak = std::max(fs.peak, fs.cur);
+    // a record's sequence is under half its bytes; the offsets start small and grow as records arrive
+    fs.bases_cap = range / 2;
+    CHK(fs.alloc(&fs.bases, fs.bases_cap + 64));
+    if (min_quality) CHK(fs.alloc(&fs.qual, fs.bases_cap + 64));
+    fs.off_cap = std::min<uint64_t>(1 << 16, range / 6 + 2);  // a record has six bytes or more
+    CHK(fs.alloc(&fs.offsets, fs.off_cap));
+    HIPCHK(h, hipMemsetAsync(fs.d_flags, 0, 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(fs.d_err, 0xFF, 8, h->stream));
+    HIPCHK(h, hipMemsetAsync(fs.d_err + 1, 0, 8, h->stream));
+    for (auto e : fs.ev_copy) HIPCHK(h, hipEventRecord(e, h->stream));  // "buffer free" holds from the start
+    fs.fq_hv->st = FqState{0, 0, 0, 0, '\n', 0};                        // a record start is a line start
+    fs.fq_hv->flags = 0;
+    fs.fq_hv->err = FQ_NO_ERROR;
+    HIPCHK(h, hipMemcpyAsync(fs.d_fq_state, &fs.fq_hv->st, sizeof(FqState), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+
+    double ms_io = 0;
+    auto read_chunk = [&](int b, uint64_t pos, uint64_t &len) -> int {
+        len = pos < stop ? std::min(fs.stage, stop - pos) : 0;
+        if (!len) return DBG_OK;
+        const auto t0 = clk::now();
+        const int64_t got = pread_full(fs.fd, fs.pin[b], len, pos);
+        ms_io += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+        if (got < 0) { h->err = std::string(path) + ": read failed: " + strerror(errno); return DBG_E_ARG; }
+        len = (uint64_t)got;  // short: the file ended early
+        h->ingest.bytes_read += len;
+        return DBG_OK;
+    };
+    auto malformed = [&](uint64_t key) {
+        h->err = "set_reads_fastq_file: " + std::string(path) + ": malformed FASTQ: record " + std::to_string(key >> 3) + ": " +
+                 fq_kind_name((uint32_t)(key & 7));
+        return DBG_E_ARG;
+    };
+    auto records_of = [](uint64_t n_lines) { return (n_lines + 2) / 4; };  // sequence lines among the lines so far
+    auto offsets_for = [&](uint64_t n_reads, uint64_t done, uint64_t at_least) {  // amortised: 1.5x, or the projection
+        const double proj = done ? (double)n_reads * std::max((double)range, (double)done) / (double)done * 1.05 + 1024 : 0;
+        return std::max<uint64_t>({at_least, fs.off_cap + fs.off_cap / 2, (uint64_t)proj});
+    };
+    auto timed_parse = [&](uint64_t n, int si, double &ms) -> int {
+        HIPCHK(h, hipEventRecord(fs.ev_t0, h->stream));
+        CHK(fastq_parse_chunk(fs, n, si));
+        HIPCHK(h, hipEventRecord(fs.ev_done, h->stream));
+        HIPCHK(h, hipEventSynchronize(fs.ev_done));
+        float c = 0;
+        (void)hipEventElapsedTime(&c, fs.ev_t0, fs.ev_done);
+        ms += c;
+        return DBG_OK;
+    };
+
+    uint64_t len[2] = {0, 0}, pos = start;
+    CHK(read_chunk(0, pos, len[0]));
+    FqState hs = fs.fq_hv->st;
+    int b = 0, si = 0;
+    double ms_h2d = 0, ms_parse = 0;
+    while (len[b] > 0) {
+        const uint64_t n = len[b], done = pos - start, recs = records_of(hs.n_lines);
+        if (done) {  // the offsets this chunk will likely need, at the record density seen so far
+            const uint64_t est = recs + (uint64_t)((double)recs * n / done * 1.25) + 64;
+            if (est + 1 > fs.off_cap) CHK(fs.grow(fs.offsets, fs.off_cap, offsets_for(recs, done, est + 1), recs, 0));
+        }
+        HIPCHK(h, hipEventRecord(fs.ev_t0, h->stream));
+        HIPCHK(h, hipMemcpyAsync(fs.d_text, fs.pin[b], n, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipEventRecord(fs.ev_copy[b], h->stream));
+        CHK(fastq_parse_chunk(fs, n, si));
+        HIPCHK(h, hipEventRecord(fs.ev_done, h->stream));
+        // the other buffer is free once its copy (chunk i-1) has completed: read chunk i+1 into it meanwhile
+        const uint64_t npos = pos + n;
+        HIPCHK(h, hipEventSynchronize(fs.ev_copy[b ^ 1]));
+        CHK(read_chunk(b ^ 1, npos, len[b ^ 1]));
+        HIPCHK(h, hipEventSynchronize(fs.ev_done));
+        float a = 0, c = 0;
+        (void)hipEventElapsedTime(&a, fs.ev_t0, fs.ev_copy[b]);
+        (void)hipEventElapsedTime(&c, fs.ev_copy[b], fs.ev_done);
+        ms_h2d += a;
+        ms_parse += c;
+        if (fs.fq_hv->err != FQ_NO_ERROR) return malformed(fs.fq_hv->err);  // every check in front of it has run: it is the first
+        if (records_of(fs.fq_hv->st.n_lines) + 1 > fs.off_cap) {  // more records than the estimate: grow and parse the chunk again
+            CHK(fs.grow(fs.offsets, fs.off_cap, offsets_for(recs, done + n, records_of(fs.fq_hv->st.n_lines) + 1), recs, 0));
+            CHK(timed_parse(n, si, ms_parse));
+        }
+        if (fs.fq_hv->flags) {
+            // Kept bytes past half the range: only a file whose quality lines are shorter than its reads, which the next
+            // header reports.  Until then the buffers grow and the chunk runs again; nothing was written out of bounds.
+            const uint64_t keep = std::min(fs.bases_cap, std::max(hs.cur_s, hs.cur_q) + hs.pend);
+            const uint64_t cap = std::max(std::max(hs.cur_s, hs.cur_q) + hs.pend + n, fs.bases_cap + fs.bases_cap / 2);
+            uint64_t qcap = fs.bases_cap;
+            CHK(fs.grow(fs.bases, fs.bases_cap, cap, keep, 64));
+            if (fs.qual) CHK(fs.grow(fs.qual, qcap, cap, keep, 64));
+            HIPCHK(h, hipMemsetAsync(fs.d_flags, 0, 8, h->stream));
+            CHK(timed_parse(n, si, ms_parse));
+            if (fs.fq_hv->flags) { h->err = "set_reads_fastq_file: packed bases overran their buffer (internal error)"; return DBG_E_HIP; }
+        }
+        hs = fs.fq_hv->st;
+        si ^= 1;
+        b ^= 1;
+        pos = npos;
+        ++h->ingest.chunks;
+    }
+    // the end of the range: whole records, or a last record of the file with an empty read and no quality line.  The
+    // pending white space of the last line is dropped (cur_s, cur_q do not count it).
+    const uint64_t n_reads = records_of(hs.n_lines), n_bases = hs.cur_s;
+    if ((hs.n_lines & 3) == 1 || (hs.n_lines & 3) == 2) return malformed((hs.n_lines >> 2) * 8 + FQ_E_TRUNCATED);
+    if (hs.cur_s != hs.cur_q) return malformed((n_reads - 1) * 8 + FQ_E_LENGTH);
+    HIPCHK(h, hipMemcpyAsync(fs.offsets + n_reads, &n_bases, 8, hipMemcpyHostToDevice, h->stream));
+    if (fs.qual) {
+        HIPCHK(h, hipEventRecord(fs.ev_t0, h->stream));
+        if (n_bases) {
+            hipLaunchKernelGGL(k_fq_mask, dim3(grid_for((n_bases + 15) / 16, 256)), dim3(256), 0, h->stream, fs.bases,
+                               (const char *)fs.qual, n_bases, min_quality, (const uint64_t *)fs.offsets, n_reads,
+                               (unsigned long long *)(fs.d_err + 1), (unsigned long long *)fs.d_err);
+            HIPCHK(h, hipGetLastError());
+        }
+        HIPCHK(h, hipEventRecord(fs.ev_done, h->stream));
+        uint64_t res[2] = {FQ_NO_ERROR, 0};
+        HIPCHK(h, hipMemcpyAsync(res, fs.d_err, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        float c = 0;
+        (void)hipEventElapsedTime(&c, fs.ev_t0, fs.ev_done);
+        h->fastq.ms_mask = c;
+        if (res[0] != FQ_NO_ERROR) return malformed(res[0]);
+        h->fastq.masked_bases = res[1];
+        h->fastq.quality_bytes_held = fs.bases_cap + 64;
+        fs.release(fs.qual, fs.bases_cap + 64);
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->d_bases = fs.bases;
+    h->own_bases = true;
+    h->d_offsets = fs.offsets;
+    h->own_offsets = true;
+    fs.bases = nullptr;
+    fs.offsets = nullptr;
+    h->n_bytes = n_bases;
+    h->n_reads = n_reads;
+    h->ingest.peak_device_bytes = fs.peak;
+    h->ingest.n_reads = n_reads;
+    h->ingest.n_bases = n_bases;
+    h->ingest.ms_io_wait = ms_io;
+    h->ingest.ms_h2d = ms_h2d;
+    h->ingest.ms_parse = ms_parse;
+    h->stats.ms_h2d = ms_h2d;
+    h->fastq.n_records = n_reads;
+    h->fastq.peak_device_bytes = fs.peak;
+    const int rc = make_startbits(h);
+    h->ingest.ms_total = std::chrono::duration<double, std::milli>(clk::now() - t_call).count();
+    return rc;
+}
+
+extern "C" int dbg_fastq_ingest_stats(dbg_t *h, dbg_fastq_stats_t *out) {
+    if (!h || !out) return DBG_E_ARG;
+    *out = h->fastq;
     return DBG_OK;
 }
 

@@ -300,7 +300,8 @@ struct dbg {
     uint64_t part_lookup_calls = 0;  // dbg_part_lookup_nodes[_device] / dbg_part_score_sequences calls that ran (dbg_get_counter)
 
     dbg_stats_t stats{};
-    dbg_ingest_stats_t ingest{};  // the last FASTA ingest
+    dbg_ingest_stats_t ingest{};  // the last FASTA or FASTQ ingest
+    dbg_fastq_stats_t fastq{};    // the last FASTQ ingest (dbg_set_reads_fastq_file)
     dbg_contig_out_stats_t ctgout{};  // the last streamed contig output (dbg_ctgout.h)
     uint64_t ctgout_chunk = 0;        // option "ctgout_chunk_bytes": window size where a call names none (0: CO_DEFAULT_CHUNK)
 };

@@ -31,7 +31,7 @@ import numpy as np
 
 import _dbg
 
-__all__ = ["Node", "read_reads", "read_reads_device", "DeviceReads", "construct_graph", "output_contigs",
+__all__ = ["Node", "read_reads", "read_fastq", "read_reads_device", "DeviceReads", "construct_graph", "output_contigs",
            "get_score_device", "score_sequences", "get_kmers", "get_graph_from_kmers"]
 
 
@@ -54,6 +54,61 @@ def read_reads(fname):
     """
     with open(fname, "r") as fh:
         return [line.rstrip() for line in fh.readlines() if line[0] != ">"]
+
+
+_FQ_SPACE = bytes([32, *range(9, 14), *range(28, 32)])  # str.isspace() over ASCII, as the FASTA path strips it
+FASTQ_KINDS = ("header", "sequence start", "separator", "length mismatch", "truncated record", "quality byte")
+
+
+class FastqError(ValueError):
+    """A malformed FASTQ file: ``record`` (0-based) and ``kind`` (one of ``FASTQ_KINDS``)."""
+
+    def __init__(self, record, kind):
+        super().__init__(f"malformed FASTQ: record {record}: {kind}")
+        self.record, self.kind = record, kind
+
+
+def parse_fastq(data, min_quality=0):
+    """The FASTQ rules of ``dbg_set_reads_fastq_file`` (include/dbg.h) over the bytes of a file, in plain Python ->
+    list of bytes reads.  Strict four-line records over universal-newline lines; trailing white space of the file is
+    ignored; only the last record may lack its quality line, and only if its read is empty.  A record is checked in the
+    order header, sequence start, separator, length; quality bytes (``min_quality`` > 0) after all of that."""
+    if not 0 <= int(min_quality) <= 93:
+        raise ValueError(f"min_quality must be 0..93, not {min_quality!r}")
+    lines = bytes(data).rstrip(_FQ_SPACE).splitlines()  # bytes.splitlines: \n, \r and \r\n only
+    reads, quals = [], []
+    for r in range(0, -(-len(lines) // 4)):
+        grp = lines[4 * r:4 * r + 4]
+        if grp[0][:1] != b"@":
+            raise FastqError(r, "header")
+        if len(grp) < 2:
+            raise FastqError(r, "truncated record")
+        if grp[1][:1] in (b"@", b"+"):
+            raise FastqError(r, "sequence start")
+        if len(grp) < 3:
+            raise FastqError(r, "truncated record")
+        if grp[2][:1] != b"+":
+            raise FastqError(r, "separator")
+        seq = grp[1].rstrip(_FQ_SPACE)
+        qual = grp[3].rstrip(_FQ_SPACE) if len(grp) == 4 else b""
+        if len(qual) != len(seq):
+            raise FastqError(r, "length mismatch")
+        reads.append(seq)
+        quals.append(qual)
+    if min_quality:
+        for r, qual in enumerate(quals):
+            if any(c < 33 or c > 126 for c in qual):
+                raise FastqError(r, "quality byte")
+        reads = [bytes(78 if q - 33 < min_quality else c for c, q in zip(seq, qual)) for seq, qual in zip(reads, quals)]
+    return reads
+
+
+def read_fastq(fname, min_quality=0):
+    """The reads of a FASTQ file as ``read_reads`` gives those of a FASTA file: a list of str, one per record, on the
+    host (no GPU needed).  ``min_quality`` q > 0 (Phred+33): base j becomes ``N`` where ``qual[j] - 33 < q``.
+    ``FastqError`` (a ValueError) names record and kind of a malformed file; see ``parse_fastq`` for the rules."""
+    with open(fname, "rb") as fh:
+        return [r.decode("latin-1") for r in parse_fastq(fh.read(), min_quality)]
 
 
 # Files of at least this many bytes stream to the device in chunks (dbg_set_reads_fasta_file) instead of going over in one
@@ -80,13 +135,26 @@ class DeviceReads:
     non_acgt="keep" (default): every byte of a read is a character, as in the reference.  "split": after the ingest the
     reads are cut at every byte that is not A/C/G/T (``acgt_pieces``; ``fold_case``: a c g t are folded to upper case
     first) and the object lists the pieces; ``split_stats`` holds what the pass did, ``origins()`` where each piece came from.
+
+    format="fastq": the file is strict four-line FASTQ (``read_fastq`` states the rules) and always takes the streamed
+    call (``dbg_set_reads_fastq_file``); read i is the sequence of record i and a byte range owns the records whose header
+    starts in it.  ``min_quality`` q > 0 turns every base below Phred q into ``N``: kept as a character by default, a cut
+    point with non_acgt="split".  Nothing is detected: the default "fasta" reads a FASTQ file line by line, as it always did.
     """
 
-    def __init__(self, fname, byte_range=None, chunk_bytes=None, non_acgt="keep", fold_case=False):
+    def __init__(self, fname, byte_range=None, chunk_bytes=None, non_acgt="keep", fold_case=False, format="fasta",
+                 min_quality=0):
         if non_acgt not in ("keep", "split"):
             raise ValueError(f"non_acgt must be 'keep' or 'split', not {non_acgt!r}")
+        if format not in ("fasta", "fastq"):
+            raise ValueError(f"format must be 'fasta' or 'fastq', not {format!r}")
+        if min_quality and format != "fastq":
+            raise ValueError("min_quality needs format='fastq'")
         self._graph = _dbg.Graph()
-        if byte_range is None and chunk_bytes is None and os.path.getsize(fname) < STREAM_MIN_BYTES:
+        if format == "fastq":
+            begin, end = (0, None) if byte_range is None else byte_range
+            self._graph.set_reads_fastq_file(fname, begin, end, chunk_bytes or 0, min_quality)
+        elif byte_range is None and chunk_bytes is None and os.path.getsize(fname) < STREAM_MIN_BYTES:
             self._graph.set_reads_fasta(fname)
         else:
             begin, end = (0, None) if byte_range is None else byte_range
@@ -140,10 +208,11 @@ class DeviceReads:
         return [text[int(a):int(b)] for a, b in zip(off[:-1], off[1:])]
 
 
-def read_reads_device(fname, byte_range=None, chunk_bytes=None, non_acgt="keep", fold_case=False):
+def read_reads_device(fname, byte_range=None, chunk_bytes=None, non_acgt="keep", fold_case=False, format="fasta",
+                      min_quality=0):
     """``read_reads`` (debruijn.py:22-32) without leaving the GPU; see DeviceReads (byte ranges, streamed ingest, the
-    split at bytes that are not bases)."""
-    return DeviceReads(fname, byte_range, chunk_bytes, non_acgt, fold_case)
+    split at bytes that are not bases, FASTQ files and their quality mask)."""
+    return DeviceReads(fname, byte_range, chunk_bytes, non_acgt, fold_case, format, min_quality)
 
 
 _ACGT_RUNS = re.compile(b"[ACGT]+")

@@ -120,7 +120,7 @@ def stamp_bases(dist, n_bytes, device):
     return bases
 
 
-def set_reads_fasta_shard(g, path, dist, chunk_bytes=0, non_acgt="keep", fold_case=False):
+def set_reads_fasta_shard(g, path, dist, chunk_bytes=0, non_acgt="keep", fold_case=False, format="fasta", min_quality=0):
     """Sets this rank's share of the FASTA file at ``path`` as the reads of handle ``g`` (the input of sharded_build).
 
     Rank r of w takes the lines that start in bytes [r*S//w, (r+1)*S//w) of the S-byte file (a line that starts in
@@ -132,12 +132,22 @@ def set_reads_fasta_shard(g, path, dist, chunk_bytes=0, non_acgt="keep", fold_ca
 
     non_acgt="split": each rank then cuts its own lines at the bytes that are not A/C/G/T (``Graph.split_reads``,
     ``fold_case`` as there) before any size is exchanged.  A piece never leaves its line, so the ranks' pieces in rank
-    order are the pieces of the whole file, and the same holds for the stamps."""
+    order are the pieces of the whole file, and the same holds for the stamps.
+
+    format="fastq": the same byte slice of a FASTQ file (``Graph.set_reads_fastq_file``): a rank takes the records whose
+    header line starts in its slice, with the quality mask ``min_quality`` of that call."""
     if non_acgt not in ("keep", "split"):
         raise ValueError(f"non_acgt must be 'keep' or 'split', not {non_acgt!r}")
+    if format not in ("fasta", "fastq"):
+        raise ValueError(f"format must be 'fasta' or 'fastq', not {format!r}")
+    if min_quality and format != "fastq":
+        raise ValueError("min_quality needs format='fastq'")
     w, r = dist.get_world_size(), dist.get_rank()
     size = os.path.getsize(path)
-    g.set_reads_fasta_file(path, r * size // w, (r + 1) * size // w, chunk_bytes)
+    if format == "fastq":
+        g.set_reads_fastq_file(path, r * size // w, (r + 1) * size // w, chunk_bytes, min_quality)
+    else:
+        g.set_reads_fasta_file(path, r * size // w, (r + 1) * size // w, chunk_bytes)
     if non_acgt == "split":
         g.split_reads(fold_case=fold_case)
     return g

@@ -126,6 +126,19 @@ def write_fasta(path, reads):
             fh.write(f">input_read{i}\n{r}\n")
 
 
+def write_fastq(path, reads, quals=None, seed=1):
+    """``@input_read{i}\\n{seq}\\n+\\n{qual}\\n`` per read.  quals: one Phred+33 string per read; None: seeded qualities of
+    Phred 2..41 (``random.Random(seed)``)."""
+    import random
+    rng = random.Random(seed)
+    with open(path, "w") as fh:
+        for i, r in enumerate(reads):
+            q = quals[i] if quals is not None else "".join(chr(33 + rng.randint(2, 41)) for _ in range(len(r)))
+            if len(q) != len(r):
+                raise ValueError(f"read {i}: {len(r)} bases, {len(q)} quality characters")
+            fh.write(f"@input_read{i}\n{r}\n+\n{q}\n")
+
+
 def write_froot(froot, reads, k_lower, k_upper, threshold=2, score_cut=0.0, source=""):
     """Creates ``{froot}/setting.json`` + ``{froot}/input_reads.fasta``."""
     os.makedirs(froot, exist_ok=True)
