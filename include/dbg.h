@@ -49,13 +49,13 @@ typedef struct dbg dbg_t;
 #define DBG_OK 0
 #define DBG_E_ARG (-1)      /* bad argument or call order */
 #define DBG_E_HIP (-2)      /* HIP runtime failure (text in dbg_last_error) */
-#define DBG_E_ALPHABET (-3) /* the reads hold more than 32 distinct bytes, or a byte outside "ACGT" in a call that takes ACGT reads only */
+#define DBG_E_ALPHABET (-3) /* the reads hold more than 32 distinct bytes, or a byte outside upper-case "ACGT" in a call that takes such reads only */
 #define DBG_E_CAPACITY (-4) /* hash table or an output limit was exceeded */
 #define DBG_E_NOMEM (-5)    /* host or device allocation failed */
 
 #define DBG_ABI_VERSION 6 /* not raised for dbg_build_from_walks, nor for the query calls (dbg_lookup_nodes[_device],
                             * dbg_gather_nodes, dbg_score_sequences, dbg_part_lookup_nodes[_device],
-                            * dbg_part_score_sequences), nor for dbg_split_reads / dbg_read_origins: they only add symbols, every earlier call and struct is
+                            * dbg_part_score_sequences), nor for dbg_split_reads / dbg_read_origins, nor for dbg_add_revcomp: they only add symbols, every earlier call and struct is
                             * unchanged, and tests/test_fasta_stream.py pins this number; a binding that needs a new
                             * call fails at symbol lookup on an older library */
 
@@ -272,6 +272,35 @@ int dbg_split_reads(dbg_t *h, uint32_t flags, dbg_split_stats_t *out /* may be N
  * its first byte's position in that read; [n_reads] each, either may be NULL.  After a call that changed nothing: (j, 0).
  * DBG_E_ARG before a dbg_split_reads on the current read set: every dbg_set_reads* forgets the origins. */
 int dbg_read_origins(dbg_t *h, uint64_t *read_index, uint64_t *pos);
+/* Both strands: replaces the resident reads r0, r1, ... by r0, rc(r0), r1, rc(r1), ... in one streaming pass on the device,
+ * whichever call set them.  The graph of both strands is, by definition, the reference run on that list; read j of the
+ * new set is strand j & 1 of old read j >> 1.  With n reads, N bytes and offsets o[] (len_i = o[i+1] - o[i]):
+ *   - the outputs are buffers of exactly their size that the handle owns: 2N + 64 bytes of bases (64 bytes of zero padding,
+ *     aligned as dbg_set_reads aligns them) and 2n + 1 offsets,
+ *       out_off[2i] = 2 o[i],  out_off[2i+1] = 2 o[i] + len_i,  out_off[2n] = 2N
+ *       out[2 o[i] + j] = in[o[i] + j],  out[2 o[i] + len_i + j] = comp(in[o[i] + len_i - 1 - j])
+ *   - comp maps A<->T, C<->G, a<->t, c<->g; every other byte ('N' and bytes >= 0x80 included) maps to itself, so the
+ *     alphabet never grows beyond what the input plus these eight bytes allow.  On generic or peptide reads the call
+ *     does exactly the same (meaningless there, but defined); n_other_bytes says how many bytes were not complemented.
+ *   - an empty read gives two empty reads; n = 0 is DBG_OK with an empty read set; no reads set is DBG_E_ARG; flags are
+ *     reserved: any bit set is DBG_E_ARG.
+ *   - like dbg_set_reads and dbg_split_reads the call drops any graph, walk and parts of the handle, forgets the cached
+ *     alphabet and rebuilds the read-start bitmap.  Buffers lent through dbg_set_reads_device are never written: they are
+ *     let go and replaced by owned ones; owned old buffers are freed after the swap.  On any failure the handle keeps
+ *     the read set it had.  Calling it twice doubles twice: it is an operation on the list, not a mode.
+ *   - dbg_read_origins keeps working: after a dbg_split_reads, entries 2i and 2i+1 both carry piece i's (read_index, pos),
+ *     pos being the position of the piece's first byte in forward orientation; identity origins become (j >> 1, 0).  The
+ *     strand of read j is j & 1, so no third array exists.  Without a dbg_split_reads it fails as before. */
+typedef struct dbg_revcomp_stats {
+    uint64_t n_reads_in, n_bytes_in;
+    uint64_t n_reads_out, n_bytes_out; /* 2 n_reads_in, 2 n_bytes_in */
+    uint64_t n_other_bytes;            /* input bytes comp leaves as they are */
+    uint64_t n_palindromes;            /* reads of at least one byte whose reverse complement is the read itself */
+    uint64_t peak_extra_device_bytes;  /* the old and the new read set live at once: 2N + 64 + 8 (2n + 1), plus 32 B per
+                                        * read for the doubled origins of an earlier split */
+    double ms_kernel;                  /* the pass's kernels, by events on the handle's stream */
+} dbg_revcomp_stats_t;
+int dbg_add_revcomp(dbg_t *h, uint32_t flags, dbg_revcomp_stats_t *out /* may be NULL */);
 
 /* ---- a3 + a4: get_graph_from_reads (debruijn.py:98-147) + edge-count table (:213-222)
  *      -> node table, 4-way successor edges, CSR ------------------------------------ */

@@ -3,7 +3,7 @@
 
 Same CLI (``-froot``), same ``{froot}/setting.json`` keys (score_cut, k_lowerlimit,
 k_upperlimit, threshold, source -- II_assembleFromReads.py:32-38; optionally non_acgt,
-fold_case, reads_format and min_quality, see ``debruijn.DeviceReads``), same stdout lines and
+fold_case, reads_format, min_quality and strands, see ``debruijn.DeviceReads``), same stdout lines and
 the same append-mode FASTA output ``{froot}/{froot}.fasta`` with records
 ``>SEQUENCE_{i}_{k}mer`` (II_assembleFromReads.py:65-69).  Input is the FASTA surface the
 reference keeps commented out at II_assembleFromReads.py:53:
@@ -82,7 +82,9 @@ if __name__ == '__main__':
     # II_assembleFromReads.py:53 with the FASTA parsed on the GPU (read_reads semantics, no Python string per read)
     # optional keys: "non_acgt": "split" cuts the reads at every byte that is not A/C/G/T, "fold_case" folds a c g t first
     # "reads_format": "fastq" reads {froot}/input_reads.fastq instead; "min_quality": q turns bases below Phred q into N
-    split = {key: setting[key] for key in ('non_acgt', 'fold_case', 'min_quality') if key in setting}
+    # "strands": "both" follows every read with its reverse complement, at this ingest only: the contigs and pulled reads
+    # that the later k's take already hold both strands, so nothing is doubled again
+    split = {key: setting[key] for key in ('non_acgt', 'fold_case', 'min_quality', 'strands') if key in setting}
     reads_format = setting.get('reads_format', 'fasta')
     if reads_format not in ('fasta', 'fastq'):
         raise ValueError(f"setting.json: reads_format must be 'fasta' or 'fastq', not {reads_format!r}")

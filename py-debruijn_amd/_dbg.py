@@ -43,7 +43,7 @@ SYMBOLS = (
     "dbg_export_contig_texts", "dbg_write_contigs_fasta", "dbg_contig_output_stats",
     "dbg_part_set_skeleton", "dbg_part_contig_window", "dbg_part_export_contig_texts", "dbg_part_write_contigs_fasta",
     "dbg_part_final_walk", "dbg_part_final_export",
-    "dbg_split_reads", "dbg_read_origins",
+    "dbg_split_reads", "dbg_read_origins", "dbg_add_revcomp",
 )
 
 
@@ -117,6 +117,21 @@ SPLIT_FOLD_CASE = 1
 SPLIT_WORD_BYTES = 64
 SPLIT_BLOCK_BYTES = 256 * 4 * SPLIT_WORD_BYTES
 SPLIT_ROUND_BYTES = 256 * SPLIT_BLOCK_BYTES
+
+
+class RevcompStats(C.Structure):
+    """dbg_revcomp_stats_t: what the last dbg_add_revcomp did"""
+    _fields_ = [(n, C.c_uint64) for n in (
+        "n_reads_in", "n_bytes_in", "n_reads_out", "n_bytes_out", "n_other_bytes", "n_palindromes",
+        "peak_extra_device_bytes")] + [("ms_kernel", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# granularities of the both-strands kernel (csrc/dbg_revcomp.h: RC_TILE_BYTES, RC_SLICE_READS); tests aim at them
+RC_TILE_BYTES = 256 * 8 * 16
+RC_SLICE_READS = 1024
 
 
 class WalkBlock(C.Structure):
@@ -263,6 +278,7 @@ def load_library():
         "dbg_part_final_export": (C.c_int, [H, vp, vp, vp, vp, vp, vp]),
         "dbg_split_reads": (C.c_int, [H, C.c_uint32, C.POINTER(SplitStats)]),
         "dbg_read_origins": (C.c_int, [H, vp, vp]),
+        "dbg_add_revcomp": (C.c_int, [H, C.c_uint32, C.POINTER(RevcompStats)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -420,9 +436,18 @@ class Graph:
             self._keep = []  # lent buffers were replaced by the handle's own
         return out.as_dict()
 
+    def add_revcomp(self):
+        """Both strands: the resident reads r0, r1, ... become r0, rc(r0), r1, rc(r1), ... (``debruijn.both_strands``)
+        -> the call's statistics.  Read j is then strand ``j & 1`` of the earlier read ``j >> 1``; lent buffers are let go."""
+        out = RevcompStats()
+        self.generation += 1
+        self._chk(self._lib.dbg_add_revcomp(self._h, 0, C.byref(out)))
+        self._keep = []  # lent buffers were replaced by the handle's own
+        return out.as_dict()
+
     def read_origins(self):
         """-> (read_index, pos) uint64 [n_reads]: the read each piece of the last ``split_reads`` came from and the
-        position of its first byte there."""
+        position of its first byte there.  After ``add_revcomp`` entries 2i and 2i + 1 are piece i's: strand ``j & 1``."""
         n = self.sizes()["n_reads"]
         r, p = np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64)
         self._chk(self._lib.dbg_read_origins(self._h, _ptr(r), _ptr(p)))

@@ -54,6 +54,7 @@
 #include "dbg_wsk.h"
 #include "dbg_fasta.h"
 #include "dbg_readsplit.h"
+#include "dbg_revcomp.h"
 #include "dbg_fastq.h"
 #include "dbg_lookup.h"
 #include "dbg_ctgout.h"
@@ -1030,6 +1031,7 @@ static void free_reads(dbg *h) {
     h->n_bytes = h->n_reads = 0;
     dev_free(h->d_org_read); dev_free(h->d_org_pos);
     h->split_done = false;
+    h->org_shift = 0;
 }
 
 extern "C" int dbg_abi_version(void) { return DBG_ABI_VERSION; }
@@ -1817,6 +1819,7 @@ extern "C" int dbg_split_reads(dbg_t *h, uint32_t flags, dbg_split_stats_t *out)
     free_build(h);
     dev_free(h->d_org_read); dev_free(h->d_org_pos);
     h->split_done = false;
+    h->org_shift = 0;
     const int fold = (flags & DBG_SPLIT_FOLD_CASE) ? 1 : 0;
     const uint64_t n = h->n_bytes, n_reads = h->n_reads;
     const uint64_t n_words = (n + RS_WORD_BYTES - 1) / RS_WORD_BYTES;
@@ -1903,9 +1906,9 @@ extern "C" int dbg_read_origins(dbg_t *h, uint64_t *read_index, uint64_t *pos) {
     if (!h) return DBG_E_ARG;
     if (!h->split_done) { h->err = "dbg_read_origins: dbg_split_reads has not run on the current read set"; return DBG_E_ARG; }
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->d_org_read) {  // nothing was cut: piece i is read i
+    if (!h->d_org_read) {  // nothing was cut: piece i is read i, and strand j & 1 of it after every dbg_add_revcomp
         for (uint64_t i = 0; i < h->n_reads; ++i) {
-            if (read_index) read_index[i] = i;
+            if (read_index) read_index[i] = i >> h->org_shift;
             if (pos) pos[i] = 0;
         }
         return DBG_OK;
@@ -1914,6 +1917,79 @@ extern "C" int dbg_read_origins(dbg_t *h, uint64_t *read_index, uint64_t *pos) {
     if (pos && h->n_reads) HIPCHK(h, hipMemcpyAsync(pos, h->d_org_pos, h->n_reads * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return DBG_OK;
+}
+
+// ---- both strands of the resident reads: r0, rc(r0), r1, rc(r1), ... (kernels: dbg_revcomp.h)
+extern "C" int dbg_add_revcomp(dbg_t *h, uint32_t flags, dbg_revcomp_stats_t *out) {
+    if (!h) return DBG_E_ARG;
+    if (flags) { h->err = "dbg_add_revcomp: flag bits are reserved"; return DBG_E_ARG; }
+    if (!h->d_offsets) { h->err = "no reads set"; return DBG_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    free_build(h);
+    const uint64_t n = h->n_bytes, n_reads = h->n_reads, n2 = 2 * n;
+    const bool origins = h->split_done && h->d_org_read;
+    dbg_revcomp_stats_t s{};
+    s.n_reads_in = n_reads;
+    s.n_bytes_in = n;
+    s.n_reads_out = 2 * n_reads;
+    s.n_bytes_out = n2;
+    // exact-size outputs next to the old read set, which stays the handle's until everything has run
+    char *nb = nullptr;
+    uint64_t *noff = nullptr, *org_read = nullptr, *org_pos = nullptr;
+    auto fail = [&](int rc) { dev_free(nb); dev_free(noff); dev_free(org_read); dev_free(org_pos); return rc; };
+    int rc = dev_alloc(h, &nb, n2 + 64);
+    if (rc == DBG_OK) rc = dev_alloc(h, &noff, 2 * n_reads + 1);
+    if (rc == DBG_OK && origins) rc = dev_alloc(h, &org_read, 2 * n_reads);
+    if (rc == DBG_OK && origins) rc = dev_alloc(h, &org_pos, 2 * n_reads);
+    if (rc != DBG_OK) return fail(rc);
+    s.peak_extra_device_bytes = (n2 + 64) + 8 * (2 * n_reads + 1) + (origins ? 32 * std::max<uint64_t>(n_reads, 1) : 0);
+    RcTotals *d_tot = (RcTotals *)(h->d_scalars + 16);
+    RcTotals t{};
+    hipError_t e = hipMemsetAsync(d_tot, 0, sizeof(RcTotals), h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(nb + n2, 0, 64, h->stream);
+    if (e == hipSuccess) {
+        Timer tm(h->stream);
+        hipLaunchKernelGGL(k_rc_offsets, dim3(grid_for(n_reads + 1, 256)), dim3(256), 0, h->stream, h->d_offsets, n_reads, noff);
+        if (n2) {
+            const uint64_t n_tiles = (n2 + RC_TILE_BYTES - 1) / RC_TILE_BYTES;
+            if (n_tiles > 0x7FFFFFFFull) { h->err = "dbg_add_revcomp: read set too large"; return fail(DBG_E_ARG); }
+            // a lent buffer ends at its last base; one the handle owns has 64 bytes more
+            hipLaunchKernelGGL(k_rc_tile, dim3((unsigned)n_tiles), dim3(256), 0, h->stream, h->d_bases,
+                               n + (h->own_bases ? 64 : 0), h->d_offsets, n_reads, nb, n2, d_tot);
+        }
+        if (n_reads) {
+            const unsigned grid = (unsigned)std::min<uint64_t>((n_reads + 3) / 4, 8192);
+            hipLaunchKernelGGL(k_rc_palindromes, dim3(grid), dim3(256), 0, h->stream, h->d_bases, h->d_offsets, n_reads, d_tot);
+        }
+        if (origins && n_reads)
+            hipLaunchKernelGGL(k_rc_origins, dim3(grid_for(n_reads, 256)), dim3(256), 0, h->stream, h->d_org_read, h->d_org_pos,
+                               n_reads, org_read, org_pos);
+        e = hipGetLastError();
+        s.ms_kernel = tm.stop();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&t, d_tot, sizeof(RcTotals), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) { h->err = std::string("dbg_add_revcomp: ") + hipGetErrorString(e); return fail(DBG_E_HIP); }
+    s.n_other_bytes = t.other;
+    s.n_palindromes = t.palindromes;
+    // swap: a borrowed buffer is let go unwritten, an owned one is freed
+    if (h->own_bases) dev_free(h->d_bases);
+    if (h->own_offsets) dev_free(h->d_offsets);
+    h->d_bases = nb; h->own_bases = true;
+    h->d_offsets = noff; h->own_offsets = true;
+    h->n_bytes = n2;
+    h->n_reads = 2 * n_reads;
+    if (origins) {
+        dev_free(h->d_org_read); dev_free(h->d_org_pos);
+        h->d_org_read = org_read;
+        h->d_org_pos = org_pos;
+    } else if (h->split_done) {
+        ++h->org_shift;
+    }
+    dev_free(h->d_lut); dev_free(h->d_alpha);
+    h->alpha_known = false;
+    if (out) *out = s;
+    return make_startbits(h);
 }
 
 // ---- a selection of the resident reads, gathered on the device (pull_out_read of construct_graph, debruijn.py:274-278:

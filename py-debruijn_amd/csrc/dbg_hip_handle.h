@@ -151,6 +151,7 @@ struct dbg {
     // dbg_split_reads ran on the current read set; the origins of its pieces (both null: the identity, nothing was cut)
     bool split_done = false;
     uint64_t *d_org_read = nullptr, *d_org_pos = nullptr;
+    uint32_t org_shift = 0;  // dbg_add_revcomp calls since then: the identity origins are (j >> org_shift, 0)
 
     // build
     int k = 0;

@@ -140,12 +140,19 @@ class DeviceReads:
     call (``dbg_set_reads_fastq_file``); read i is the sequence of record i and a byte range owns the records whose header
     starts in it.  ``min_quality`` q > 0 turns every base below Phred q into ``N``: kept as a character by default, a cut
     point with non_acgt="split".  Nothing is detected: the default "fasta" reads a FASTQ file line by line, as it always did.
+
+    strands="forward" (default): the reads as they are.  "both": after the ingest (and its quality mask) and after the split,
+    every read is followed by its reverse complement (``both_strands``; ``Graph.add_revcomp``): the object lists
+    r0, rc(r0), r1, rc(r1), ... and ``revcomp_stats`` holds what the pass did.  Cutting before complementing gives the same
+    pieces as the other order.
     """
 
     def __init__(self, fname, byte_range=None, chunk_bytes=None, non_acgt="keep", fold_case=False, format="fasta",
-                 min_quality=0):
+                 min_quality=0, strands="forward"):
         if non_acgt not in ("keep", "split"):
             raise ValueError(f"non_acgt must be 'keep' or 'split', not {non_acgt!r}")
+        if strands not in ("forward", "both"):
+            raise ValueError(f"strands must be 'forward' or 'both', not {strands!r}")
         if format not in ("fasta", "fastq"):
             raise ValueError(f"format must be 'fasta' or 'fastq', not {format!r}")
         if min_quality and format != "fastq":
@@ -160,12 +167,14 @@ class DeviceReads:
             begin, end = (0, None) if byte_range is None else byte_range
             self._graph.set_reads_fasta_file(fname, begin, end, chunk_bytes or 0)
         self.split_stats = self._graph.split_reads(fold_case=fold_case) if non_acgt == "split" else None
+        self.revcomp_stats = self._graph.add_revcomp() if strands == "both" else None
         self._n = self._graph.sizes()["n_reads"]
         self._host = None
 
     def origins(self):
         """non_acgt="split": (read_index, pos) uint64 arrays -- the read of the file (the line, headers not counted;
-        within the byte range) every piece came from and the position of its first byte in it."""
+        within the byte range) every piece came from and the position of its first byte in it.
+        strands="both": entry j is strand ``j & 1`` of piece ``j >> 1``, pos in forward orientation."""
         if self.split_stats is None:
             raise ValueError("origins() needs non_acgt='split'")
         return self._graph.read_origins()
@@ -209,10 +218,10 @@ class DeviceReads:
 
 
 def read_reads_device(fname, byte_range=None, chunk_bytes=None, non_acgt="keep", fold_case=False, format="fasta",
-                      min_quality=0):
+                      min_quality=0, strands="forward"):
     """``read_reads`` (debruijn.py:22-32) without leaving the GPU; see DeviceReads (byte ranges, streamed ingest, the
-    split at bytes that are not bases, FASTQ files and their quality mask)."""
-    return DeviceReads(fname, byte_range, chunk_bytes, non_acgt, fold_case, format, min_quality)
+    split at bytes that are not bases, FASTQ files and their quality mask, both strands)."""
+    return DeviceReads(fname, byte_range, chunk_bytes, non_acgt, fold_case, format, min_quality, strands)
 
 
 _ACGT_RUNS = re.compile(b"[ACGT]+")
@@ -230,6 +239,27 @@ def acgt_pieces(reads, fold_case=False):
         if fold_case:
             b = b.translate(_FOLD_ACGT)
         out.extend(m.decode("latin-1") if text else m for m in _ACGT_RUNS.findall(b))
+    return out
+
+
+_COMP = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+
+
+def revcomp(read):
+    """The reverse complement of one read: the read backwards with A<->T, C<->G, a<->t, c<->g swapped and every other
+    byte (``N``, bytes >= 0x80, ...) as it is.  str in (one byte per character, latin-1), str out; bytes in, bytes out."""
+    if isinstance(read, str):
+        return read.encode("latin-1").translate(_COMP)[::-1].decode("latin-1")
+    return bytes(read).translate(_COMP)[::-1]
+
+
+def both_strands(reads):
+    """What ``add_revcomp`` / ``strands="both"`` computes, in plain Python: ``[r0, revcomp(r0), r1, revcomp(r1), ...]``.
+    The graph of both strands is the reference run on this list; read j is strand ``j & 1`` of read ``j >> 1``."""
+    out = []
+    for r in reads:
+        out.append(r if isinstance(r, str) else bytes(r))
+        out.append(revcomp(r))
     return out
 
 

@@ -120,7 +120,8 @@ def stamp_bases(dist, n_bytes, device):
     return bases
 
 
-def set_reads_fasta_shard(g, path, dist, chunk_bytes=0, non_acgt="keep", fold_case=False, format="fasta", min_quality=0):
+def set_reads_fasta_shard(g, path, dist, chunk_bytes=0, non_acgt="keep", fold_case=False, format="fasta", min_quality=0,
+                          strands="forward"):
     """Sets this rank's share of the FASTA file at ``path`` as the reads of handle ``g`` (the input of sharded_build).
 
     Rank r of w takes the lines that start in bytes [r*S//w, (r+1)*S//w) of the S-byte file (a line that starts in
@@ -135,9 +136,16 @@ def set_reads_fasta_shard(g, path, dist, chunk_bytes=0, non_acgt="keep", fold_ca
     order are the pieces of the whole file, and the same holds for the stamps.
 
     format="fastq": the same byte slice of a FASTQ file (``Graph.set_reads_fastq_file``): a rank takes the records whose
-    header line starts in its slice, with the quality mask ``min_quality`` of that call."""
+    header line starts in its slice, with the quality mask ``min_quality`` of that call.
+
+    strands="both": each rank then follows every read of its own with its reverse complement (``Graph.add_revcomp``), after
+    its split and before any size is exchanged.  The reverse complements are interleaved, r0, rc(r0), r1, rc(r1), ..., not
+    appended behind all reads: a rank's doubled reads are then a contiguous stretch of the doubled reads of the whole file,
+    so the ranks' reads in rank order are still the single handle's reads in file order and the stamp bases stay its."""
     if non_acgt not in ("keep", "split"):
         raise ValueError(f"non_acgt must be 'keep' or 'split', not {non_acgt!r}")
+    if strands not in ("forward", "both"):
+        raise ValueError(f"strands must be 'forward' or 'both', not {strands!r}")
     if format not in ("fasta", "fastq"):
         raise ValueError(f"format must be 'fasta' or 'fastq', not {format!r}")
     if min_quality and format != "fastq":
@@ -150,6 +158,8 @@ def set_reads_fasta_shard(g, path, dist, chunk_bytes=0, non_acgt="keep", fold_ca
         g.set_reads_fasta_file(path, r * size // w, (r + 1) * size // w, chunk_bytes)
     if non_acgt == "split":
         g.split_reads(fold_case=fold_case)
+    if strands == "both":
+        g.add_revcomp()
     return g
 
 
