@@ -55,7 +55,8 @@ typedef struct dbg dbg_t;
 
 #define DBG_ABI_VERSION 6 /* not raised for dbg_build_from_walks, nor for the query calls (dbg_lookup_nodes[_device],
                             * dbg_gather_nodes, dbg_score_sequences, dbg_part_lookup_nodes[_device],
-                            * dbg_part_score_sequences), nor for dbg_split_reads / dbg_read_origins, nor for dbg_add_revcomp: they only add symbols, every earlier call and struct is
+                            * dbg_part_score_sequences), nor for dbg_split_reads / dbg_read_origins, nor for dbg_add_revcomp,
+                            * nor for dbg_set_reads_fasta_records[_file] / dbg_fasta_records_stats / dbg_write_contigs_fasta_wrapped: they only add symbols, every earlier call and struct is
                             * unchanged, and tests/test_fasta_stream.py pins this number; a binding that needs a new
                             * call fails at symbol lookup on an older library */
 
@@ -199,6 +200,35 @@ int dbg_set_reads_fasta(dbg_t *h, const char *text, uint64_t n_text);
  * past the end of the file gives an empty read set. */
 int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t begin, uint64_t end, uint64_t chunk_bytes);
 int dbg_fasta_ingest_stats(dbg_t *h, dbg_ingest_stats_t *out);
+/* Record mode of the FASTA ingest: read i is RECORD i, not line i.  Lines are those of dbg_set_reads_fasta_file (universal
+ * newlines).  A header is a line whose first byte is '>' (a '>' anywhere else is a character; a line that begins with a
+ * space and then '>' is a sequence line).  Read i is the concatenation of the sequence lines between header i and the next
+ * header or the end of the file, each line rstrip'ed on its own (white space inside a line stays, a blank line adds
+ * nothing); a header followed at once by a header or by the end of the file gives an empty read, so n_reads is the number
+ * of headers.  Non-header lines in front of the file's first header must be blank after rstrip; anything else is a
+ * malformed file: DBG_E_ARG, dbg_last_error names the byte position of the first offending byte, and the handle is left
+ * with no reads (and stays usable).  No ';' comment lines, no detection of the format, no check of the alphabet.
+ * dbg_set_reads_fasta_records_file reads the records whose header's FIRST byte lies in [begin, end) of the file at `path`
+ * (end = UINT64_MAX: to EOF), with the arguments and errors of dbg_set_reads_fasta_file.  A record that starts inside the
+ * range is read to its end, even past `end`; bytes between `begin` and the first owned header belong to the previous
+ * range's last record; only the range with begin == 0 reports sequence before the first header; a range without a header
+ * is an empty read set (DBG_OK).  So the reads of [0, b) followed by those of [b, size) are the reads of the file for every
+ * b.  The host finds the first header at or after `begin` and at or after `end` before the first chunk, then the owned
+ * bytes stream as in dbg_set_reads_fasta_file; the device holds the packed bases (owned bytes at most), the offsets and
+ * ~1.5 chunks of parse state.  dbg_set_reads_fasta_records takes the whole image from a host buffer and runs it as one
+ * range through the same stream.  Both fill dbg_ingest_stats_t too (bytes_read counts the host's search as well). */
+int dbg_set_reads_fasta_records(dbg_t *h, const char *text, uint64_t n_text);
+int dbg_set_reads_fasta_records_file(dbg_t *h, const char *path, uint64_t begin, uint64_t end, uint64_t chunk_bytes);
+/* what the last record-mode ingest did, beside dbg_ingest_stats_t */
+typedef struct dbg_fasta_records_stats {
+    uint64_t n_records;         /* owned headers = reads */
+    uint64_t n_sequence_lines;  /* owned non-header lines, blank ones included */
+    uint64_t longest_record;    /* bases of the longest read */
+    uint64_t first_byte;        /* file position of the first owned header (end_byte if none) */
+    uint64_t end_byte;          /* file position of the first header at or past `end`, or the file size */
+    uint64_t scan_bytes;        /* bytes the host read to find those two positions */
+} dbg_fasta_records_stats_t;
+int dbg_fasta_records_stats(dbg_t *h, dbg_fasta_records_stats_t *out);
 /* Reads of the FASTQ records whose header line's FIRST byte lies in [begin, end) of the file at `path` (end = UINT64_MAX:
  * to EOF), streamed and parsed like dbg_set_reads_fasta_file (same arguments, same errors, any chunk_bytes from 1 up; it
  * fills dbg_ingest_stats_t too, bytes_read being the bytes of the owned records).  Read i is the sequence line of record i,
@@ -531,6 +561,13 @@ int dbg_export_contig_texts(dbg_t *h, const uint64_t *indices, uint64_t n, uint6
  * cannot be opened for writing and for a chunk_bytes that is no multiple of 4096; n = 0 writes nothing. */
 int dbg_write_contigs_fasta(dbg_t *h, const char *path, int append, const uint64_t *indices, uint64_t n,
                             uint64_t first_number, int k_label, uint64_t chunk_bytes, uint64_t *bytes_written);
+/* dbg_write_contigs_fasta with the contig of every record in lines of line_width characters, each ended by '\n' (the last
+ * line may be shorter).  A contig of 0 characters still gets its one '\n'; a contig whose length is a multiple of
+ * line_width gets no extra empty line: the body of a record takes len + max(1, ceil(len / line_width)) bytes.
+ * line_width 0: one line per contig, exactly the bytes of dbg_write_contigs_fasta (which is this call with 0). */
+int dbg_write_contigs_fasta_wrapped(dbg_t *h, const char *path, int append, const uint64_t *indices, uint64_t n,
+                                    uint64_t first_number, int k_label, uint64_t chunk_bytes, uint32_t line_width,
+                                    uint64_t *bytes_written);
 int dbg_contig_output_stats(dbg_t *h, dbg_contig_out_stats_t *out);
 /* ---- the same two outputs for the walk over a graph in parts (csrc/dbg_partout.h).  The caller ranks the skeleton of
  *      segments (one row per entry node, sorted by global id = virtual shard << 32 | local id) and hands it over once:

@@ -3,7 +3,8 @@
 
 Same CLI (``-froot``), same ``{froot}/setting.json`` keys (score_cut, k_lowerlimit,
 k_upperlimit, threshold, source -- II_assembleFromReads.py:32-38; optionally non_acgt,
-fold_case, reads_format, min_quality and strands, see ``debruijn.DeviceReads``), same stdout lines and
+fold_case, reads_format, min_quality, strands and fasta_records, see ``debruijn.DeviceReads``, and
+fasta_line_width for the output), same stdout lines and
 the same append-mode FASTA output ``{froot}/{froot}.fasta`` with records
 ``>SEQUENCE_{i}_{k}mer`` (II_assembleFromReads.py:65-69).  Input is the FASTA surface the
 reference keeps commented out at II_assembleFromReads.py:53:
@@ -35,8 +36,9 @@ def get_args():
     return parser.parse_args()
 
 
-def assemble(sequences, k_lowerlimit, k_upperlimit, threshold, out_path=None):
-    """II_assembleFromReads.py:56-75.  Returns the final, score-sorted contig list."""
+def assemble(sequences, k_lowerlimit, k_upperlimit, threshold, out_path=None, line_width=0):
+    """II_assembleFromReads.py:56-75.  Returns the final, score-sorted contig list.  ``line_width`` W > 0: the contigs of
+    the output file in lines of W characters (``debruijn.wrap_fasta_record``); 0: one line each, as in the reference."""
     for k in range(k_lowerlimit, k_upperlimit + 1):
         final = not (k <= k_upperlimit - 1)
         g, pull_out_read, branch_kmer, already_pull_out, edge_count_table = db.construct_graph(
@@ -54,14 +56,17 @@ def assemble(sequences, k_lowerlimit, k_upperlimit, threshold, out_path=None):
             max_len = max((len(x) for x in sequences), default=0)
         if k == k_upperlimit:
             if out_path is not None and isinstance(sequences, db.LazyContigs):
-                sequences.write_fasta(out_path, k)  # append mode; formatted on the device, streamed window by window
+                # append mode; formatted on the device, streamed window by window
+                sequences.write_fasta(out_path, k, line_width=line_width)
+            elif out_path is not None and line_width and getattr(contigs, "_graph", None) is not None:
+                contigs.write_fasta(out_path, k, order, line_width=line_width)  # the score order above, wrapped on the device
             elif out_path is not None:
                 with open(out_path, mode='a+') as out_file:  # append mode, as in the reference
                     if hasattr(contigs, "sorted_fasta"):
                         out_file.write(contigs.sorted_fasta())  # the same records, sorted and formatted on the device
                     else:
                         for i in range(len(sequences)):
-                            out_file.write('>SEQUENCE_{}_{}mer\n{}\n'.format(i, k, sequences[i]))
+                            out_file.write('>SEQUENCE_{}_{}mer\n{}'.format(i, k, db.wrap_fasta_record(sequences[i], line_width)))
             break
         print('max length: ', max_len)
         print('number of output for k={}: '.format(k), len(sequences))
@@ -85,9 +90,19 @@ if __name__ == '__main__':
     # "strands": "both" follows every read with its reverse complement, at this ingest only: the contigs and pulled reads
     # that the later k's take already hold both strands, so nothing is doubled again
     split = {key: setting[key] for key in ('non_acgt', 'fold_case', 'min_quality', 'strands') if key in setting}
+    # "fasta_records": "record" takes one read per FASTA record (a line-wrapped input file), "line" (default) one per line
+    # "fasta_line_width": W writes the contigs of the output file in lines of W characters
     reads_format = setting.get('reads_format', 'fasta')
     if reads_format not in ('fasta', 'fastq'):
         raise ValueError(f"setting.json: reads_format must be 'fasta' or 'fastq', not {reads_format!r}")
+    fasta_records = setting.get('fasta_records', 'line')
+    if fasta_records not in ('line', 'record'):
+        raise ValueError(f"setting.json: fasta_records must be 'line' or 'record', not {fasta_records!r}")
+    line_width = setting.get('fasta_line_width', 0)
+    if isinstance(line_width, bool) or not isinstance(line_width, int) or line_width < 0:
+        raise ValueError(f"setting.json: fasta_line_width must be a non-negative integer, not {line_width!r}")
+    if 'fasta_records' in setting:
+        split['records'] = fasta_records
     sequences = read_reads_device(f'{froot}/input_reads.{reads_format}', format=reads_format, **split)
     print(len(sequences))
-    assemble(sequences, k_lowerlimit, k_upperlimit, threshold, out_path=f'{froot}/{froot}.fasta')
+    assemble(sequences, k_lowerlimit, k_upperlimit, threshold, out_path=f'{froot}/{froot}.fasta', line_width=line_width)

@@ -23,6 +23,7 @@ ABI_VERSION = 6
 SYMBOLS = (
     "dbg_create", "dbg_destroy", "dbg_last_error", "dbg_abi_version", "dbg_set_option", "dbg_set_reads", "dbg_set_reads_fasta",
     "dbg_set_reads_fasta_file", "dbg_fasta_ingest_stats", "dbg_set_reads_fastq_file", "dbg_fastq_ingest_stats",
+    "dbg_set_reads_fasta_records", "dbg_set_reads_fasta_records_file", "dbg_fasta_records_stats", "dbg_write_contigs_fasta_wrapped",
     "dbg_set_reads_device",
     "dbg_synth_reads", "dbg_reads_checksum", "dbg_copy_reads", "dbg_reads_device", "dbg_build", "dbg_refine_edge_order", "dbg_export_orders",
     "dbg_get_alphabet", "dbg_export_keepmask", "dbg_export_dict_order",
@@ -88,6 +89,15 @@ class FastqStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "n_records", "masked_bases", "quality_bytes_held", "peak_device_bytes", "min_quality", "first_byte", "end_byte")] + [
         ("ms_mask", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class FastaRecordsStats(C.Structure):
+    """dbg_fasta_records_stats_t: what the last record-mode FASTA ingest did, beside IngestStats"""
+    _fields_ = [(n, C.c_uint64) for n in (
+        "n_records", "n_sequence_lines", "longest_record", "first_byte", "end_byte", "scan_bytes")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -194,6 +204,9 @@ def load_library():
         "dbg_fasta_ingest_stats": (C.c_int, [H, C.POINTER(IngestStats)]),
         "dbg_set_reads_fastq_file": (C.c_int, [H, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32]),
         "dbg_fastq_ingest_stats": (C.c_int, [H, C.POINTER(FastqStats)]),
+        "dbg_set_reads_fasta_records": (C.c_int, [H, vp, C.c_uint64]),
+        "dbg_set_reads_fasta_records_file": (C.c_int, [H, C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64]),
+        "dbg_fasta_records_stats": (C.c_int, [H, C.POINTER(FastaRecordsStats)]),
         "dbg_set_reads_device": (C.c_int, [H, vp, C.c_uint64, vp, C.c_uint64]),
         "dbg_synth_reads": (C.c_int, [H, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32]),
         "dbg_reads_checksum": (C.c_int, [H, u64p]),
@@ -269,6 +282,8 @@ def load_library():
         "dbg_part_score_sequences": (C.c_int, [H, vp, vp, C.c_uint64, vp, vp]),
         "dbg_export_contig_texts": (C.c_int, [H, vp, C.c_uint64, vp, vp, C.c_uint64, u64p]),
         "dbg_write_contigs_fasta": (C.c_int, [H, C.c_char_p, C.c_int, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, u64p]),
+        "dbg_write_contigs_fasta_wrapped": (C.c_int, [H, C.c_char_p, C.c_int, vp, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64,
+                                                      C.c_uint32, u64p]),
         "dbg_contig_output_stats": (C.c_int, [H, C.POINTER(ContigOutStats)]),
         "dbg_part_set_skeleton": (C.c_int, [H, C.c_uint64, vp, vp, vp, vp, vp]),
         "dbg_part_contig_window": (C.c_int, [H, vp, C.c_uint64, C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.c_uint64, vp, u64p]),
@@ -390,6 +405,33 @@ class Graph:
         """What the last FASTQ ingest did beside ``ingest_stats()``: records, masked bases, quality bytes held, peak."""
         out = FastqStats()
         self._chk(self._lib.dbg_fastq_ingest_stats(self._h, C.byref(out)))
+        return out.as_dict()
+
+    def set_reads_fasta_records(self, path_or_bytes):
+        """``set_reads_fasta`` in record mode: read i is record i, the sequence lines between header i and the next header
+        joined (``debruijn.parse_fasta_records`` states the rules).  Sequence before the first header raises DbgError
+        (DBG_E_ARG) naming its byte position and leaves the handle without reads."""
+        if isinstance(path_or_bytes, np.ndarray):
+            raw = np.ascontiguousarray(path_or_bytes, dtype=np.uint8).reshape(-1)
+        elif isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+            raw = np.frombuffer(path_or_bytes, dtype=np.uint8)
+        else:
+            raw = np.fromfile(path_or_bytes, dtype=np.uint8)
+        self.generation += 1
+        self._chk(self._lib.dbg_set_reads_fasta_records(self._h, _ptr(raw) if raw.size else None, raw.size))
+
+    def set_reads_fasta_records_file(self, path, begin=0, end=None, chunk_bytes=0):
+        """Streams the records of ``path`` whose header line starts in bytes [begin, end) (end None: to the end of the
+        file) like ``set_reads_fasta_file``; a record that starts in the range is read to its end."""
+        end = (1 << 64) - 1 if end is None else int(end)
+        self.generation += 1
+        self._chk(self._lib.dbg_set_reads_fasta_records_file(self._h, os.fsencode(path), int(begin), end, int(chunk_bytes)))
+
+    def fasta_records_stats(self):
+        """What the last record-mode ingest did beside ``ingest_stats()``: records, sequence lines, the longest record, the
+        owned bytes [first_byte, end_byte) and the bytes the host read to find them."""
+        out = FastaRecordsStats()
+        self._chk(self._lib.dbg_fasta_records_stats(self._h, C.byref(out)))
         return out.as_dict()
 
     def set_reads_device(self, bases_ptr, n_bytes, offsets_ptr, n_reads, keepalive=()):
@@ -641,17 +683,21 @@ class Graph:
                                                         C.byref(total)))
         return off, chars
 
-    def write_contigs_fasta(self, path, indices=None, append=True, first_number=0, k_label=0, chunk_bytes=0):
+    def write_contigs_fasta(self, path, indices=None, append=True, first_number=0, k_label=0, chunk_bytes=0, line_width=0):
         """Writes ``>SEQUENCE_{first_number + i}_{k_label}mer`` records of the contigs ``indices`` of the last walk (None: all
         of them in the driver's order, score descending and stable) to ``path``, streamed window by window; -> bytes written.
-        ``k_label`` 0: the graph's k; ``chunk_bytes`` 0: the library default."""
+        ``k_label`` 0: the graph's k; ``chunk_bytes`` 0: the library default; ``line_width`` W > 0: every contig in lines of
+        W characters (``debruijn.wrap_fasta_record``), 0: on one line."""
+        if not 0 <= int(line_width) < (1 << 32):
+            raise ValueError(f"line_width must be 0..2**32-1, not {line_width!r}")
         idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
         n_idx = 0 if idx is None else idx.size
         if idx is not None and not idx.size:
             idx = np.zeros(1, dtype=np.uint64)  # an empty list is not "all of them": a pointer, and n = 0
         n = C.c_uint64()
-        self._chk(self._lib.dbg_write_contigs_fasta(self._h, os.fsencode(path), 1 if append else 0, _ptr(idx), n_idx,
-                                                    int(first_number), int(k_label), int(chunk_bytes), C.byref(n)))
+        self._chk(self._lib.dbg_write_contigs_fasta_wrapped(self._h, os.fsencode(path), 1 if append else 0, _ptr(idx), n_idx,
+                                                            int(first_number), int(k_label), int(chunk_bytes),
+                                                            int(line_width), C.byref(n)))
         return int(n.value)
 
     def contig_output_stats(self):

@@ -90,6 +90,37 @@ DBG_CO_HD inline char co_fixed_char(CoWhere w, uint64_t number, uint32_t n_digit
     }
 }
 
+// ---- wrapped records (dbg_write_contigs_fasta_wrapped): the contig in lines of line_width characters ------------------------
+// bytes of a record's body, the contig and its line ends: every line ends with '\n', the last may be shorter, a contig of
+// no characters keeps its one '\n' and a contig of a whole number of lines gets no empty line.  line_width 0: one line.
+DBG_CO_HD inline uint64_t co_body_len(uint64_t len, uint32_t line_width) {
+    if (!line_width || !len) return len + 1ull;
+    return len + (len + line_width - 1ull) / line_width;
+}
+
+DBG_CO_HD inline uint64_t co_record_len_wrapped(uint64_t number, uint32_t k_digits, uint64_t len, uint32_t line_width) {
+    return co_header_len(co_digits(number), k_digits) + co_body_len(len, line_width);
+}
+
+// byte q of a body of `body` bytes: false for a '\n', else true and *j = the contig character it holds
+DBG_CO_HD inline bool co_body_char(uint64_t q, uint64_t body, uint32_t line_width, uint64_t *j) {
+    if (q + 1 == body) return false;
+    if (!line_width) { *j = q; return true; }
+    const uint64_t line = q / (line_width + 1ull);
+    if (q - line * (line_width + 1ull) == line_width) return false;
+    *j = q - line;
+    return true;
+}
+
+// co_field_at for a wrapped record: CO_TEXT carries the contig character, CO_NEWLINE the byte of the body
+DBG_CO_HD inline CoWhere co_field_at_wrapped(uint64_t rel, uint32_t n_digits, uint32_t k_digits, uint64_t len, uint32_t line_width) {
+    const uint64_t hdr = co_header_len(n_digits, k_digits);
+    if (rel < hdr) return co_field_at(rel, n_digits, k_digits, len);
+    uint64_t j = 0;
+    if (co_body_char(rel - hdr, co_body_len(len, line_width), line_width, &j)) return CoWhere{CO_TEXT, j};
+    return CoWhere{CO_NEWLINE, rel - hdr};
+}
+
 // ---- windows ---------------------------------------------------------------------------------------------------------------
 struct CoWindow {
     uint64_t b0, b1;  // bytes [b0, b1) of the virtual text
@@ -120,6 +151,7 @@ struct CoText {
     uint64_t first_number;  // record i is numbered first_number + i
     uint32_t k_label, k_digits;
     int fasta;              // 0: bare texts
+    uint32_t line_width = 0;  // FASTA records: characters of a line of the contig (0: the contig on one line); set last, by those who wrap
 };
 
 // Last record i in [lo, hi) with pos[i] <= b; needs pos[lo] <= b.  Taking the last skips records of no bytes.
@@ -134,14 +166,16 @@ DBG_CO_HD inline uint64_t co_find_record(const uint64_t *pos, uint64_t lo, uint6
 
 // The CO_RUN bytes from b on (fewer at the end of the text; the rest stay zero), b inside record `rec`, packed little-endian
 // into w[4].  Src spells contigs: first(c, j) is character j of contig c and opens a cursor there, next(j) is the
-// character behind the last one asked for (j counts on: the cursor never jumps).
+// character behind the last one asked for (j counts on: the cursor never jumps -- the '\n' bytes of a wrapped contig ask
+// nothing).
 template <class Src>
 DBG_CO_HD inline void co_fill_run(const CoText &t, uint64_t rec, uint64_t b, Src &src, uint32_t w[4]) {
     w[0] = w[1] = w[2] = w[3] = 0;
     uint64_t rel = b - t.pos[rec];
     uint32_t c = t.list ? t.list[rec] : (uint32_t)rec, nd = 0;
     uint64_t len = t.off[c + 1] - t.off[c], number = t.first_number + rec, hdr = 0, rec_len = len;
-    if (t.fasta) { nd = co_digits(number); hdr = co_header_len(nd, t.k_digits); rec_len = hdr + len + 1; }
+    const uint32_t lw = t.fasta ? t.line_width : 0u;  // bare texts are never wrapped
+    if (t.fasta) { nd = co_digits(number); hdr = co_header_len(nd, t.k_digits); rec_len = hdr + co_body_len(len, lw); }
     bool open = false;
 #if defined(__HIPCC__)
 #pragma unroll  // w[] is indexed by constants: it stays in registers
@@ -154,12 +188,13 @@ DBG_CO_HD inline void co_fill_run(const CoText &t, uint64_t rec, uint64_t b, Src
             c = t.list ? t.list[rec] : (uint32_t)rec;
             len = t.off[c + 1] - t.off[c];
             rec_len = len;
-            if (t.fasta) { number = t.first_number + rec; nd = co_digits(number); hdr = co_header_len(nd, t.k_digits); rec_len = hdr + len + 1; }
+            if (t.fasta) { number = t.first_number + rec; nd = co_digits(number); hdr = co_header_len(nd, t.k_digits); rec_len = hdr + co_body_len(len, lw); }
             open = false;
         }
         char ch;
-        if (rel >= hdr && rel < hdr + len) {
-            ch = open ? src.next(rel - hdr) : src.first(c, rel - hdr);
+        uint64_t j = rel - hdr;
+        if (lw ? (rel >= hdr && co_body_char(rel - hdr, rec_len - hdr, lw, &j)) : (rel >= hdr && rel < hdr + len)) {
+            ch = open ? src.next(j) : src.first(c, j);
             open = true;
         } else {
             ch = co_fixed_char(co_field_at(rel, nd, t.k_digits, len), number, nd, t.k_label, t.k_digits);

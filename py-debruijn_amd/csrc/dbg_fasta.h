@@ -19,7 +19,47 @@
 //
 // Per chunk of n bytes the device holds the text (n + 64), two u32 masks and one u64 rank per 32-byte word
 // (n / 2 bytes) and one byte per 64 KiB block of text: ~1.5 n.
+//
+// Record mode (dbg_set_reads_fasta_records*): a read is a record, the sequence lines between two header lines joined,
+// each rstrip'ed on its own.  What is written and where stays as above -- the bytes of the sequence lines, packed --
+// and one thing changes: the read starts are the header line starts, not the sequence line starts, and a read's offset
+// is the number of written bytes in front of its header.  The host finds the owned bytes [first header at or after
+// begin, first header at or after end) before the first chunk (FaHeaderScan), so the stream begins and ends at a header.
+//
+// The header search is plain C++: a host compiler can include this file alone (tests/fasta_records_host.cpp does).
 #pragma once
+#include <stdint.h>
+
+namespace dbgk {
+
+inline bool fa_space(uint32_t c) {  // str.isspace() over the ASCII range (fs_space below)
+    return c == ' ' || (c >= 9 && c <= 13) || (c >= 28 && c <= 31);
+}
+
+// The first header line start at or after `from`: the first line start p >= from with t[p] == '>'.  Fed the bytes from
+// `from` on, window by window.  first_seq: the first non-space byte fed in front of it (~0: none) -- from 0 on that is
+// sequence before the first header.
+struct FaHeaderScan {
+    uint64_t found = ~0ull;      // ~0: not seen yet
+    uint64_t first_seq = ~0ull;
+    uint32_t prev;               // the byte before the next one fed ('\n' in front of the file)
+
+    explicit FaHeaderScan(uint32_t byte_before) : prev(byte_before) {}
+    // b: the n bytes at file position pos.  True once the start is known.
+    bool feed(const uint8_t *b, uint64_t n, uint64_t pos) {
+        for (uint64_t i = 0; i < n && found == ~0ull; ++i) {
+            const uint32_t c = b[i];
+            if (c == '>' && (prev == '\n' || prev == '\r')) found = pos + i;  // after '\r' a '>' is no '\n': a line start
+            else if (first_seq == ~0ull && !fa_space(c)) first_seq = pos + i;
+            prev = c;
+        }
+        return found != ~0ull;
+    }
+};
+
+}  // namespace dbgk
+
+#if defined(__HIPCC__)
 #include "dbg_device.h"
 
 namespace dbgk {
@@ -154,10 +194,13 @@ __global__ __launch_bounds__(256) void k_fs_carry(uint8_t *blk_f, uint8_t *blk_b
     }
 }
 
-// per word: written bytes (wr) and read starts (rs); pending bytes counted into ck->pend
+// per word: written bytes (wr) and read starts (rs); pending bytes counted into ck->pend.  REC (record mode): the read
+// starts are the header line starts (ls & ~rs), and the sequence line starts of the chunk are summed into *n_seq, one
+// atomic per workgroup.
+template <bool REC>
 __global__ __launch_bounds__(256) void k_fs_count(const char *__restrict__ t, uint64_t n, const FsState *st,
                                                   const uint8_t *blk_f, const uint8_t *blk_b, uint32_t *wr_out,
-                                                  uint32_t *rs_out, FsChunk *ck) {
+                                                  uint32_t *rs_out, FsChunk *ck, unsigned long long *n_seq) {
     __shared__ uint32_t sh[256];
     const uint64_t n_words = (n + 31) / 32;
     const uint64_t w0 = (uint64_t)blockIdx.x * FS_WPB + (uint64_t)threadIdx.x * FS_WPT;
@@ -206,10 +249,23 @@ __global__ __launch_bounds__(256) void k_fs_count(const char *__restrict__ t, ui
             inread |= kind << i;
         }
         wr_out[w] = inread & (yes[j] | open[j]);
-        rs_out[w] = rs[j];
+        rs_out[w] = REC ? ls[j] & ~rs[j] : rs[j];
         pend += __popc(inread & open[j]);
     }
     if (pend) atomicAdd(&ck->pend, (unsigned long long)pend);
+    if constexpr (REC) {
+        uint32_t lines = 0;
+#pragma unroll
+        for (int j = 0; j < FS_WPT; ++j) lines += __popc(rs[j]);
+        __syncthreads();  // the scans above are done with sh
+        sh[threadIdx.x] = lines;
+        __syncthreads();
+        for (uint32_t d = 128; d; d >>= 1) {
+            if (threadIdx.x < d) sh[threadIdx.x] += sh[threadIdx.x + d];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0 && sh[0]) atomicAdd(n_seq, (unsigned long long)sh[0]);
+    }
 }
 
 struct FsPopcPair {  // written bytes in the low half, read starts in the high half (a chunk is < 4 GiB)
@@ -254,4 +310,23 @@ __global__ void k_fs_finish(const char *__restrict__ t, uint64_t n, const FsStat
     out->kind = ck->last_kind;
 }
 
+// record mode, after the last chunk: the longest read, from the finished offsets (offsets[n_reads] is set)
+__global__ __launch_bounds__(256) void k_fs_longest(const uint64_t *__restrict__ offsets, uint64_t n_reads,
+                                                    unsigned long long *out) {
+    __shared__ unsigned long long sh[256];
+    unsigned long long m = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n_reads; i += (uint64_t)gridDim.x * 256) {
+        const unsigned long long len = offsets[i + 1] - offsets[i];
+        if (len > m) m = len;
+    }
+    sh[threadIdx.x] = m;
+    __syncthreads();
+    for (uint32_t d = 128; d; d >>= 1) {
+        if (threadIdx.x < d && sh[threadIdx.x + d] > sh[threadIdx.x]) sh[threadIdx.x] = sh[threadIdx.x + d];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && sh[0]) atomicMax(out, sh[0]);
+}
+
 }  // namespace dbgk
+#endif  // __HIPCC__

@@ -1221,9 +1221,13 @@ struct FastaStream {
     struct HostView {
         FsState st;
         uint64_t flags;
+        uint64_t n_seq;  // record mode: sequence line starts of the last chunk
     };
     dbg *h;
     int fd = -1;
+    const char *mem = nullptr;  // the image in a host buffer instead of a file (fd < 0)
+    bool records = false;       // record mode: a read is a record (dbg_set_reads_fasta_records*)
+    uint64_t *d_nseq = nullptr;
     char *pin[2] = {nullptr, nullptr};
     HostView *hv = nullptr;  // pinned: the state after the last chunk
     hipEvent_t ev_copy[2] = {nullptr, nullptr}, ev_t0 = nullptr, ev_done = nullptr;
@@ -1269,7 +1273,7 @@ struct FastaStream {
         if (hv) (void)hipHostFree(hv);
         for (auto e : {ev_copy[0], ev_copy[1], ev_t0, ev_done}) if (e) (void)hipEventDestroy(e);
         dev_free(d_text); dev_free(d_wr); dev_free(d_rs); dev_free(d_rank); dev_free(d_flags); dev_free(d_blk);
-        dev_free(d_state); dev_free(d_chunk); dev_free(bases); dev_free(offsets);
+        dev_free(d_state); dev_free(d_chunk); dev_free(bases); dev_free(offsets); dev_free(d_nseq);
         (void)hipGetLastError();
     }
 };
@@ -1282,8 +1286,14 @@ static int fasta_parse_chunk(FastaStream &fs, uint64_t n, int si) {
     uint8_t *blk_f = fs.d_blk, *blk_b = fs.d_blk + fs.nblk_cap;
     hipLaunchKernelGGL(k_fs_blocks, dim3((unsigned)nblk), dim3(256), 0, h->stream, fs.d_text, n, in, blk_f, blk_b);
     hipLaunchKernelGGL(k_fs_carry, dim3(1), dim3(256), 0, h->stream, blk_f, blk_b, nblk, in, fs.d_chunk);
-    hipLaunchKernelGGL(k_fs_count, dim3((unsigned)nblk), dim3(256), 0, h->stream, fs.d_text, n, in, (const uint8_t *)blk_f,
-                       (const uint8_t *)blk_b, fs.d_wr, fs.d_rs, fs.d_chunk);
+    if (fs.records) {
+        HIPCHK(h, hipMemsetAsync(fs.d_nseq, 0, 8, h->stream));
+        hipLaunchKernelGGL(k_fs_count<true>, dim3((unsigned)nblk), dim3(256), 0, h->stream, fs.d_text, n, in, (const uint8_t *)blk_f,
+                           (const uint8_t *)blk_b, fs.d_wr, fs.d_rs, fs.d_chunk, (unsigned long long *)fs.d_nseq);
+    } else {
+        hipLaunchKernelGGL(k_fs_count<false>, dim3((unsigned)nblk), dim3(256), 0, h->stream, fs.d_text, n, in, (const uint8_t *)blk_f,
+                           (const uint8_t *)blk_b, fs.d_wr, fs.d_rs, fs.d_chunk, (unsigned long long *)nullptr);
+    }
     CHK(exclusive_scan(h, words, FsPopcPair{fs.d_wr, fs.d_rs}, fs.d_rank, (uint64_t *)nullptr));
     const uint64_t *total = (const uint64_t *)h->ar_scan.p + std::max<uint64_t>((words + SCAN_TILE - 1) / SCAN_TILE, 1);
     hipLaunchKernelGGL(k_fs_write, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, fs.d_text, n, in,
@@ -1294,31 +1304,88 @@ static int fasta_parse_chunk(FastaStream &fs, uint64_t n, int si) {
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(&fs.hv->st, fs.d_state + (si ^ 1), sizeof(FsState), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(&fs.hv->flags, fs.d_flags, 8, hipMemcpyDeviceToHost, h->stream));
+    if (fs.records) HIPCHK(h, hipMemcpyAsync(&fs.hv->n_seq, fs.d_nseq, 8, hipMemcpyDeviceToHost, h->stream));
     return DBG_OK;
 }
 
-extern "C" int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t begin, uint64_t end, uint64_t chunk_bytes) {
-    if (!h) return DBG_E_ARG;
+// bytes [off, off + len) of the stream's source, a file or a host buffer of `size` bytes: short only at its end
+static int64_t fasta_src_read(const FastaStream &fs, uint64_t size, char *buf, uint64_t len, uint64_t off) {
+    if (fs.fd >= 0) return pread_full(fs.fd, buf, len, off);
+    const uint64_t got = off < size ? std::min(len, size - off) : 0;
+    if (got) memcpy(buf, fs.mem + off, got);
+    return (int64_t)got;
+}
+
+// record mode: the header line start at or after `from` (`size` if none), by windows with the byte in front as prev.
+// *first_seq: the first non-space byte in front of it (~0: none); *scanned counts the bytes read.
+static int fasta_header_start(const FastaStream &fs, uint64_t size, uint64_t from, uint64_t *out, uint64_t *first_seq,
+                              uint64_t *scanned) {
+    *out = size;
+    *first_seq = ~0ull;
+    if (from >= size) return 0;
+    std::vector<uint8_t> win(1 << 16);
+    uint32_t prev = '\n';  // before the file: byte 0 starts a line
+    if (from) {
+        if (fasta_src_read(fs, size, (char *)win.data(), 1, from - 1) != 1) return -1;
+        prev = win[0];
+        ++*scanned;
+    }
+    FaHeaderScan scan(prev);
+    for (uint64_t pos = from; pos < size; pos += win.size()) {
+        const uint64_t len = std::min<uint64_t>(win.size(), size - pos);
+        if (fasta_src_read(fs, size, (char *)win.data(), len, pos) != (int64_t)len) return -1;
+        *scanned += len;
+        const bool hit = scan.feed(win.data(), len, pos);
+        *first_seq = scan.first_seq;
+        if (hit) { *out = scan.found; return 0; }
+    }
+    return 0;
+}
+
+// the streamed ingest of a file (path) or of an image in a host buffer (mem, mem_size), in line or in record mode
+static int fasta_stream_ingest(dbg *h, const char *what, const char *path, const char *mem, uint64_t mem_size, uint64_t begin,
+                               uint64_t end, uint64_t chunk_bytes, bool records) {
     using clk = std::chrono::steady_clock;
     const auto t_call = clk::now();
-    if (!path) { h->err = "set_reads_fasta_file: no path"; return DBG_E_ARG; }
+    const std::string call(what);
+    if (!path && !mem && mem_size) { h->err = call + (records ? ": no text" : ": no path"); return DBG_E_ARG; }
     if (begin > end) {
-        h->err = "set_reads_fasta_file: begin " + std::to_string(begin) + " > end " + std::to_string(end);
+        h->err = call + ": begin " + std::to_string(begin) + " > end " + std::to_string(end);
         return DBG_E_ARG;
     }
     HIPCHK(h, hipSetDevice(h->device));
     FastaStream fs(h);
-    fs.fd = open(path, O_RDONLY | O_CLOEXEC);
-    if (fs.fd < 0) { h->err = std::string(path) + ": " + strerror(errno); return DBG_E_ARG; }
-    struct stat sb;
-    if (fstat(fs.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { h->err = std::string(path) + ": not a readable regular file"; return DBG_E_ARG; }
-    const uint64_t size = (uint64_t)sb.st_size;
-    const uint64_t lim = std::min(end, size);      // line starts at or past lim are not owned: they end the last owned line
-    const uint64_t start = std::min(begin, size);
+    fs.records = records;
+    fs.mem = mem;
+    uint64_t size = mem_size;
+    const std::string name(path ? path : "text");
+    if (path) {
+        fs.fd = open(path, O_RDONLY | O_CLOEXEC);
+        if (fs.fd < 0) { h->err = name + ": " + strerror(errno); return DBG_E_ARG; }
+        struct stat sb;
+        if (fstat(fs.fd, &sb) != 0 || !S_ISREG(sb.st_mode)) { h->err = name + ": not a readable regular file"; return DBG_E_ARG; }
+        size = (uint64_t)sb.st_size;
+    }
+    uint64_t lim = std::min(end, size);      // line starts at or past lim are not owned: they end the last owned line
+    uint64_t start = std::min(begin, size);
     uint32_t prev = '\n';                          // before the file: byte 0 starts a line
-    if (start > 0 && start < size) {
+    uint64_t scan_bytes = 0;
+    if (records) {  // the owned bytes: from the first header at or after begin to the first at or after end
+        uint64_t seq0 = ~0ull, seq1 = ~0ull;
+        if (fasta_header_start(fs, size, start, &start, &seq0, &scan_bytes) != 0 ||
+            fasta_header_start(fs, size, std::max(lim, start), &lim, &seq1, &scan_bytes) != 0) {
+            h->err = name + ": read failed: " + strerror(errno);
+            return DBG_E_ARG;
+        }
+        if (begin == 0 && seq0 != ~0ull) {
+            free_build(h);
+            free_reads(h);
+            h->err = call + ": " + name + ": malformed FASTA: sequence before the first header at byte " + std::to_string(seq0);
+            return DBG_E_ARG;
+        }
+    } else if (start > 0 && start < size) {
         char c;
-        if (pread_full(fs.fd, &c, 1, start - 1) != 1) { h->err = std::string(path) + ": read failed: " + strerror(errno); return DBG_E_ARG; }
+        if (pread_full(fs.fd, &c, 1, start - 1) != 1) { h->err = name + ": read failed: " + strerror(errno); return DBG_E_ARG; }
         prev = (uint8_t)c;
     }
     uint64_t chunk = chunk_bytes ? std::min(chunk_bytes, FS_MAX_CHUNK) : FS_DEFAULT_CHUNK;
@@ -1326,14 +1393,21 @@ extern "C" int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t beg
     free_reads(h);
     h->ingest = dbg_ingest_stats_t{};
     h->ingest.chunk_bytes = chunk;
-    h->ingest.bytes_read = (start > 0 && start < size) ? 1 : 0;
+    h->ingest.bytes_read = records ? scan_bytes : (start > 0 && start < size) ? 1 : 0;
+    if (records) {
+        h->fasta_rec = dbg_fasta_records_stats_t{};
+        h->fasta_rec.first_byte = start;
+        h->fasta_rec.end_byte = lim;
+        h->fasta_rec.scan_bytes = scan_bytes;
+    }
 
     // staging and parse state for chunks of up to `stage` bytes
-    fs.stage = std::max<uint64_t>(std::min(chunk, size - start), 1);
+    fs.stage = std::max<uint64_t>(std::min(chunk, (records ? lim : size) - start), 1);
     fs.words_cap = (fs.stage + 31) / 32;
     fs.nblk_cap = (fs.words_cap + FS_WPB - 1) / FS_WPB;
     for (auto &p : fs.pin) HIPCHK(h, hipHostMalloc((void **)&p, fs.stage, hipHostMallocDefault));
     HIPCHK(h, hipHostMalloc((void **)&fs.hv, sizeof(FastaStream::HostView), hipHostMallocDefault));
+    if (records) CHK(fs.alloc(&fs.d_nseq, 1));
     for (auto *e : {&fs.ev_copy[0], &fs.ev_copy[1], &fs.ev_t0, &fs.ev_done}) HIPCHK(h, hipEventCreate(e));
     CHK(fs.alloc(&fs.d_text, fs.stage + 64));
     CHK(fs.alloc(&fs.d_wr, fs.words_cap));
@@ -1352,11 +1426,13 @@ extern "C" int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t beg
     CHK(fs.alloc(&fs.offsets, fs.off_cap));
     HIPCHK(h, hipMemsetAsync(fs.d_flags, 0, 8, h->stream));
     for (auto e : fs.ev_copy) HIPCHK(h, hipEventRecord(e, h->stream));  // "buffer free" holds from the start
-    fs.hv->st = FsState{0, 0, 0, prev, 0};
+    fs.hv->st = FsState{0, 0, 0, prev, 0};  // record mode: the stream begins at a header line start
+    fs.hv->n_seq = 0;
     HIPCHK(h, hipMemcpyAsync(fs.d_state, &fs.hv->st, sizeof(FsState), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
 
-    uint64_t stop = lim >= size ? size : UINT64_MAX;  // first line start at or past lim (UINT64_MAX: not seen yet)
+    // first line start at or past lim (UINT64_MAX: not seen yet); record mode knows it: the stream ends at a header
+    uint64_t stop = (records || lim >= size) ? lim : UINT64_MAX;
     uint32_t host_prev = prev;                         // the byte before the next chunk
     double ms_io = 0;
     auto read_chunk = [&](int b, uint64_t pos, uint64_t &len) -> int {
@@ -1364,9 +1440,9 @@ extern "C" int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t beg
         len = pos < limit ? std::min(fs.stage, limit - pos) : 0;
         if (!len) return DBG_OK;
         const auto t0 = clk::now();
-        const int64_t got = pread_full(fs.fd, fs.pin[b], len, pos);
+        const int64_t got = fasta_src_read(fs, size, fs.pin[b], len, pos);
         ms_io += std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-        if (got < 0) { h->err = std::string(path) + ": read failed: " + strerror(errno); return DBG_E_ARG; }
+        if (got < 0) { h->err = name + ": read failed: " + strerror(errno); return DBG_E_ARG; }
         len = (uint64_t)got;  // short: the file ended early
         h->ingest.bytes_read += len;
         if (stop == UINT64_MAX && pos + len > lim) {  // the last owned line ends at the first line start at or past lim
@@ -1385,7 +1461,7 @@ extern "C" int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t beg
         return std::max<uint64_t>({at_least, fs.off_cap + fs.off_cap / 2, (uint64_t)proj});
     };
 
-    uint64_t len[2] = {0, 0}, pos = start;
+    uint64_t len[2] = {0, 0}, pos = start, n_seq_lines = 0;
     CHK(read_chunk(0, pos, len[0]));
     FsState hs = fs.hv->st;
     int b = 0, si = 0;
@@ -1423,8 +1499,9 @@ extern "C" int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t beg
             (void)hipEventElapsedTime(&c, fs.ev_t0, fs.ev_done);
             ms_parse += c;
         }
-        if (fs.hv->flags) { h->err = "set_reads_fasta_file: packed bases overran their buffer (internal error)"; return DBG_E_HIP; }
+        if (fs.hv->flags) { h->err = call + ": packed bases overran their buffer (internal error)"; return DBG_E_HIP; }
         hs = fs.hv->st;
+        n_seq_lines += fs.hv->n_seq;
         si ^= 1;
         b ^= 1;
         pos = npos;
@@ -1432,7 +1509,22 @@ extern "C" int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t beg
     }
     const uint64_t n_reads = hs.n_reads, n_bases = hs.cursor;  // the pending white space of the last line is dropped
     HIPCHK(h, hipMemcpyAsync(fs.offsets + n_reads, &n_bases, 8, hipMemcpyHostToDevice, h->stream));
+    if (records) {
+        HIPCHK(h, hipMemsetAsync(fs.d_nseq, 0, 8, h->stream));
+        if (n_reads) {
+            const unsigned grid = (unsigned)std::min<uint64_t>(grid_for(n_reads, 256), 1024);
+            hipLaunchKernelGGL(k_fs_longest, dim3(grid), dim3(256), 0, h->stream, (const uint64_t *)fs.offsets, n_reads,
+                               (unsigned long long *)fs.d_nseq);
+            HIPCHK(h, hipGetLastError());
+        }
+        HIPCHK(h, hipMemcpyAsync(&fs.hv->n_seq, fs.d_nseq, 8, hipMemcpyDeviceToHost, h->stream));
+    }
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (records) {
+        h->fasta_rec.n_records = n_reads;
+        h->fasta_rec.n_sequence_lines = n_seq_lines;
+        h->fasta_rec.longest_record = fs.hv->n_seq;
+    }
     h->d_bases = fs.bases;
     h->own_bases = true;
     h->d_offsets = fs.offsets;
@@ -1451,6 +1543,30 @@ extern "C" int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t beg
     const int rc = make_startbits(h);
     h->ingest.ms_total = std::chrono::duration<double, std::milli>(clk::now() - t_call).count();
     return rc;
+}
+
+extern "C" int dbg_set_reads_fasta_file(dbg_t *h, const char *path, uint64_t begin, uint64_t end, uint64_t chunk_bytes) {
+    if (!h) return DBG_E_ARG;
+    if (!path) { h->err = "set_reads_fasta_file: no path"; return DBG_E_ARG; }
+    return fasta_stream_ingest(h, "set_reads_fasta_file", path, nullptr, 0, begin, end, chunk_bytes, false);
+}
+
+extern "C" int dbg_set_reads_fasta_records_file(dbg_t *h, const char *path, uint64_t begin, uint64_t end, uint64_t chunk_bytes) {
+    if (!h) return DBG_E_ARG;
+    if (!path) { h->err = "set_reads_fasta_records_file: no path"; return DBG_E_ARG; }
+    return fasta_stream_ingest(h, "set_reads_fasta_records_file", path, nullptr, 0, begin, end, chunk_bytes, true);
+}
+
+// the whole image in a host buffer: one range through the same stream (the buffer is staged chunk by chunk)
+extern "C" int dbg_set_reads_fasta_records(dbg_t *h, const char *text, uint64_t n_text) {
+    if (!h || (n_text && !text)) return DBG_E_ARG;
+    return fasta_stream_ingest(h, "set_reads_fasta_records", nullptr, text, n_text, 0, UINT64_MAX, 0, true);
+}
+
+extern "C" int dbg_fasta_records_stats(dbg_t *h, dbg_fasta_records_stats_t *out) {
+    if (!h || !out) return DBG_E_ARG;
+    *out = h->fasta_rec;
+    return DBG_OK;
 }
 
 extern "C" int dbg_fasta_ingest_stats(dbg_t *h, dbg_ingest_stats_t *out) {
@@ -6995,9 +7111,12 @@ struct CoRecLen {  // bytes of record i of the list
     uint64_t first_number;
     uint32_t k_digits;
     int fasta;
+    uint32_t line_width;
     __device__ uint64_t operator()(uint64_t i) const {
         const uint32_t c = list[i];
-        return co_record_len(fasta != 0, first_number + i, k_digits, off[c + 1] - off[c]);
+        const uint64_t len = off[c + 1] - off[c];
+        if (fasta && line_width) return co_record_len_wrapped(first_number + i, k_digits, len, line_width);
+        return co_record_len(fasta != 0, first_number + i, k_digits, len);
     }
 };
 
@@ -7065,7 +7184,7 @@ static int ctgout_layout(CtgOut &co, const uint64_t *indices, uint64_t n, CoText
     t.pos = co.d_pos;
     t.off = h->d_ctg_off;
     t.n = n;
-    CHK(exclusive_scan(h, n, CoRecLen{co.d_list, h->d_ctg_off, t.first_number, t.k_digits, t.fasta}, co.d_pos, &t.total));
+    CHK(exclusive_scan(h, n, CoRecLen{co.d_list, h->d_ctg_off, t.first_number, t.k_digits, t.fasta, t.line_width}, co.d_pos, &t.total));
     if (offsets_out) {
         HIPCHK(h, hipMemcpyAsync(offsets_out, co.d_pos, n * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -7223,6 +7342,12 @@ extern "C" int dbg_export_contig_texts(dbg_t *h, const uint64_t *indices, uint64
 
 extern "C" int dbg_write_contigs_fasta(dbg_t *h, const char *path, int append, const uint64_t *indices, uint64_t n,
                                        uint64_t first_number, int k_label, uint64_t chunk_bytes, uint64_t *bytes_written) {
+    return dbg_write_contigs_fasta_wrapped(h, path, append, indices, n, first_number, k_label, chunk_bytes, 0, bytes_written);
+}
+
+extern "C" int dbg_write_contigs_fasta_wrapped(dbg_t *h, const char *path, int append, const uint64_t *indices, uint64_t n,
+                                               uint64_t first_number, int k_label, uint64_t chunk_bytes, uint32_t line_width,
+                                               uint64_t *bytes_written) {
     if (!h) return DBG_E_ARG;
     using clk = std::chrono::steady_clock;
     const auto t_call = clk::now();
@@ -7246,6 +7371,7 @@ extern "C" int dbg_write_contigs_fasta(dbg_t *h, const char *path, int append, c
     if (!n) return DBG_OK;
     CoText t{};
     ctgout_fasta(t, h, first_number, k_label);
+    t.line_width = line_width;
     CHK(ctgout_layout(co, indices, n, t, nullptr));
     const int rc = ctgout_dispatch(co, t, chunk, nullptr, path);
     if (bytes_written) *bytes_written = h->ctgout.bytes_written;

@@ -303,6 +303,7 @@ struct dbg {
     dbg_stats_t stats{};
     dbg_ingest_stats_t ingest{};  // the last FASTA or FASTQ ingest
     dbg_fastq_stats_t fastq{};    // the last FASTQ ingest (dbg_set_reads_fastq_file)
+    dbg_fasta_records_stats_t fasta_rec{};  // the last record-mode FASTA ingest (dbg_set_reads_fasta_records[_file])
     dbg_contig_out_stats_t ctgout{};  // the last streamed contig output (dbg_ctgout.h)
     uint64_t ctgout_chunk = 0;        // option "ctgout_chunk_bytes": window size where a call names none (0: CO_DEFAULT_CHUNK)
 };

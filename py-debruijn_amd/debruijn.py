@@ -31,7 +31,7 @@ import numpy as np
 
 import _dbg
 
-__all__ = ["Node", "read_reads", "read_fastq", "read_reads_device", "DeviceReads", "construct_graph", "output_contigs",
+__all__ = ["Node", "read_reads", "read_fastq", "read_fasta_records", "wrap_fasta_record", "read_reads_device", "DeviceReads", "construct_graph", "output_contigs",
            "get_score_device", "score_sequences", "get_kmers", "get_graph_from_kmers"]
 
 
@@ -111,6 +111,53 @@ def read_fastq(fname, min_quality=0):
         return [r.decode("latin-1") for r in parse_fastq(fh.read(), min_quality)]
 
 
+class FastaError(ValueError):
+    """A malformed FASTA file in record mode: ``kind``, the 0-based ``line`` and the byte position ``pos`` of the first
+    offending byte."""
+
+    def __init__(self, kind, line, pos=None):
+        super().__init__(f"malformed FASTA: {kind}: line {line}" + ("" if pos is None else f", byte {pos}"))
+        self.kind, self.line, self.pos = kind, line, pos
+
+
+def parse_fasta_records(data):
+    """The record rules of ``dbg_set_reads_fasta_records`` (include/dbg.h) over the bytes of a file, in plain Python ->
+    list of bytes reads, one per header.  Lines are universal-newline lines; a header is a line whose first byte is ``>``;
+    read i is the sequence lines between header i and the next header (or the end of the file) joined, each rstrip'ed on
+    its own, so a blank line adds nothing and a header followed at once by a header gives an empty read.  Lines in front
+    of the first header must be blank after rstrip: anything else raises ``FastaError``."""
+    reads, cur, pos = [], None, 0
+    for ln, line in enumerate(bytes(data).splitlines(keepends=True)):  # bytes.splitlines: \n, \r and \r\n only
+        if line[:1] == b">":
+            cur = []
+            reads.append(cur)
+        else:
+            body = line.rstrip(_FQ_SPACE)
+            if cur is not None:
+                cur.append(body)
+            elif body:
+                raise FastaError("sequence before the first header", ln, pos + len(line) - len(line.lstrip(_FQ_SPACE)))
+        pos += len(line)
+    return [b"".join(r) for r in reads]
+
+
+def read_fasta_records(fname):
+    """The reads of a FASTA file with one read per RECORD, as ``read_reads`` gives one per line: a list of str on the host
+    (no GPU needed).  This is what a line-wrapped file means; see ``parse_fasta_records`` for the rules."""
+    with open(fname, "rb") as fh:
+        return [r.decode("latin-1") for r in parse_fasta_records(fh.read())]
+
+
+def wrap_fasta_record(text, line_width):
+    """The body of a FASTA record as ``write_contigs_fasta(line_width=)`` writes it: ``text`` in lines of ``line_width``
+    characters, each ended by a newline, the last possibly shorter.  An empty text is one newline, a text of a whole
+    number of lines gets no empty line, and ``line_width`` 0 puts the text on one line.  str in, str out; bytes likewise."""
+    nl = "\n" if isinstance(text, str) else b"\n"
+    if line_width <= 0 or not len(text):
+        return text + nl
+    return type(nl)().join(text[i:i + line_width] + nl for i in range(0, len(text), line_width))
+
+
 # Files of at least this many bytes stream to the device in chunks (dbg_set_reads_fasta_file) instead of going over in one
 # image (dbg_set_reads_fasta, which holds ~2.5x the file on the device at its peak).  The reads are the same either way.
 STREAM_MIN_BYTES = int(os.environ.get("DBG_STREAM_MIN_BYTES", str(1 << 30)))
@@ -145,10 +192,15 @@ class DeviceReads:
     every read is followed by its reverse complement (``both_strands``; ``Graph.add_revcomp``): the object lists
     r0, rc(r0), r1, rc(r1), ... and ``revcomp_stats`` holds what the pass did.  Cutting before complementing gives the same
     pieces as the other order.
+
+    records="line" (default): every line that is no header is a read, as in the reference.  "record": read i is record i,
+    the sequence lines between header i and the next header joined (``read_fasta_records`` states the rules) -- what a
+    line-wrapped file means.  A byte range then owns the records whose header starts in it, ``records_stats`` holds what
+    the ingest did, and ``origins()`` speaks of records and of positions in the joined read.  FASTA only.
     """
 
     def __init__(self, fname, byte_range=None, chunk_bytes=None, non_acgt="keep", fold_case=False, format="fasta",
-                 min_quality=0, strands="forward"):
+                 min_quality=0, strands="forward", records="line"):
         if non_acgt not in ("keep", "split"):
             raise ValueError(f"non_acgt must be 'keep' or 'split', not {non_acgt!r}")
         if strands not in ("forward", "both"):
@@ -157,11 +209,24 @@ class DeviceReads:
             raise ValueError(f"format must be 'fasta' or 'fastq', not {format!r}")
         if min_quality and format != "fastq":
             raise ValueError("min_quality needs format='fastq'")
+        if records not in ("line", "record"):
+            raise ValueError(f"records must be 'line' or 'record', not {records!r}")
+        if records == "record" and format == "fastq":
+            raise ValueError("records='record' needs format='fasta': a FASTQ read is a record already")
         self._graph = _dbg.Graph()
-        if format == "fastq":
+        self.records_stats = None
+        one_image = byte_range is None and chunk_bytes is None and os.path.getsize(fname) < STREAM_MIN_BYTES
+        if records == "record":
+            if one_image:
+                self._graph.set_reads_fasta_records(fname)
+            else:
+                begin, end = (0, None) if byte_range is None else byte_range
+                self._graph.set_reads_fasta_records_file(fname, begin, end, chunk_bytes or 0)
+            self.records_stats = self._graph.fasta_records_stats()
+        elif format == "fastq":
             begin, end = (0, None) if byte_range is None else byte_range
             self._graph.set_reads_fastq_file(fname, begin, end, chunk_bytes or 0, min_quality)
-        elif byte_range is None and chunk_bytes is None and os.path.getsize(fname) < STREAM_MIN_BYTES:
+        elif one_image:
             self._graph.set_reads_fasta(fname)
         else:
             begin, end = (0, None) if byte_range is None else byte_range
@@ -172,8 +237,8 @@ class DeviceReads:
         self._host = None
 
     def origins(self):
-        """non_acgt="split": (read_index, pos) uint64 arrays -- the read of the file (the line, headers not counted;
-        within the byte range) every piece came from and the position of its first byte in it.
+        """non_acgt="split": (read_index, pos) uint64 arrays -- the read of the file (the line, headers not counted, or
+        with records="record" the record and the position in its joined read; within the byte range) every piece came from and the position of its first byte in it.
         strands="both": entry j is strand ``j & 1`` of piece ``j >> 1``, pos in forward orientation."""
         if self.split_stats is None:
             raise ValueError("origins() needs non_acgt='split'")
@@ -218,10 +283,10 @@ class DeviceReads:
 
 
 def read_reads_device(fname, byte_range=None, chunk_bytes=None, non_acgt="keep", fold_case=False, format="fasta",
-                      min_quality=0, strands="forward"):
+                      min_quality=0, strands="forward", records="line"):
     """``read_reads`` (debruijn.py:22-32) without leaving the GPU; see DeviceReads (byte ranges, streamed ingest, the
-    split at bytes that are not bases, FASTQ files and their quality mask, both strands)."""
-    return DeviceReads(fname, byte_range, chunk_bytes, non_acgt, fold_case, format, min_quality, strands)
+    split at bytes that are not bases, FASTQ files and their quality mask, both strands, one read per record)."""
+    return DeviceReads(fname, byte_range, chunk_bytes, non_acgt, fold_case, format, min_quality, strands, records)
 
 
 _ACGT_RUNS = re.compile(b"[ACGT]+")
@@ -559,11 +624,22 @@ class ContigList(list):
     _graph = None
     _generation = None
     _walk = None
+    _index = None  # contig of the walk behind every position of the list
 
     def sorted_fasta(self):
         if self._graph is None or self._generation != self._graph.generation or self._walk != self._graph.walks:
             raise ValueError("the device contigs of this list are gone (the handle built another graph or walked again)")
         return self._graph.export_sorted_fasta()[0].decode("latin-1")
+
+    def write_fasta(self, path, k, order=None, append=True, line_width=0):
+        """``>SEQUENCE_{i}_{k}mer`` records of the positions ``order`` of this list (None: as it stands), formatted on the
+        device and streamed to ``path`` (``Graph.write_contigs_fasta``); ``line_width`` W > 0 wraps every contig at W
+        characters.  Valid until the graph handle builds or walks again, like ``sorted_fasta``."""
+        if self._graph is None or self._generation != self._graph.generation or self._walk != self._graph.walks:
+            raise ValueError("the device contigs of this list are gone (the handle built another graph or walked again)")
+        pos = np.arange(len(self)) if order is None else np.asarray(order, dtype=np.int64)
+        return self._graph.write_contigs_fasta(path, np.asarray(self._index, dtype=np.uint64)[pos], append=append, k_label=k,
+                                               line_width=line_width)
 
 
 MAX_CONTIG_CHARS = 0  # dbg_walk's max_chars; 0 = the library default (1 GiB of contig text kept on the device)
@@ -756,10 +832,11 @@ class LazyContigs(Sequence):
             np.cumsum(np.concatenate(lens), out=offsets[1:])
         return (np.concatenate(chars) if chars else np.zeros(0, dtype=np.uint8)), offsets
 
-    def write_fasta(self, path, k, append=True):
+    def write_fasta(self, path, k, append=True, line_width=0):
         """The driver's loop over this sequence (``>SEQUENCE_{i}_{k}mer`` records, II_assembleFromReads.py:65-69) written to
         ``path``: the main part and every tail block are formatted on the device of the graph that holds them and
-        streamed to the file (dbg_write_contigs_fasta), runs of plain strings are written by the host in between."""
+        streamed to the file (dbg_write_contigs_fasta), runs of plain strings are written by the host in between.
+        ``line_width`` W > 0 wraps every contig at W characters, on both routes (``wrap_fasta_record``)."""
         open(path, "a" if append else "w").close()
         for first, item in self._segments():
             if not len(item):
@@ -769,11 +846,12 @@ class LazyContigs(Sequence):
                 g = item._graph  # the writer takes bare indices: they must still be those of the walk the block came from
                 if item._generation is not None and (g.generation != item._generation or g.walks != item._walk):
                     raise RuntimeError("the device contigs of this list are gone (the handle built another graph or walked again)")
-                write(path, item._idx, append=True, first_number=first, k_label=k)
+                wrap = {"line_width": line_width} if line_width else {}
+                write(path, item._idx, append=True, first_number=first, k_label=k, **wrap)
                 continue
             with open(path, mode="a") as out_file:
                 for j, text in enumerate(item):
-                    out_file.write('>SEQUENCE_{}_{}mer\n{}\n'.format(first + j, k, text))
+                    out_file.write('>SEQUENCE_{}_{}mer\n{}'.format(first + j, k, wrap_fasta_record(text, line_width)))
 
     def _main_block(self):
         return _ContigBlock(self._graph, self._order, np.asarray(self.lengths, dtype=np.int64), self._final, self._generation,
@@ -1063,7 +1141,7 @@ def output_contigs(g, branch_kmer, already_pull_out):
     text = chars.tobytes().decode("latin-1")
     out = ContigList(text[int(off[i]):int(off[i + 1])] for i in order)
     out.scores = [int(score[i]) for i in order]
-    out._graph, out._generation, out._walk = graph, graph.generation, graph.walks
+    out._graph, out._generation, out._walk, out._index = graph, graph.generation, graph.walks, order
     return out
 
 

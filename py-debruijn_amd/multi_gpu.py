@@ -121,7 +121,7 @@ def stamp_bases(dist, n_bytes, device):
 
 
 def set_reads_fasta_shard(g, path, dist, chunk_bytes=0, non_acgt="keep", fold_case=False, format="fasta", min_quality=0,
-                          strands="forward"):
+                          strands="forward", records="line"):
     """Sets this rank's share of the FASTA file at ``path`` as the reads of handle ``g`` (the input of sharded_build).
 
     Rank r of w takes the lines that start in bytes [r*S//w, (r+1)*S//w) of the S-byte file (a line that starts in
@@ -141,7 +141,12 @@ def set_reads_fasta_shard(g, path, dist, chunk_bytes=0, non_acgt="keep", fold_ca
     strands="both": each rank then follows every read of its own with its reverse complement (``Graph.add_revcomp``), after
     its split and before any size is exchanged.  The reverse complements are interleaved, r0, rc(r0), r1, rc(r1), ..., not
     appended behind all reads: a rank's doubled reads are then a contiguous stretch of the doubled reads of the whole file,
-    so the ranks' reads in rank order are still the single handle's reads in file order and the stamp bases stay its."""
+    so the ranks' reads in rank order are still the single handle's reads in file order and the stamp bases stay its.
+
+    records="record": one read per FASTA record (``Graph.set_reads_fasta_records_file``): rank r takes the records whose
+    header line starts in its slice and reads the last of them to its end, so the ranks' reads in rank order are the file's
+    records.  Slices are cut by bytes, not by records: a file of few long records gives unequal ranks (a slice that lies
+    inside one record owns nothing), and nothing here balances them."""
     if non_acgt not in ("keep", "split"):
         raise ValueError(f"non_acgt must be 'keep' or 'split', not {non_acgt!r}")
     if strands not in ("forward", "both"):
@@ -150,10 +155,16 @@ def set_reads_fasta_shard(g, path, dist, chunk_bytes=0, non_acgt="keep", fold_ca
         raise ValueError(f"format must be 'fasta' or 'fastq', not {format!r}")
     if min_quality and format != "fastq":
         raise ValueError("min_quality needs format='fastq'")
+    if records not in ("line", "record"):
+        raise ValueError(f"records must be 'line' or 'record', not {records!r}")
+    if records == "record" and format == "fastq":
+        raise ValueError("records='record' needs format='fasta': a FASTQ read is a record already")
     w, r = dist.get_world_size(), dist.get_rank()
     size = os.path.getsize(path)
     if format == "fastq":
         g.set_reads_fastq_file(path, r * size // w, (r + 1) * size // w, chunk_bytes, min_quality)
+    elif records == "record":
+        g.set_reads_fasta_records_file(path, r * size // w, (r + 1) * size // w, chunk_bytes)
     else:
         g.set_reads_fasta_file(path, r * size // w, (r + 1) * size // w, chunk_bytes)
     if non_acgt == "split":
