@@ -56,7 +56,7 @@ typedef struct dbg dbg_t;
 #define DBG_ABI_VERSION 6 /* not raised for dbg_build_from_walks, nor for the query calls (dbg_lookup_nodes[_device],
                             * dbg_gather_nodes, dbg_score_sequences, dbg_part_lookup_nodes[_device],
                             * dbg_part_score_sequences), nor for dbg_split_reads / dbg_read_origins, nor for dbg_add_revcomp,
-                            * nor for dbg_set_reads_fasta_records[_file] / dbg_fasta_records_stats / dbg_write_contigs_fasta_wrapped: they only add symbols, every earlier call and struct is
+                            * nor for dbg_set_reads_fasta_records[_file] / dbg_fasta_records_stats / dbg_write_contigs_fasta_wrapped, nor for dbg_count_spectrum: they only add symbols, every earlier call and struct is
                             * unchanged, and tests/test_fasta_stream.py pins this number; a binding that needs a new
                             * call fails at symbol lookup on an older library */
 
@@ -178,7 +178,10 @@ int dbg_abi_version(void);
  * "lookup_index" 1: the query calls (dbg_lookup_nodes, dbg_score_sequences) find nodes through the sorted index even where
  * the build's directory would answer (test hook: both ways must agree);
  * "ctgout_chunk_bytes": window size of the contig output calls where they are given none (dbg_export_contig_texts;
- * dbg_write_contigs_fasta with chunk_bytes 0) -- a multiple of 4096, 0 = the library default of 4 MiB. */
+ * dbg_write_contigs_fasta with chunk_bytes 0) -- a multiple of 4096, 0 = the library default of 4 MiB;
+ * "spectrum_variant" 0..3 (A/B and tests; the default is the measured winner): how dbg_count_spectrum's kernel
+ * takes the contention off its hot bins -- 0 plain LDS atomics, 1 one sub-histogram per wave, 2 equal bins of a wave combined
+ * by ballots until every lane is served, 3 one such round for the first lane's bin and plain atomics for the rest. */
 int dbg_set_option(dbg_t *h, const char *name, int64_t value);
 
 /* ---- reads (replaces the `reads` list argument, debruijn.py:206; FASTA
@@ -677,6 +680,46 @@ int dbg_gather_nodes(dbg_t *h, const uint32_t *ids, uint64_t n, uint64_t *keys, 
  * The text goes to the device once; the work is split over the windows of the concatenated text, not over sequences. */
 int dbg_score_sequences(dbg_t *h, const char *chars, const uint64_t *offsets, uint64_t n_seq, uint64_t *scores,
                         uint64_t *first_missing);
+
+/* ---- whole-graph statistics on the device (csrc/dbg_spectrum.h): the numbers someone with real reads looks at first, and
+ *      how `threshold` is chosen (pruningEdges keeps a successor whose count is at least maxCount / threshold).  One
+ *      read-only pass over the counts the graph already holds; nothing of size n_nodes moves or is allocated.  All in the
+ *      reference's terms, for the graph construct_graph(reads, k) builds, before pruning:
+ *        edge spectrum   E[c] = number of (k+1)-mers e with edge_count_table[e] == c.  A build at k counts (k+1)-mers, so
+ *                        this is the exact (k+1)-mer abundance spectrum of the reads: for the 31-mer spectrum build at k = 30.
+ *        out-weight      W[c] = number of nodes whose successor counts sum to c (len(edges[v]) before pruningEdges); W[0]
+ *                        counts the nodes without a successor.  The sum is the number of windows that START at the k-mer:
+ *                        it is NOT the k-mer's multiplicity, because the last k-mer of a read is not counted.
+ *        out-degree      D[d] = number of nodes with d distinct successors (Node.outdegree): 0..4 on ACGT graphs, 0..32 on
+ *                        generic ones.
+ *        kept degree     K[d] = number of nodes with d bits set in the keep mask, over all nodes (pulled ones included):
+ *                        valid after dbg_prune (in parts: after dbg_part_prune on every part that has nodes; a part not
+ *                        yet pruned adds nothing).  Before that K is all zero and pruned == 0.
+ *      Binning: with n_bins = B a count c lands in bin min(c, B - 1): the last bin collects everything at or above B - 1.
+ *      edge_hist[0] is always 0.  The bins are zeroed by every call.
+ *      The host statement of all this is debruijn.count_spectrum on plain dicts (py-debruijn_amd/debruijn.py). */
+typedef struct dbg_spectrum {
+    uint64_t n_nodes;          /* nodes looked at */
+    uint64_t n_edges;          /* distinct (k+1)-mers = sum of E */
+    uint64_t sum_edge_counts;  /* sum of c * E[c] without the clamp; on a whole single graph dbg_sizes_t.n_edge_instances */
+    uint64_t max_edge_count;
+    uint64_t max_out_weight;
+    uint64_t D[33];
+    uint64_t K[33];
+    uint64_t pruned;           /* 1: K is valid */
+    uint64_t n_bins;
+    uint64_t peak_extra_device_bytes; /* the one allocation of the call: the bins and the summary, 16 * n_bins + 560 */
+    double ms_kernel;          /* the memset of the bins and the kernels, by events on the handle's stream */
+} dbg_spectrum_t;
+/* part < 0: the handle's whole graph -- the single graph, or the sum over every part it holds (maxima: the maximum);
+ * part >= 0: that part of a graph in parts.  edge_hist / node_hist: [n_bins] host arrays, either may be NULL (summary
+ * only); out may be NULL.  Works on every graph a handle can hold (dbg_build on every engine and alphabet, dbg_import_graph,
+ * dbg_build_from_walk(s), dbg_build_multipass, dbg_shard_build_multipass[_from], a shard after dbg_shard_apply), before and
+ * after prune, tips, pull reads and walk, and changes nothing the other calls read.  A graph with 0 nodes: DBG_OK, zeros.
+ * DBG_E_ARG (text in dbg_last_error, the handle stays usable) for: no graph; n_bins < 2 or > 2^20; part >= dbg_part_count;
+ * part >= 0 on a single graph; a handle on which dbg_shard_build has run and dbg_shard_apply has not run since (for any
+ * n_shards: the shard's successors are still open). */
+int dbg_count_spectrum(dbg_t *h, int part, uint64_t n_bins, uint64_t *edge_hist, uint64_t *node_hist, dbg_spectrum_t *out);
 
 /* ---- multi-GPU: hash-prefix sharding (no reference counterpart: the reference is one process).
  *      One handle per rank; the caller moves the buffers between ranks (RCCL all-to-all).  Owner

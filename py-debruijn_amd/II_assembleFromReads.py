@@ -3,8 +3,8 @@
 
 Same CLI (``-froot``), same ``{froot}/setting.json`` keys (score_cut, k_lowerlimit,
 k_upperlimit, threshold, source -- II_assembleFromReads.py:32-38; optionally non_acgt,
-fold_case, reads_format, min_quality, strands and fasta_records, see ``debruijn.DeviceReads``, and
-fasta_line_width for the output), same stdout lines and
+fold_case, reads_format, min_quality, strands and fasta_records, see ``debruijn.DeviceReads``,
+fasta_line_width for the output, and spectrum_bins for a ``{froot}/{froot}_k{k}.hist`` per k), same stdout lines and
 the same append-mode FASTA output ``{froot}/{froot}.fasta`` with records
 ``>SEQUENCE_{i}_{k}mer`` (II_assembleFromReads.py:65-69).  Input is the FASTA surface the
 reference keeps commented out at II_assembleFromReads.py:53:
@@ -36,13 +36,23 @@ def get_args():
     return parser.parse_args()
 
 
-def assemble(sequences, k_lowerlimit, k_upperlimit, threshold, out_path=None, line_width=0):
+def write_spectrum(path, edge_hist):
+    """The edge spectrum as lines ``count<TAB>n`` for count 1..B-1; the last line is the clamp bin (B - 1 and above)."""
+    with open(path, mode='w') as out_file:
+        out_file.write(''.join('{}\t{}\n'.format(c, int(edge_hist[c])) for c in range(1, len(edge_hist))))
+
+
+def assemble(sequences, k_lowerlimit, k_upperlimit, threshold, out_path=None, line_width=0, spectrum_bins=0, spectrum_path=None):
     """II_assembleFromReads.py:56-75.  Returns the final, score-sorted contig list.  ``line_width`` W > 0: the contigs of
-    the output file in lines of W characters (``debruijn.wrap_fasta_record``); 0: one line each, as in the reference."""
+    the output file in lines of W characters (``debruijn.wrap_fasta_record``); 0: one line each, as in the reference.
+    ``spectrum_bins`` B > 0: the (k+1)-mer abundance spectrum of every k's graph (``debruijn.count_spectrum``, counted on
+    the device) goes to ``spectrum_path.format(k)``; nothing is printed for it."""
     for k in range(k_lowerlimit, k_upperlimit + 1):
         final = not (k <= k_upperlimit - 1)
         g, pull_out_read, branch_kmer, already_pull_out, edge_count_table = db.construct_graph(
             sequences, k, threshold=threshold, final=final)
+        if spectrum_bins and spectrum_path is not None:
+            write_spectrum(spectrum_path.format(k), db.count_spectrum(g, edge_count_table, spectrum_bins)["edge_hist"])
         contigs = db.output_contigs(g, branch_kmer, already_pull_out)
         if isinstance(contigs, db.LazyContigs):
             # more text than fits the host: the index is sorted (device scores == getScore), no contig text moves
@@ -101,8 +111,14 @@ if __name__ == '__main__':
     line_width = setting.get('fasta_line_width', 0)
     if isinstance(line_width, bool) or not isinstance(line_width, int) or line_width < 0:
         raise ValueError(f"setting.json: fasta_line_width must be a non-negative integer, not {line_width!r}")
+    # "spectrum_bins": B writes {froot}/{froot}_k{k}.hist for every k: the (k+1)-mer abundance spectrum of that k's graph,
+    # lines "count<TAB>n" for count 1..B-1, the last line collecting every count at or above B - 1; stdout and the FASTA stay
+    spectrum_bins = setting.get('spectrum_bins', 0)
+    if isinstance(spectrum_bins, bool) or not isinstance(spectrum_bins, int) or spectrum_bins == 1 or not 0 <= spectrum_bins <= 1 << 20:
+        raise ValueError(f"setting.json: spectrum_bins must be an integer in 2..2**20 (or 0: no spectrum), not {spectrum_bins!r}")
     if 'fasta_records' in setting:
         split['records'] = fasta_records
     sequences = read_reads_device(f'{froot}/input_reads.{reads_format}', format=reads_format, **split)
     print(len(sequences))
-    assemble(sequences, k_lowerlimit, k_upperlimit, threshold, out_path=f'{froot}/{froot}.fasta', line_width=line_width)
+    assemble(sequences, k_lowerlimit, k_upperlimit, threshold, out_path=f'{froot}/{froot}.fasta', line_width=line_width,
+             spectrum_bins=spectrum_bins, spectrum_path=f'{froot}/{froot}_k{{}}.hist')

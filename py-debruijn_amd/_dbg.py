@@ -44,7 +44,7 @@ SYMBOLS = (
     "dbg_export_contig_texts", "dbg_write_contigs_fasta", "dbg_contig_output_stats",
     "dbg_part_set_skeleton", "dbg_part_contig_window", "dbg_part_export_contig_texts", "dbg_part_write_contigs_fasta",
     "dbg_part_final_walk", "dbg_part_final_export",
-    "dbg_split_reads", "dbg_read_origins", "dbg_add_revcomp",
+    "dbg_split_reads", "dbg_read_origins", "dbg_add_revcomp", "dbg_count_spectrum",
 )
 
 
@@ -142,6 +142,21 @@ class RevcompStats(C.Structure):
 # granularities of the both-strands kernel (csrc/dbg_revcomp.h: RC_TILE_BYTES, RC_SLICE_READS); tests aim at them
 RC_TILE_BYTES = 256 * 8 * 16
 RC_SLICE_READS = 1024
+
+
+class Spectrum(C.Structure):
+    """dbg_spectrum_t: the summary of dbg_count_spectrum"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_nodes", "n_edges", "sum_edge_counts", "max_edge_count", "max_out_weight")] + [
+        ("D", C.c_uint64 * 33), ("K", C.c_uint64 * 33)] + [
+        (n, C.c_uint64) for n in ("pruned", "n_bins", "peak_extra_device_bytes")] + [("ms_kernel", C.c_double)]
+
+    def as_dict(self):
+        return {n: (np.array(getattr(self, n), dtype=np.uint64) if n in ("D", "K") else getattr(self, n)) for n, _ in self._fields_}
+
+
+# what the spectrum kernel keeps in LDS and the most bins a call takes (csrc/dbg_spectrum.h: SP_LDS_BINS, SP_MAX_BINS); tests aim at them
+SP_LDS_BINS = 1024
+SP_MAX_BINS = 1 << 20
 
 
 class WalkBlock(C.Structure):
@@ -294,6 +309,7 @@ def load_library():
         "dbg_split_reads": (C.c_int, [H, C.c_uint32, C.POINTER(SplitStats)]),
         "dbg_read_origins": (C.c_int, [H, vp, vp]),
         "dbg_add_revcomp": (C.c_int, [H, C.c_uint32, C.POINTER(RevcompStats)]),
+        "dbg_count_spectrum": (C.c_int, [H, C.c_int, C.c_uint64, vp, vp, C.POINTER(Spectrum)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -790,6 +806,22 @@ class Graph:
         self._chk(self._lib.dbg_score_sequences(self._h, _ptr(c) if c.size else None, _ptr(o), n, _ptr(scores) if n else None,
                                                 _ptr(miss) if n else None))
         return scores, miss
+
+    def count_spectrum(self, n_bins=256, part=None, hists=True):
+        """Edge spectrum, out-weight spectrum and degree distributions of the current graph, counted on the device
+        (dbg_count_spectrum; the definitions: include/dbg.h, the host rule: debruijn.count_spectrum) -> dict of the summary
+        (``D`` and ``K`` as uint64[33]) plus, with ``hists``, ``edge_hist`` and ``node_hist`` as uint64[n_bins].
+        part None: the whole graph (every part of a graph in parts, summed); an int: that part."""
+        n_bins = int(n_bins)
+        out = Spectrum()
+        e = np.zeros(n_bins if hists and 0 < n_bins <= SP_MAX_BINS else 0, dtype=np.uint64)
+        w = np.zeros_like(e)
+        self._chk(self._lib.dbg_count_spectrum(self._h, -1 if part is None else int(part), n_bins, _ptr(e) if e.size else None,
+                                               _ptr(w) if w.size else None, C.byref(out)))
+        d = out.as_dict()
+        if hists:
+            d["edge_hist"], d["node_hist"] = e, w
+        return d
 
     # ---- read-support scores (IV_sortOutputs.py:10-15)
     def support_read_scores(self, read_chars, read_off, scores, is_float, contig_chars, contig_off):

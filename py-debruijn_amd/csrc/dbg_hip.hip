@@ -23,7 +23,8 @@
 //     dbg_nextk.h          dbg_build_from_walk(s)
 //   Everything else stands in this file between them, section by section under banner comments, in the order the
 //   sections rely on: traversal kernels, the ABI of the handle and its reads, build dispatch, the ABI of one graph, the
-//   query side, the LDS engines' host side, shards, multi-pass builds, graphs in parts, scores, contig output.
+//   query side, the LDS engines' host side, shards, multi-pass builds, graphs in parts, scores, contig output, whole-graph
+//   statistics (dbg_count_spectrum).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,6 +56,7 @@
 #include "dbg_fasta.h"
 #include "dbg_readsplit.h"
 #include "dbg_revcomp.h"
+#include "dbg_spectrum.h"
 #include "dbg_fastq.h"
 #include "dbg_lookup.h"
 #include "dbg_ctgout.h"
@@ -1006,6 +1008,7 @@ static void free_build(dbg *h) {
     dev_free(h->d_ctg_seq); dev_free(h->d_ctg_start); dev_free(h->d_lift);
     h->lift_levels = 0;
     h->partial_graph = false;
+    h->shard_open = false;
     h->sk_src.valid = false;
     h->k = 0; h->cap = 0; h->n_nodes = h->n_edges = 0;
     h->pruned = h->tipped = h->pull_reads_done = h->walked = h->walk_indexed = h->walk_sizes_only = false;
@@ -2466,6 +2469,7 @@ extern "C" int dbg_set_option(dbg_t *h, const char *name, int64_t value) {
     if (n == "count_kernel_u64" && value >= 1 && value <= 3) { h->count_kernel_u64 = (int)value; return DBG_OK; }
     if (n == "lookup_index" && (value == 0 || value == 1)) { h->lookup_index = (int)value; return DBG_OK; }
     if (n == "ctgout_chunk_bytes" && value >= 0 && dbgk::co_chunk_ok((uint64_t)value)) { h->ctgout_chunk = (uint64_t)value; return DBG_OK; }
+    if (n == "spectrum_variant" && value >= 0 && value <= 3) { h->spectrum_variant = (int)value; return DBG_OK; }
     if (n == "part_final_walk_steps" && value >= 1) { h->part_final_steps = (uint64_t)value; return DBG_OK; }
     if (n == "shard_node_limit" && value >= 0 && value < (1ll << 29)) { h->shard_node_limit = (uint64_t)value; return DBG_OK; }
     h->err = "unknown option or value out of range: " + n;
@@ -5104,6 +5108,7 @@ static int shard_build_wide(dbg *h, int k, int n_shards, int my_shard, const uin
     for (int d = 0; d < n_shards; ++d) { q_starts[d] = 0; q_counts[d] = 0; }
     *d_q_keys = nullptr;
     h->partial_graph = n_shards > 1;
+    h->shard_open = true;  // until dbg_shard_apply: dbg_count_spectrum refuses the handle
     h->stats.ms_build_total = t_total.stop();
     return DBG_OK;
 }
@@ -5221,6 +5226,7 @@ static int shard_build_wsk(dbg *h, int k, int n_shards, int my_shard, const uint
     for (int d = 0; d < n_shards; ++d) { q_starts[d] = sh.q_start[d]; q_counts[d] = sh.q_cnt[d]; }
     *d_q_keys = h->ar_shard[SHARD_Q_KEYS].p;
     h->partial_graph = n_shards > 1;
+    h->shard_open = true;  // until dbg_shard_apply: dbg_count_spectrum refuses the handle
     h->stats.ms_build_total = t_total.stop();
     return DBG_OK;
 }
@@ -5434,6 +5440,7 @@ extern "C" int dbg_shard_build(dbg_t *h, int k, int n_shards, int my_shard, cons
     for (int d = 0; d < n_shards; ++d) { q_starts[d] = sh.q_start[d]; q_counts[d] = sh.q_cnt[d]; }
     *d_q_keys = h->ar_shard[SHARD_Q_KEYS].p;
     h->partial_graph = n_shards > 1;
+    h->shard_open = true;  // until dbg_shard_apply: dbg_count_spectrum refuses the handle
     h->stats.ms_build_total = t_total.stop();
     return DBG_OK;
 }
@@ -5625,6 +5632,7 @@ extern "C" int dbg_shard_apply(dbg_t *h, const void *d_answers) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (sc0 & STATUS_REMOTE_UNRESOLVED) { h->err = "a remote successor came back unresolved"; return DBG_E_HIP; }
     h->stats.ms_succ += t.stop();
+    h->shard_open = false;
     return finish_graph(h);
 }
 
@@ -7382,6 +7390,104 @@ extern "C" int dbg_write_contigs_fasta_wrapped(dbg_t *h, const char *path, int a
 extern "C" int dbg_contig_output_stats(dbg_t *h, dbg_contig_out_stats_t *out) {
     if (!h || !out) return DBG_E_ARG;
     *out = h->ctgout;
+    return DBG_OK;
+}
+
+// ==========================================================================================
+// Whole-graph statistics (dbg_spectrum.h): edge spectrum, out-weight spectrum, degree and kept-degree distributions of the
+// single graph, of one part or of all parts of a graph in parts.  Read-only: no ensure_dense(), nothing of size n_nodes
+// allocated; the one allocation is the result (16 B a bin + 560 B).
+// ==========================================================================================
+template <class Src>
+static void spectrum_launch(dbg *h, const Src &src, const SpKeep &keep, uint64_t n_bins, unsigned long long *res) {
+    if (!src.n_nodes) return;
+    const unsigned grid = (unsigned)std::min<uint64_t>(grid_for(src.n_nodes, SP_TILE), SP_MAX_GRID);
+    if (h->spectrum_variant == 0)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spectrum<Src, 0>), dim3(grid), dim3(SP_BLOCK), 0, h->stream, src, keep, n_bins, res);
+    else if (h->spectrum_variant == 1)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spectrum<Src, 1>), dim3(grid), dim3(SP_BLOCK), 0, h->stream, src, keep, n_bins, res);
+    else if (h->spectrum_variant == 2)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spectrum<Src, 2>), dim3(grid), dim3(SP_BLOCK), 0, h->stream, src, keep, n_bins, res);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spectrum<Src, 3>), dim3(grid), dim3(SP_BLOCK), 0, h->stream, src, keep, n_bins, res);
+}
+
+// the count source of one graph: g is the handle itself or a part of it (always the CSR of the LDS engines there)
+static void spectrum_of_graph(dbg *h, const dbg *g, const uint8_t *part_flags, uint64_t n_bins, unsigned long long *res) {
+    const uint64_t n = g->n_nodes, ne = g->n_edges;
+    if (g != h || g->dense_pending) {  // as the build left it: 32-bit row pointers
+        spectrum_launch(h, SpCsr<uint32_t>{g->d_rowptr32, g->d_ecnt, n, ne}, SpKeep{part_flags, nullptr}, n_bins, res);
+        return;
+    }
+    const SpKeep keep{g->pruned && g->D != GEN_D ? g->d_flags : nullptr, g->pruned && g->D == GEN_D ? g->d_keepmask : nullptr};
+    if (g->csr_built && g->D == 4 && g->d_rowptr && g->d_ecnt)  // an LDS-engine graph after ensure_dense(): its CSR is still the shorter read
+        spectrum_launch(h, SpCsr<uint64_t>{g->d_rowptr, g->d_ecnt, n, ne}, keep, n_bins, res);
+    else if (g->D == GEN_D)
+        spectrum_launch(h, SpDense<GEN_D>{g->d_cnt, n, ne}, keep, n_bins, res);
+    else
+        spectrum_launch(h, SpDense<4>{g->d_cnt, n, ne}, keep, n_bins, res);
+}
+
+extern "C" int dbg_count_spectrum(dbg_t *h, int part, uint64_t n_bins, uint64_t *edge_hist, uint64_t *node_hist,
+                                  dbg_spectrum_t *out) {
+    if (!h) return DBG_E_ARG;
+    MultiPass *mp = (MultiPass *)h->multipass;
+    if (!h->k && !mp) { h->err = "dbg_count_spectrum: no graph (a build must run first)"; return DBG_E_ARG; }
+    if (n_bins < 2 || n_bins > SP_MAX_BINS) { h->err = "dbg_count_spectrum: n_bins must be in 2..2^20"; return DBG_E_ARG; }
+    if (part >= 0 && !mp) { h->err = "dbg_count_spectrum: part >= 0 on a single graph (pass part < 0)"; return DBG_E_ARG; }
+    if (mp && part >= mp->n_passes) { h->err = "dbg_count_spectrum: no such part"; return DBG_E_ARG; }
+    if (!mp && h->shard_open) { h->err = "dbg_count_spectrum: dbg_shard_apply must run first (the shard's successors are still open)"; return DBG_E_ARG; }
+    HIPCHK(h, hipSetDevice(h->device));
+    dbg_spectrum_t s{};
+    s.n_bins = n_bins;
+    const uint64_t words = sp_result_words(n_bins);
+    std::vector<uint64_t> host(words, 0);
+    uint64_t n_nodes = 0;
+    bool all_pruned = true;
+    if (mp) {
+        for (int p = part < 0 ? 0 : part; p < (part < 0 ? mp->n_passes : part + 1); ++p) {
+            n_nodes += mp->part[p]->n_nodes;
+            if (mp->part[p]->n_nodes && !mp->pflags[p]) all_pruned = false;
+        }
+    } else {
+        n_nodes = h->n_nodes;
+        all_pruned = h->pruned;
+    }
+    s.n_nodes = n_nodes;
+    if (n_nodes) {
+        unsigned long long *res = nullptr;
+        CHK(dev_alloc(h, &res, words));
+        s.peak_extra_device_bytes = words * 8;
+        hipError_t e;
+        {
+            Timer tm(h->stream);
+            e = hipMemsetAsync(res, 0, words * 8, h->stream);  // every call starts from zero bins
+            if (e == hipSuccess) {
+                if (mp) {
+                    for (int p = part < 0 ? 0 : part; p < (part < 0 ? mp->n_passes : part + 1); ++p)
+                        if (mp->part[p]->n_nodes) spectrum_of_graph(h, mp->part[p], mp->pflags[p], n_bins, res);
+                } else {
+                    spectrum_of_graph(h, h, nullptr, n_bins, res);
+                }
+                e = hipGetLastError();
+            }
+            s.ms_kernel = tm.stop();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(host.data(), res, words * 8, hipMemcpyDeviceToHost, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+        dev_free(res);
+        if (e != hipSuccess) { h->err = std::string("dbg_count_spectrum: ") + hipGetErrorString(e); return DBG_E_HIP; }
+    }
+    const uint64_t *deg = host.data() + 2 * n_bins, *sc = deg + 2 * SP_DEG_BINS;
+    if (edge_hist) memcpy(edge_hist, host.data(), n_bins * 8);
+    if (node_hist) memcpy(node_hist, host.data() + n_bins, n_bins * 8);
+    for (uint32_t d = 0; d < SP_DEG_BINS; ++d) { s.D[d] = deg[d]; s.K[d] = deg[SP_DEG_BINS + d]; }
+    s.n_edges = sc[SP_N_EDGES];
+    s.sum_edge_counts = sc[SP_SUM_EDGE_COUNTS];
+    s.max_edge_count = sc[SP_MAX_EDGE_COUNT];
+    s.max_out_weight = sc[SP_MAX_OUT_WEIGHT];
+    s.pruned = n_nodes && all_pruned ? 1 : 0;
+    if (out) *out = s;
     return DBG_OK;
 }
 

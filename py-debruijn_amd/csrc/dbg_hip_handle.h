@@ -272,6 +272,8 @@ struct dbg {
     std::vector<uint64_t> host_scpre;    // multisplit_level: staging that must outlive an asynchronous upload
     uint64_t shard_node_limit = 0;  // option (tests): lowers the 2^29 - 16 node ids a shard may hand out
     bool partial_graph = false;   // the node table is one shard of several: successor ids point into other handles
+    bool shard_open = false;      // dbg_shard_build ran and dbg_shard_apply has not yet: the successors other shards own are unresolved
+    int spectrum_variant = 3;     // option "spectrum_variant": how k_spectrum relieves its hot bins (dbg_spectrum.h; measured: DESIGN.md 4l)
     // branch k-mer lookup (pull-out reads)
     uint64_t *d_btab = nullptr;
     uint64_t btab_cap = 0;

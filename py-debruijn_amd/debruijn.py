@@ -32,7 +32,7 @@ import numpy as np
 import _dbg
 
 __all__ = ["Node", "read_reads", "read_fastq", "read_fasta_records", "wrap_fasta_record", "read_reads_device", "DeviceReads", "construct_graph", "output_contigs",
-           "get_score_device", "score_sequences", "get_kmers", "get_graph_from_kmers"]
+           "get_score_device", "score_sequences", "count_spectrum", "get_kmers", "get_graph_from_kmers"]
 
 
 
@@ -1179,6 +1179,54 @@ def score_sequences(edge_count_table, sequences, k):
                 raise KeyError(s[i:i + k + 1])
             return [int(x) for x in scores]
     return [sum(edge_count_table[s[i:i + k + 1]] for i in range(len(s) - k)) for s in sequences]
+
+
+def count_spectrum(g, edge_count_table, n_bins=256):
+    """Abundance spectrum and degree statistics of the graph ``construct_graph`` returned, as a dict:
+
+      ``edge_hist[c]``  number of (k+1)-mers ``e`` with ``edge_count_table[e] == c`` -- a build at k counts (k+1)-mers, so
+                        this is the exact (k+1)-mer abundance spectrum of the reads: for the 31-mer spectrum build at k = 30;
+      ``node_hist[c]``  number of nodes whose successor counts sum to ``c`` (``len(edges[v])`` before pruningEdges;
+                        ``node_hist[0]``: the nodes without a successor).  That sum is the number of windows that START
+                        at the k-mer, not the k-mer's multiplicity: the last k-mer of a read is not counted;
+      ``D[d]``          number of nodes with ``d`` distinct successors (``Node.outdegree``), uint64[33];
+      ``n_nodes``, ``n_edges``, ``sum_edge_counts``, ``max_edge_count``, ``max_out_weight``, ``n_bins``.
+
+    With ``n_bins = B`` a count ``c`` lands in bin ``min(c, B - 1)``; ``edge_hist[0]`` is always 0; 2 <= B <= 2**20.
+    On the views (or the dicts) ``construct_graph`` of this module returned, while their graph still lives on the device,
+    this is one call (dbg_count_spectrum): nothing of the size of the graph moves, and the dict also holds ``K`` (kept successors per node after pruningEdges, over all nodes),
+    ``pruned``, ``peak_extra_device_bytes`` and ``ms_kernel``.  On plain dicts (the reference's own) it is the loop below -- the statement of the
+    definitions that the device is tested against; ``K`` and ``pruned`` are None there (the dicts of a pruned graph no
+    longer hold the pulled nodes' successors)."""
+    B = int(n_bins)
+    if not 2 <= B <= _dbg.SP_MAX_BINS:
+        raise ValueError("n_bins must be in 2..2**20")
+    store = getattr(edge_count_table, "_s", None)
+    graph = getattr(store, "_graph", None) if type(edge_count_table) is _LazyEdgeCounts else None
+    if graph is not None:
+        if graph.generation != store._generation:
+            raise RuntimeError(_STALE_VIEWS)
+        return graph.count_spectrum(B)
+    V = g[0]
+    graph, state = getattr(V, "_graph", None), getattr(V, "_state", None)
+    if graph is not None and state is not None and type(V) is _Vertices:  # the dicts of a small graph that is still on the device
+        if state.get("generation") != graph.generation:
+            raise RuntimeError(_STALE_VIEWS)
+        return graph.count_spectrum(B)
+    edge_hist, node_hist, deg = np.zeros(B, dtype=np.uint64), np.zeros(B, dtype=np.uint64), np.zeros(33, dtype=np.uint64)
+    weight = dict.fromkeys(V, 0)
+    total = most = 0
+    for e, c in edge_count_table.items():
+        edge_hist[min(c, B - 1)] += 1
+        weight[e[:-1]] += c
+        total += c
+        most = max(most, c)
+    for v, w in weight.items():
+        node_hist[min(w, B - 1)] += 1
+        deg[V[v].outdegree] += 1
+    return {"n_nodes": len(V), "n_edges": len(edge_count_table), "sum_edge_counts": total, "max_edge_count": most,
+            "max_out_weight": max(weight.values(), default=0), "D": deg, "K": None, "pruned": None, "n_bins": B,
+            "edge_hist": edge_hist, "node_hist": node_hist}
 
 
 # ------------------------------------------------------------------------------------------------------------------

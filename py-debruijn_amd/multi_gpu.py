@@ -356,6 +356,14 @@ def sharded_build(g, k, dist, check=True):
     return g
 
 
+def count_spectrum(g, dist, n_bins=256, hists=True):
+    """Collective, after ``sharded_build`` (or ``sharded_build_multipass``): the spectrum and degree statistics of the WHOLE
+    graph on every rank -- ``g.count_spectrum`` on this rank's shard, summed over the ranks (part_traversal.merge_spectrum)."""
+    import part_traversal  # (it imports this module)
+    net = part_traversal._Net(dist, torch.device("cuda", g.sizes_device()))
+    return part_traversal.merge_spectrum(net, g.count_spectrum(n_bins, hists=hists))
+
+
 def _exchange_records(g, k, dist, xc):
     """Steps 1-3 of a sharded build for super-k-mer records split by the 512 level-1 groups: extract, one all-gather
     of what the ranks must know about each other, all-to-all of the records.  -> (received w0, w1, st, recv_counts,

@@ -171,6 +171,37 @@ class _Net:
         return parts.sum(dim=0).cpu().numpy().astype(np.uint64).reshape(arr.shape)
 
 
+def merge_spectrum(net, sp):
+    """Collective.  One rank's ``Graph.count_spectrum`` dict -> the whole graph's, on every rank: bins, degree
+    distributions and the three totals are sums over ranks (every node and edge lives on exactly one), the maxima are
+    maxima, ``pruned`` says that every rank that holds nodes has pruned them; ``ms_kernel`` and
+    ``peak_extra_device_bytes`` are the largest any rank saw."""
+    if net.world == 1:
+        return sp
+    totals = ("n_nodes", "n_edges", "sum_edge_counts")
+    mine = [int(sp["n_bins"]), int(sp["n_nodes"]), int(sp["pruned"]), int(sp["max_edge_count"]), int(sp["max_out_weight"]),
+            int(sp["peak_extra_device_bytes"]), int(sp["ms_kernel"] * 1e6), int("edge_hist" in sp)]
+    seen = net.all_ints(mine)
+    if any(s[0] != mine[0] or s[7] != mine[7] for s in seen):
+        raise RuntimeError(f"count_spectrum: the ranks asked for different bins: {[list(s) for s in seen]}")
+    cols = [sp["D"], sp["K"], np.array([sp[n] for n in totals], dtype=np.uint64)]
+    if "edge_hist" in sp:
+        cols += [sp["edge_hist"], sp["node_hist"]]
+    flat = net.sum_u64(np.concatenate([np.asarray(c, dtype=np.uint64) for c in cols]))
+    out = dict(sp)
+    out["D"], out["K"] = flat[:33].copy(), flat[33:66].copy()
+    for i, n in enumerate(totals):
+        out[n] = int(flat[66 + i])
+    if "edge_hist" in sp:
+        B = mine[0]
+        out["edge_hist"], out["node_hist"] = flat[69:69 + B].copy(), flat[69 + B:69 + 2 * B].copy()
+    out["max_edge_count"], out["max_out_weight"] = max(s[3] for s in seen), max(s[4] for s in seen)
+    out["pruned"] = int(out["n_nodes"] > 0 and all(s[2] for s in seen if s[1]))
+    out["peak_extra_device_bytes"] = max(s[5] for s in seen)
+    out["ms_kernel"] = max(s[6] for s in seen) / 1e6
+    return out
+
+
 class PartTraversal:
     """The traversal state of one process: its handle ``g`` with ``n_passes`` parts (part p = virtual shard rank * P + p)."""
 
@@ -267,6 +298,11 @@ class PartTraversal:
         if scores.size == 0:
             return scores, miss
         return self.net.sum_u64(scores), self.net.min_u64(miss)
+
+    def count_spectrum(self, n_bins=256, hists=True):
+        """Collective.  Edge spectrum, out-weight spectrum and degree distributions of the WHOLE graph on every rank
+        (include/dbg.h: dbg_count_spectrum): one device call over this handle's parts, then the sum over ranks."""
+        return merge_spectrum(self.net, self.g.count_spectrum(n_bins, hists=hists))
 
     # ---- a5 + a6
     def prune(self, threshold):
