@@ -1,5 +1,5 @@
-// Chunked FASTQ ingest (dbg_set_reads_fastq_file): strict four-line records over the staging machinery of the FASTA stream
-// (dbg_fasta.h), with an optional quality mask.
+// Chunked FASTQ ingest (dbg_set_reads_fastq_file): strict four-line records through the chunk pipeline it shares with
+// the FASTA stream (dbg_hip_reads.h), with an optional quality mask.
 //
 // Lines are the project's universal-newline lines.  Line g of the range (counted from its first record) is a header
 // (g % 4 == 0), a sequence (1), a separator (2) or a quality line (3): the kind of a byte is a COUNT of line starts, not a

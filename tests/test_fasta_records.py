@@ -127,6 +127,23 @@ def test_sequence_before_the_first_header_fails_with_its_position_and_the_handle
     assert e.value.code == _dbg.DBG_E_ARG and "begin" in str(e.value)
 
 
+def test_more_records_in_the_first_chunk_than_the_first_offsets_hold(g, tmp_path):
+    """The offsets start with 65 536 entries at the most and are sized from the records seen only from the second chunk on:
+    70 000 records in the first chunk make the ingest grow them and parse the chunk a second time."""
+    n = 70_000
+    data = b"".join(b">\n" + s + b"\n" for s in (b"ACGT", b"CGTA", b"GTAC", b"TACG")) * (n // 4)
+    p = str(tmp_path / "many.fasta")
+    with open(p, "wb") as fh:
+        fh.write(data)
+    want = prod.parse_fasta_records(data)
+    assert len(want) == n and want[:5] == [b"ACGT", b"CGTA", b"GTAC", b"TACG", b"ACGT"]
+    for how in (0, None):  # streamed from the file at the default chunk size, and the one-image call
+        assert ingest(g, p, data, how) == want, how
+        check_stats(g, data)
+        st = g.ingest_stats()
+        assert st["chunks"] == 1 and st["n_reads"] == n
+
+
 # ---- 2. chunk, word and block borders -------------------------------------------------------------------------------------
 def bases(rng, n):
     return bytes(rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), n))

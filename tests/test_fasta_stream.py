@@ -189,6 +189,22 @@ def test_seeded_fuzz_of_files_chunks_and_splits(tmp_path):
 
 
 @pytest.mark.gpu
+def test_more_reads_in_the_first_chunk_than_the_first_offsets_hold(tmp_path):
+    """The offsets start with 65 536 entries at the most and are sized from the reads seen only from the second chunk on:
+    70 000 reads in the first chunk make the ingest grow them and parse the chunk a second time."""
+    n = 70_000
+    data = b"".join(b">\n" + s + b"\n" for s in (b"ACGT", b"CGTA", b"GTAC", b"TACG")) * (n // 4)
+    p = write(tmp_path, "many", data)
+    want = orc.read_reads(p)
+    assert len(want) == n and want[:5] == ["ACGT", "CGTA", "GTAC", "TACG", "ACGT"]
+    wb, wo, wsum = one_shot(data)
+    b, o, s, st = streamed(p, stats=True)
+    assert np.array_equal(o, wo) and np.array_equal(b, wb) and s == wsum
+    assert [r.decode() for r in as_list(b, o)] == want
+    assert st["chunks"] == 1 and st["n_reads"] == n and st["bytes_read"] == len(data)
+
+
+@pytest.mark.gpu
 def test_errors_and_empty_ranges(tmp_path):
     import _dbg
     p = write(tmp_path, "small", ">a\nACGT\n>b\nTTGA\n")

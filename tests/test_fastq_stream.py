@@ -382,6 +382,46 @@ def test_malformed_files_fail_and_leave_the_handle_usable(name, tmp_path):
 
 
 @pytest.mark.gpu
+def test_more_records_in_the_first_chunk_than_the_first_offsets_hold(tmp_path):
+    """The offsets start with 65 536 entries at the most and are sized from the records seen only from the second chunk on:
+    70 000 records in the first chunk make the ingest grow them and parse the chunk a second time."""
+    import debruijn as prod
+    n = 70_000
+    data = b"".join(b"@\n" + s + b"\n+\nIIII\n" for s in (b"ACGT", b"CGTA", b"GTAC", b"TACG")) * (n // 4)
+    p = write(tmp_path, "many", data)
+    want = prod.parse_fastq(data)
+    assert len(want) == n and want[:5] == [b"ACGT", b"CGTA", b"GTAC", b"TACG", b"ACGT"]
+    for q in (0, 20):
+        b, o, _, st, fq = streamed(p, q=q)
+        assert as_list(b, o) == want, q
+        assert st["chunks"] == 1 and st["n_reads"] == fq["n_records"] == n and st["n_bases"] == 4 * n, q
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("q", [0, 20])
+def test_a_read_of_more_than_half_its_record_grows_the_buffers_until_the_next_header_reports_it(q, tmp_path):
+    """The bases (and, under a mask, the quality bytes) have room for half the range.  A 64-base read with a one-byte quality
+    line outgrows it in a chunk that ends before the next header: the buffers grow and the chunk runs again, and the chunk
+    with the next header reports the record.  At the default chunk size the report comes with the first parse."""
+    import _dbg
+    import debruijn as prod
+    bad = write(tmp_path, "long_read_short_quality", "@a\n" + "ACGT" * 16 + "\n+\nI\n@b\nACGT\n+\nIIII\n")
+    good = write(tmp_path, "good", PLAIN)
+    with pytest.raises(ValueError) as e:
+        prod.read_fastq(bad, min_quality=q)
+    assert (e.value.record, e.value.kind) == (0, "length mismatch")
+    g = _dbg.Graph()
+    for chunk in (16, 64, 0):
+        with pytest.raises(_dbg.DbgError) as e:
+            g.set_reads_fastq_file(bad, chunk_bytes=chunk, min_quality=q)
+        assert e.value.code == _dbg.DBG_E_ARG and "record 0: length mismatch" in str(e.value), (chunk, str(e.value))
+        assert g.sizes()["n_reads"] == 0 and g.sizes()["n_bytes"] == 0
+        g.set_reads_fastq_file(good, chunk_bytes=chunk, min_quality=q)
+        assert as_list(*g.copy_reads()) == [b"ACGTACGTTG", b"TTGACCA"]
+    g.close()
+
+
+@pytest.mark.gpu
 def test_errors_and_empty_ranges(tmp_path):
     import _dbg
     p = write(tmp_path, "small", PLAIN)
