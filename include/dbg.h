@@ -173,7 +173,9 @@ int dbg_abi_version(void);
  * dbg_get_counter; "wide_engine" 0: k > 31 on the global-table engine of round 1;
  * "extract_generic" 1: the window-minimum-through-LDS extraction kernels; "extract_presplit" f0 in 0..6: dbg_build's
  * extraction (13 <= k <= 31 over ACGT) writes its records pre-split by the top f0 bits of the bucket hash so that level 1 of
- * the multisplit has 2^f0 times fewer children per group (0: one segment per workgroup); "shard_stamp64" 1: dbg_shard_extract hands out
+ * the multisplit has 2^f0 times fewer children per group (0: one segment per workgroup);
+ * "extract_grid" 0..65535: the workgroups of that pre-split extraction (0: four per CU; a whole multiple of it where a
+ * sub-segment would otherwise outgrow one super-chunk of the multisplit; tests and A/B); "shard_stamp64" 1: dbg_shard_extract hands out
  * 64-bit rank-local stamps; "target_distinct": mean distinct k-mers per bucket the geometry aims at (0 = default);
  * "lookup_index" 1: the query calls (dbg_lookup_nodes, dbg_score_sequences) find nodes through the sorted index even where
  * the build's directory would answer (test hook: both ways must agree);
@@ -487,6 +489,8 @@ int dbg_get_stats(dbg_t *h, dbg_stats_t *out);
  * "extract_presplit_fallbacks": builds whose pre-split extraction overflowed a sub-segment and ran again without the split.
  * "extract_presplit_rehists": builds whose level 1 took another width than the pre-split extraction had counted its
  *   records for, so that the level ran its histogram pass after all.
+ * "ms_scatter_small" / "ms_scatter_wide": multisplit levels that ran the scatter kernel of a small fan-out (up to 64 children
+ *   a group) / the wide one.
  * "refine_crowded" / "pull_crowded": dbg_refine_edge_order / dbg_mark_pull_reads calls (k <= 31) whose per-range kernel met a
  *   range with more multi-successor / branch nodes than it has slots for, so that the pass over the reads ran instead.
  * "resolve_direct_hits" / "resolve_keyed": cross-bucket successor queries (dbg_shard_answer's included) answered from the

@@ -169,7 +169,9 @@ class WalkBlock(C.Structure):
 # lookup_*: which way the query calls found their nodes (the build's directory / the sorted index) and how often such an
 # index was built
 # count_*: the rare paths the LDS count kernels took in the last build (EV_* below), its sub-range passes and repeated launches
-COUNTERS = ("extract_presplit_fallbacks", "extract_presplit_rehists", "resolve_direct_hits", "resolve_keyed",
+# ms_scatter_*: multisplit levels of the handle's builds by the scatter kernel they ran (small fan-out, up to 64 children / wide)
+COUNTERS = ("extract_presplit_fallbacks", "extract_presplit_rehists", "ms_scatter_small", "ms_scatter_wide",
+            "resolve_direct_hits", "resolve_keyed",
             "refine_crowded", "pull_crowded", "lookup_index_builds", "lookup_dir_calls", "lookup_index_calls",
             "part_lookup_calls", "count_events", "count_extra_ranges", "count_retries_query_cap", "count_retries_node_cap",
             "count_retries_counter16")

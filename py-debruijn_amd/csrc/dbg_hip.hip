@@ -1408,6 +1408,7 @@ extern "C" int dbg_set_option(dbg_t *h, const char *name, int64_t value) {
     if (n == "shard_stamp64" && (value == 0 || value == 1)) { h->shard_stamp64 = (int)value; return DBG_OK; }
     if (n == "extract_generic" && (value == 0 || value == 1)) { h->extract_generic = (int)value; return DBG_OK; }
     if (n == "extract_presplit" && value >= 0 && value <= SK_PS_MAX_F0) { h->extract_presplit = (int)value; return DBG_OK; }
+    if (n == "extract_grid" && value >= 0 && value <= 65535) { h->extract_grid = (int)value; return DBG_OK; }
     if (n == "refine_streaming" && (value == 0 || value == 1)) { h->refine_streaming = value != 0; return DBG_OK; }
     if (n == "walk_jump_min_nodes" && value >= 0) { h->walk_jump_min = (uint64_t)value; return DBG_OK; }
     if (n == "wide_engine" && (value == 0 || value == 1)) { h->wide_engine = (int)value; return DBG_OK; }
@@ -2353,6 +2354,8 @@ extern "C" int dbg_get_counter(dbg_t *h, const char *name, uint64_t *out) {
     const std::string n(name);
     if (n == "extract_presplit_rehists") { *out = h->presplit_rehists; return DBG_OK; }
     if (n == "extract_presplit_fallbacks") { *out = h->presplit_fallbacks; return DBG_OK; }
+    if (n == "ms_scatter_small") { *out = h->ms_scatter_small; return DBG_OK; }
+    if (n == "ms_scatter_wide") { *out = h->ms_scatter_wide; return DBG_OK; }
     if (n == "refine_crowded") { *out = h->refine_crowded; return DBG_OK; }
     if (n == "pull_crowded") { *out = h->pull_crowded; return DBG_OK; }
     if (n == "resolve_direct_hits") { *out = h->resolve_direct_hits; return DBG_OK; }
@@ -2848,12 +2851,23 @@ static int multisplit_level(dbg *h, const uint64_t *p_start, const uint64_t *p_c
     const uint64_t n_child = (uint64_t)(n_seg / spg) * nb;
     hipLaunchKernelGGL(k_ms_children, dim3(grid_for(n_child, 256)), dim3(256), 0, h->stream, P, offs, nb, total, c_start,
                        c_cnt);
-    if (nsc) {
+    // a small fan-out takes the scatter with 2048-record rounds, three workgroups to a CU (dbg_sk.h); the levels that
+    // change the stamp type on the way keep the wide one
+    constexpr bool HAS_SMALL = std::is_same<ST, STI>::value && STHI == 0;
+    bool small = false;
+    if constexpr (HAS_SMALL) small = nb <= MS_S_NB;
+    if (nsc && small) {
+        if constexpr (HAS_SMALL)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ms_scatter_s<ST, HAS_ST>), dim3((unsigned)nsc), dim3(MS_NT), 0, h->stream, P, in_w0,
+                               in_w1, in_st, seg_add, shift, nb, fbits, offs, out_w0, out_w1, out_st);
+        ++h->ms_scatter_small;
+    } else if (nsc) {
         auto kern = k_ms_scatter<ST, HAS_ST, STI, STHI>;
         const size_t lds = sizeof(MsLds<ST>);
         HIPCHK(h, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, dim3((unsigned)nsc), dim3(MS_NT), lds, h->stream, P, in_w0, in_w1, in_st, seg_add, shift, nb,
                            fbits, offs, out_w0, out_w1, out_st);
+        ++h->ms_scatter_wide;
     }
     HIPCHK(h, hipGetLastError());
     return DBG_OK;
@@ -2923,10 +2937,15 @@ static int sk_extract(dbg *h, int k, uint64_t *w0[2], uint64_t *w1[2], ST *st[2]
         const uint64_t tpw_max = std::max<uint64_t>(1, (uint64_t)((double)(MS_SC - 64) / per_tile));
         // as few workgroups as that allows, but one resident wave of them (DBG_EXW_WAVES per CU) where there are the tiles:
         // long sub-segments -- level 1 runs one scatter workgroup per sub-segment, and 1 000 records do not pay for one
-        // (768 on the 256 CUs of an MI355X; DESIGN.md 3 has 1024 and 1536 measured beside it, on that chip only)
+        // (1024 on the 256 CUs of an MI355X; DESIGN.md 3 has 768 and 1536 measured beside it, on that chip only).
+        // Option "extract_grid" names the number instead.
         int n_cu = 0;
         HIPCHK(h, hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->device));
-        n_wg = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(tiles, (uint64_t)n_cu * DBG_PS_WG_PER_CU), (tiles + tpw_max - 1) / tpw_max);
+        const uint64_t want_wg = h->extract_grid ? (uint64_t)h->extract_grid : (uint64_t)n_cu * DBG_PS_WG_PER_CU;
+        n_wg = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(tiles, want_wg), (tiles + tpw_max - 1) / tpw_max);
+        // where the sub-segment limit asks for more than one resident wave (k = 21: 1205), whole waves (2048): a part-filled
+        // last round costs the extraction as much as a full one
+        if (n_wg > want_wg) n_wg = (uint32_t)std::min<uint64_t>(tiles, (n_wg + want_wg - 1) / want_wg * want_wg);
         tiles_per_wg = (tiles + n_wg - 1) / n_wg;
         seg_cap = std::min<uint64_t>(MS_SC, (uint64_t)((double)tiles_per_wg * per_tile) + 64);
         n_seg = (uint64_t)n_wg * F0;

@@ -257,6 +257,8 @@ struct dbg {
     // were repeated, by reason.  A multi-pass parent or a shard holds the OR / the sums of its parts.
     struct CountPaths { uint64_t events = 0, extra_ranges = 0, retries_query_cap = 0, retries_node_cap = 0, retries_counter16 = 0; } count_paths;
     uint64_t presplit_rehists = 0;  // builds whose level 1 took another width than the pre-split extraction counted for, so it ran its histogram pass (dbg_get_counter)
+    int extract_grid = 0;  // option: workgroups of a pre-split extraction (0: DBG_PS_WG_PER_CU per CU); the sub-segment limit may still ask for more (tests, A/B)
+    uint64_t ms_scatter_small = 0, ms_scatter_wide = 0;  // multisplit levels of this handle that ran the small-fan-out / the wide scatter (dbg_get_counter)
     uint64_t presplit_fallbacks = 0;  // builds whose pre-split extraction overflowed a sub-segment and ran again without the split (dbg_get_counter)
     uint64_t refine_crowded = 0, pull_crowded = 0;  // dbg_refine_edge_order / dbg_mark_pull_reads calls whose per-range kernel met a crowded range and fell back to the pass over the reads (dbg_get_counter)
     uint64_t sk_n_ranges = 0, sk_n_buckets = 0;

@@ -219,7 +219,7 @@ struct SkLdsW {
 };
 
 #ifndef DBG_EXW_WAVES
-#define DBG_EXW_WAVES 3
+#define DBG_EXW_WAVES 4  // workgroups per CU: every instantiation stays below 128 VGPRs, and 4 x 35.3 KB of LDS fit
 #endif
 // PS (pre-split, option "extract_presplit"): the workgroup writes its records into 2^f0 sub-segments, one per value of the
 // top f0 bits of the bucket hash, laid out group-major (sub-segment (child c, workgroup g) = index c * gridDim.x + g, seg_cap
@@ -421,13 +421,24 @@ constexpr int MS_CH = DBG_MS_CH;      // records sorted per LDS round with 64-bi
 // ... and with 32-bit stamps (20 B per record: 6144 fit): a child gets chunk / fan-out records per round in one piece --
 // 12 instead of 8 at a fan-out of 512, 96-byte instead of 64-byte pieces of w0 / w1 (partition 4.82 -> 4.57 ms)
 template <class ST> struct MsChunk { static constexpr int CH = sizeof(ST) == 8 ? MS_CH : MS_CH + MS_CH / 2; };
-constexpr int MS_SC = 32768;          // records per super-chunk
+// records per super-chunk.  (With 32-bit stamps that is 5 1/3 chunks; 6 x 6144 = 36 864 was measured: level 2 at k = 31
+// gains 0.06 ms, the two-word partition at k = 63 loses 0.05 ms -- DESIGN.md 3.)
+constexpr int MS_SC = 32768;
 constexpr int MS_MAX_NB = 1024;
 #ifndef DBG_MS_NT
 #define DBG_MS_NT 512
 #endif
-constexpr int MS_NT = DBG_MS_NT;      // threads of the scatter workgroup: its 90 KB of LDS allow one per CU, so the
-                                      // workgroup itself has to bring the waves that hide the record loads
+constexpr int MS_NT = DBG_MS_NT;      // threads of the scatter workgroup: its 136 KB of LDS (112 KB with 64-bit stamps)
+                                      // allow one per CU, so the workgroup itself has to bring the waves that hide the
+                                      // record loads
+// Small fan-out (nb <= MS_S_NB: level 1 behind a pre-split extraction splits 32 or 64 ways): 2048-record chunks still
+// give a child whole 128-byte lines per round (64 records: 512 B of w0 / w1), and with per-child arrays of 64 entries the
+// workgroup takes 41 KB of LDS (49 KB with 64-bit stamps) -- three workgroups share a CU, and one loads while another
+// writes out.
+constexpr int MS_S_NB = 64;           // a child is a lane of the wave (k_ms_scatter_s)
+constexpr int MS_S_CH = 2048;
+constexpr int MS_S_WG_PER_CU = 3;
+static_assert(MS_S_NB <= 64 && MS_SC % MS_S_CH == 0, "small fan-out: one lane per child, whole rounds per super-chunk");
 
 // Input of one multisplit level: `n_seg` contiguous segments of the record arrays, in groups of `spg`
 // consecutive segments: all segments in ONE group (level 1: the per-workgroup output segments of
@@ -651,6 +662,98 @@ __global__ __launch_bounds__(MS_NT) void k_ms_scatter(MsParents P, const uint64_
         atomicAdd(&g_ms_prof[7], 1ull);
     }
 #endif
+}
+
+// The scatter of a small fan-out (nb <= 64; constants above).  A child is a lane: lane b of EVERY wave keeps child b's global
+// cursor and its count so far in registers, and the per-round scan is a wave scan that each wave does for itself -- no
+// per-child array but the counters, which run on over the rounds of the super-chunk (a record's rank in its child then
+// places it in LDS and in the output alike).  Two barriers a round: the counters are read behind the first and written
+// again behind the second only, and the write-out of one round is parted from the placement of the next by the next
+// round's first barrier, so a wave that has written out goes on to load at once.
+template <class ST>
+struct MsLdsS {
+    uint64_t w0[MS_S_CH];
+    uint64_t w1[MS_S_CH];
+    ST st[MS_S_CH];
+    uint32_t hist[64];   // records of the super-chunk per child so far
+};
+
+template <class ST, bool HAS_ST>
+__global__ __launch_bounds__(MS_NT, MS_S_WG_PER_CU * MS_NT / 256) void k_ms_scatter_s(
+    MsParents P, const uint64_t *__restrict__ in_w0, const uint64_t *__restrict__ in_w1, const ST *__restrict__ in_st,
+    const uint64_t *__restrict__ seg_add, int shift, int nb, int fbits, const uint64_t *__restrict__ offs, uint64_t *out_w0,
+    uint64_t *out_w1, ST *out_st) {
+    __shared__ MsLdsS<ST> s;
+    constexpr int CH = MS_S_CH, R = CH / MS_NT;
+    constexpr uint64_t SC = MS_SC;
+    static_assert(CH % MS_NT == 0 && MS_S_WG_PER_CU * sizeof(MsLdsS<ST>) <= 160 * 1024, "small-fan-out chunk");
+    uint32_t seg;
+    uint64_t sidx;
+    ms_locate(P, blockIdx.x, &seg, &sidx);
+    const ST st_add = (HAS_ST && seg_add) ? (ST)seg_add[seg] : (ST)0;
+    const uint32_t grp = seg / P.spg;
+    const uint64_t g_lo = P.sc_pre[grp * P.spg], g_hi = P.sc_pre[(grp + 1) * P.spg];
+    const uint64_t nsc = g_hi - g_lo, gidx = (uint64_t)blockIdx.x - g_lo;
+    const int lane = threadIdx.x & 63;
+    const uint64_t run = lane < nb ? offs[(uint64_t)nb * g_lo + (uint64_t)lane * nsc + gidx] : 0;  // child `lane`: its first output index
+    uint32_t prev = 0;                                                                            // ... and its records before this round
+    if (threadIdx.x < 64) s.hist[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t beg = P.start[seg] + sidx * SC;
+    const uint64_t end = min(P.start[seg] + P.cnt[seg], beg + SC);
+    for (uint64_t c0 = beg; c0 < end; c0 += CH) {
+        const int n = (int)min((uint64_t)CH, end - c0);
+        uint64_t r0[R], r1[R];
+        ST rs[R];
+        uint32_t rk[R];  // rank of the record among its child's records of the whole super-chunk
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const int q = i * MS_NT + threadIdx.x;
+            r1[i] = 0;
+            if (q < n) {
+                r0[i] = in_w0[c0 + q];
+                r1[i] = in_w1[c0 + q];
+                if (HAS_ST) rs[i] = in_st[c0 + q] + st_add;
+                rk[i] = atomicAdd(&s.hist[ms_child(r1[i], shift, nb, fbits)], 1u);
+            }
+        }
+        __syncthreads();
+        const uint32_t cum = s.hist[lane];  // lanes from nb on: 0
+        const uint32_t cnt = cum - prev;
+        uint32_t inc = cnt;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += o;
+        }
+        const uint32_t ex = inc - cnt;       // first LDS slot of the child this round
+        const uint32_t slot0 = ex - prev;    // LDS slot = slot0 + rank (mod 2^32)
+#pragma unroll
+        for (int i = 0; i < R; ++i) {  // (the shuffles run in all lanes: a lane without a record asks for child 0)
+            const int q = i * MS_NT + threadIdx.x;
+            const uint32_t b = ms_child(r1[i], shift, nb, fbits);
+            const uint32_t d0 = __shfl(slot0, (int)b, 64);
+            if (q < n) {
+                const uint32_t d = d0 + rk[i];
+                s.w0[d] = r0[i];
+                s.w1[d] = r1[i];
+                if (HAS_ST) s.st[d] = rs[i];
+            }
+        }
+        __syncthreads();
+        const unsigned long long gb = run + prev - ex;  // output index = gb + LDS slot (mod 2^64)
+        for (int q0 = 0; q0 < n; q0 += MS_NT) {
+            const int q = q0 + threadIdx.x;
+            const uint64_t x1 = q < n ? s.w1[q] : 0;
+            const uint64_t g = __shfl(gb, (int)ms_child(x1, shift, nb, fbits), 64) + (uint64_t)q;
+            if (q < n) {
+                out_w0[g] = s.w0[q];
+                out_w1[g] = x1;
+                if (HAS_ST) out_st[g] = s.st[q];
+            }
+        }
+        prev = cum;
+    }
 }
 
 
